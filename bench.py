@@ -1,6 +1,7 @@
 """bench.py -- training samples/sec of the multimodal-VAE step on N MI355X (default: BASELINE.json configs[1]).
 
-    python bench.py --gpus 1 --steps 200 --warmup 20 [--config cfg1|cfg2|cfg3|cfg4|cfg5|mnistsvhn]
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--config cfg1|cfg2|cfg3|cfg4|cfg5|mnistsvhn] [--full]
+                    [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -8,6 +9,11 @@ One step = forward + backward + Adam(amsgrad) of the mixer on one synthetic batc
 Default workload cfg2 = MoPoE (CNN2 image tower + TxtTransformer text tower, n_latents 32), 128 samples per GPU
 (64x64x3 image + 32-token text).  N > 1: one process per GPU, weak scaling, ONE RCCL all-reduce of the flat gradient
 buffer per step (multimodal_vae_comparison_amd/parallel.py).  Prints ONE JSON line (rank 0).
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else on one GPU:
+the first window's time, three repeats of the timed region, the dominant kernel's roofline, the input-pipeline and
+large-batch figures (cfg2) and the CPU baseline.  --dump-outputs DIR writes what the last timed step computed (the
+step's returned losses, the parameters after its Adam update, its gradients) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -43,8 +49,14 @@ def parse():
     p.add_argument("--config", default="cfg2", help="BASELINE workload: cfg1..cfg5 | mnistsvhn (default cfg2, the one "
                                                     "the metric is quoted on)")
     p.add_argument("--batch", type=int, default=None, help="samples per GPU (default: the workload's)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="skip the non-headline figures (input pipeline, large batch)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline (one GPU): first window, spread, roofline, extras, "
+                        "CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-extras", action="store_true",
+                   help="with --full: skip the non-headline figures (input pipeline, large batch)")
     p.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                    help="process-group backend for N > 1: nccl = RCCL over xGMI (one GPU per rank); gloo moves the CUDA "
                         "buffers through the host and lets several ranks share one GPU (N > 1 readiness test on a "
@@ -387,6 +399,46 @@ def _timed(tr, steps, warmup, path_world, barrier, pre=None):
     return time.perf_counter() - t0, out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 4 << 20        # a larger array is written as a fixed, seeded sample of this many of its elements
+
+
+def step_outputs(tr, out):
+    """name -> tensor: what the last step handed its caller (the objective's dict) and what it left in the trainer (the
+    parameters after its Adam update, its gradients: the flat buffers)"""
+    arrays = {}
+    for k, v in out.items():
+        if torch.is_tensor(v):
+            arrays[k] = v
+        elif isinstance(v, (list, tuple)):
+            for i, t in enumerate(v):
+                if torch.is_tensor(t):
+                    arrays[f"{k}_{i}"] = t
+    arrays["parameters"] = tr.flat.data
+    arrays["gradients"] = tr.flat.grad
+    return arrays
+
+
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy per array: float64 stays float64, integers become float64, everything else float32; an array of
+    more than DUMP_MAX_ELEMS elements is flattened and sampled at sorted indices of a seed-0 permutation (the same
+    indices for the same size, run to run and build to build)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        wide = t.dtype == torch.float64 or not (t.is_floating_point() or t.dtype == torch.bool)
+        a = t.cpu().to(torch.float64 if wide else torch.float32).numpy()
+        total += a.nbytes
+        if total > DUMP_BUDGET_BYTES:
+            raise RuntimeError(f"--dump-outputs: more than {DUMP_BUDGET_BYTES >> 20} MB at '{name}'")
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _build(name, batch, dev, rank, world, path_world, input_ring=None):
     from multimodal_vae_comparison_amd import parallel
     from multimodal_vae_comparison_amd.models.trainer import MultimodalVAE
@@ -465,6 +517,8 @@ def main():
     # (round 6) the caller's protocol on the fresh graph is measured FIRST and reported beside the headline
     # (`first_window_ms_per_step`: W warm-ups, K timed steps, nothing in front), so that lines of different rounds can be
     # compared on either footing; `untimed_steps_before_timed_region` is everything that ran before the headline's K steps.
+    # A plain run replays the first window too (the headline's K steps start from the same state in either mode); only
+    # --full reports its time.
     settle = max(0, a.settle)
     first_dt = None
     if settle > 0:
@@ -473,9 +527,11 @@ def main():
             tr.fused_step(path_world)
         barrier()
     dt, out = _timed(tr, a.steps, a.warmup, path_world, barrier)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(tr, out), a.dump_outputs)
     if first_dt is None:
         first_dt = dt
-    if world > 1:
+    if world > 1 and a.full:
         t = torch.tensor([first_dt], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         first_dt = float(t.item())
@@ -499,7 +555,6 @@ def main():
         res = {"metric": METRIC.get(a.config, f"training samples/sec, {a.config} (fwd+bwd+Adam)"), "value": round(sps, 1),
                "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
                "ms_per_step": round(1e3 * dt / a.steps, 4),
-               "first_window_ms_per_step": round(1e3 * first_dt / a.steps, 4),
                "untimed_steps_before_timed_region": (a.warmup + a.steps + settle if settle > 0 else 0) + a.warmup,
                "higher_is_better": True, "scaling": "weak",
                "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -515,6 +570,8 @@ def main():
                                         "form each fp32 product from six bf16 MFMAs on three exact bf16 terms per operand "
                                         "(error vs fp64 as the fp32-MFMA kernels, DESIGN 5d)"},
                "final_loss": round(loss, 3)}
+        if a.full:
+            res["first_window_ms_per_step"] = round(1e3 * first_dt / a.steps, 4)
         if world > 1 or path_world > 1:
             # top level, so that the driver's scaling record can read them: which collective path the step took and
             # whether the replicas still hold bit-identical parameters after the timed steps
@@ -539,7 +596,7 @@ def main():
             res["n_collectives"] = stager.n_collectives if (in_graph and stager is not None) else 1
             res["replicas_in_sync"] = in_sync
             res["config"]["collective"] = res["collective"]["what"]
-    if world == 1 and rank == 0:
+    if a.full and world == 1 and rank == 0:
         # the timed region above is short (K x ~0.4 ms); three more timed repeats of the same K steps say how much one
         # reading moves on THIS box (box-to-box spread is larger: profiles/ keeps the builder boxes' lines)
         reps = [round(1e3 * _timed(tr, a.steps, 0, path_world, barrier)[0] / a.steps, 4) for _ in range(3)]

@@ -17,6 +17,7 @@ from conftest import GOLDEN_DIR
 
 with open(os.path.join(GOLDEN_DIR, "shipped_configs.json")) as f:
     SHIPPED = json.load(f)
+SHIPPED_YML_DIR = os.path.join(GOLDEN_DIR, "shipped_configs")
 
 # file -> what construction must do.  ("ok", mixer class, checks) or ("error", substring of the message)
 EXPECT = {
@@ -95,9 +96,11 @@ def test_vilanro_config_with_the_plain_conv_encoder(tmp_path):
     assert all(v.ltype == "optimal_sigma" for v in m.vaes.values())
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/multimodal_compare/configs"), reason="reference tree absent")
 def test_fixture_matches_the_reference_files():
-    """in the build container: the JSON fixture is exactly what the reference's files parse to"""
+    """the JSON fixture is exactly what the reference's files parse to (tests/golden/shipped_configs/: the shipped
+    configs/config_*.yml, copied unmodified by make_config_fixture.py)"""
+    names = sorted(f for f in os.listdir(SHIPPED_YML_DIR) if f.endswith(".yml"))
+    assert names == sorted(SHIPPED)
     for name, rec in SHIPPED.items():
-        with open(os.path.join("/root/reference/multimodal_compare/configs", name)) as f:
+        with open(os.path.join(SHIPPED_YML_DIR, name)) as f:
             assert yaml.safe_load(f) == rec["config"], name
