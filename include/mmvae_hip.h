@@ -486,7 +486,8 @@ int mmvae_lincomb_rowptrs_bwd(const mmvae_gptrs_t* gout, const float* W_host, co
 
 /* MoE ELBO (models/mmvae_models.py:61-77): wc = exp(lw) * r;  loss = (sum_n W_n rowsum_n + n_nz beta sum kld) / M
  * where n_nz counts the rows whose weighted sum is not exactly 0 (the reference's `lp.sum() != 0` filter and the
- * broadcast in BaseObjective.elbo).  out[0] = loss, out[1] = n_nz (kept for the backward). */
+ * broadcast in BaseObjective.elbo).  out (2 + n_rows floats): out[0] = loss, out[1] = n_nz, out[2 + n] = 1 if row n
+ * is kept, else 0 (kept for the backward: a dropped row's gradient is 0). */
 int mmvae_expmul_fwd(const float* lw, const float* r, float* out, int n, mmvae_stream_t stream);
 int mmvae_expmul_bwd(const float* lw, const float* r, const float* g, float* dlw, float* dr, int n,
                      mmvae_stream_t stream);

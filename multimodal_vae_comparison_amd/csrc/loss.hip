@@ -806,7 +806,8 @@ extern "C" int mmvae_lincomb_rowptrs_bwd(const mmvae_gptrs_t* gout, const float*
 //   wc[b] = exp(lw[b]) * r[b]                                  (importance-weighted cross term)
 //   loss  = ( sum_n w_n rowsum_n + n_nz * beta * sum kld ) / M,   n_nz = #rows with w_n rowsum_n != 0:
 //   the reference drops rows whose sum is exactly 0 (`lp.sum() != 0`, a host sync there) and its broadcast
-//   subtracts beta*kld.sum() once per surviving row -- reproduced on the device, no sync.
+//   subtracts beta*kld.sum() once per surviving row -- reproduced on the device, no sync.  A dropped row is not part
+//   of the reference's loss at all: its gradient is 0 (the forward's keep flags out[2 + n], read by the backward).
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void expmul_kernel(const float* __restrict__ lw, const float* __restrict__ r,
                                                      const float* __restrict__ g, float* __restrict__ o0,
@@ -845,6 +846,7 @@ __global__ __launch_bounds__(256) void moe_elbo_fwd_kernel(const float* __restri
     a = block_sum_256(a, red) * W.w[n];
     total += a;
     nnz += (a != 0.f) ? 1.f : 0.f;
+    if (threadIdx.x == 0) out[2 + n] = (a != 0.f) ? 1.f : 0.f;   // keep flag: a dropped row gets no gradient
   }
   float k = 0.f;
   for (int i = threadIdx.x; i < M * B; i += 256) k += kld[i];
@@ -860,7 +862,7 @@ __global__ __launch_bounds__(256) void moe_elbo_bwd_kernel(const float* __restri
                                                            float beta) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const float gg = g[0] / (float)M;
-  if (i < n_rows * B) drows[i] = gg * W.w[i / B];
+  if (i < n_rows * B) drows[i] = gg * W.w[i / B] * out[2 + i / B];
   if (i < M * B) dkld[i] = gg * out[1] * beta;
 }
 extern "C" int mmvae_moe_elbo_fwd(const float* rows, const float* W_host, const float* kld, float* out, int n_rows,

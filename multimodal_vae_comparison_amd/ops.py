@@ -1996,7 +1996,8 @@ class ExpMul(Function):
 
 
 class MoeElbo(Function):
-    """loss = (sum_n W_n sum_b rows_n[b] + n_nz * beta * sum kld) / M  (see mmvae_moe_elbo_fwd)"""
+    """loss = (sum_n W_n sum_b rows_n[b] + n_nz * beta * sum kld) / M  (see mmvae_moe_elbo_fwd); a row whose weighted
+    sum is exactly 0 is dropped, as the reference's `lp.sum() != 0` filter does, and gets a zero gradient"""
 
     @staticmethod
     def forward(ctx, kld, W, beta, M, *rows):
@@ -2006,7 +2007,7 @@ class MoeElbo(Function):
         torch.stack(rows, out=V)
         kld = H.f32c(kld)
         flat = (H.c_f * n)(*[float(x) for x in W])
-        out = torch.empty(2, device=V.device)
+        out = torch.empty(2 + n, device=V.device)      # loss, n_nz, a keep flag per row
         _call("mmvae_moe_elbo_fwd", H.ptr(V), flat, H.ptr(kld), H.ptr(out), n, M, B, float(beta), H.stream())
         ctx.save_for_backward(out)
         ctx.cfg = (flat, n, M, B, float(beta), tuple(kld.shape))
