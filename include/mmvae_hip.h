@@ -761,6 +761,36 @@ int mmvae_laplace_logratio_bwd(const float* packed_r, const float* z, const floa
 int mmvae_rand_laplace(float* out, long n, uint32_t* state, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Held-out log-likelihood estimation (TorchMMVAE.estimate_log_likelihood; csrc/loglik.hip).  Forward only.
+ * Mixture proposal q(z) = (1/C) sum_c q_c(z), q_c = Normal | Laplace(loc_c, scale_c) (bit c of laplace_mask), prior
+ * p(z) = Normal | Laplace(prior_loc (D) or NULL = 0, softmax(theta) D).
+ *   comps (C,B,2D) = [loc | scale] per component;  stratified: draw k0 + k comes from component (k0 + k) % C,
+ *   z[k,b,:] = loc_c[b,:] + scale_c[b,:] * e[k,b,:]  (k = 0 .. Kc-1: chunk [k0, k0 + Kc) of a larger draw);
+ *   e: eps (Kc,B,D) given, or eps = NULL and rng_state = the mmvae_randn / mmvae_rand_laplace generator state: element
+ *   (k0 + k) B D + b D + d of the current draw of the component's family (the convention of mmvae_poe_reparam_kl_fwd),
+ *   so a chunk repeats the matching slice of the whole draw; advance != 0: this launch bumps the call counter when it
+ *   is done (pass it with the LAST chunk of a draw).
+ *   lw0 (Kc,B) = sum_d log p(z[k,b,d]) - log((1/C) sum_c exp sum_d log q_c(z[k,b,d]))    (log-sum-exp form)
+ * C <= MMVAE_MIX_MAX_COMPONENTS, D <= 256; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_MIX_MAX_COMPONENTS 8
+int mmvae_mix_ksample_logw_fwd(const float* comps, unsigned laplace_mask, const float* theta, const float* prior_loc,
+                               int prior_laplace, const float* eps, uint32_t* rng_state, int advance, float* z,
+                               float* lw0, int C, int Kc, int k0, int B, int D, mmvae_stream_t stream);
+/* Streaming log-sum-exp over the sample axis, fp64 sums.  state (1 + n_rows, 3, B) doubles, per (row, b): running
+ * maximum | sum exp(w - max) | sum exp(2 (w - max)); an empty state is (-inf, 0, 0).  Row 0 holds the joint weights
+ * w = lw0 + sum_{m: bit m of joint_mask} ll[m], row 1 + m the likelihood rows ll[m] themselves (lw0, ll[m]: (Kc,B)).
+ * update folds one chunk of Kc samples into every row in one launch; finish (K = samples folded in all):
+ *   out (1 + n_rows, B) = log-mean-exp_k,  ess (B) = exp(2 lse_k(w) - lse_k(2 w)) of row 0.
+ * n_rows <= MMVAE_MOE_MAX_MODS. */
+typedef struct {
+  const float* ll[MMVAE_MOE_MAX_MODS];
+} mmvae_lme_rows;
+int mmvae_lme_update(double* state, const float* lw0, const mmvae_lme_rows* rows, int n_rows, unsigned joint_mask,
+                     int Kc, int B, mmvae_stream_t stream);
+int mmvae_lme_finish(const double* state, double* out, double* ess, int n_rows, long K, int B, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -2,6 +2,7 @@
 // Elementwise / small-reduction work over (experts x B x D) with D <= 256: one wavefront per sample,
 // lanes over the latent dimension, wave-shuffle reductions; no LDS, no atomics (deterministic).
 #include "common.hpp"
+#include "noise.hpp"
 #include <type_traits>
 
 // one wave per sample up to this many waves, then samples round robin (round 4: 128 -> 512; a wave's samples are a serial
@@ -100,34 +101,6 @@ __device__ __forceinline__ void row_softmax_stats(const float* __restrict__ u, i
   sum = wave_sum(sum);
   *mx_out = mx;
   *inv_out = 1.0f / sum;
-}
-
-// element e of the counter-based standard-normal stream `key` (see randn_kernel: Box-Muller over the hash pair of
-// element pair e >> 1; the even element takes the cosine branch)
-__device__ __forceinline__ uint32_t randn_key(const uint32_t* __restrict__ state) {
-  return drop_fmix(state[0] ^ (state[1] * 0x9E3779B1u) ^ 0x632BE5ABu);
-}
-__device__ __forceinline__ float randn_elem(uint32_t key, long e) {
-  const long i = e >> 1;
-  const uint32_t h1 = drop_fmix(key + (uint32_t)(2 * i) * 0x9E3779B1u);
-  const uint32_t h2 = drop_fmix(key + (uint32_t)(2 * i + 1) * 0x9E3779B1u);
-  const float u1 = ((float)(h1 >> 8) + 1.0f) * (1.0f / 16777216.0f);   // (0, 1]
-  const float u2 = (float)(h2 >> 8) * (1.0f / 16777216.0f);            // [0, 1)
-  const float r = sqrtf(-2.0f * logf(u1));
-  float sn, cs;
-  sincosf(6.283185307179586f * u2, &sn, &cs);
-  return (e & 1) ? r * sn : r * cs;
-}
-// the last workgroup of a launch that consumed the stream advances its counter
-__device__ __forceinline__ void randn_advance(uint32_t* __restrict__ state) {
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t ticket = atomicAdd(state + 2, 1u);
-    if (ticket == gridDim.x - 1) {
-      state[2] = 0u;
-      state[1] += 1u;
-    }
-  }
 }
 
 __device__ __forceinline__ float kl_elem(float mu, float s, float sp) {

@@ -6,6 +6,7 @@
 // plus the Laplace pieces `prior: laplace` switches on for the elbo objective (KL(Laplace || Normal), the importance
 // ratio under Laplace posteriors).  All HBM-bound elementwise / row-reduction work on (M, K, B, D) <= a few MB.
 #include "common.hpp"
+#include "noise.hpp"
 
 #define MOE_SLOTS 4   // D <= 256: lane owns d = lane + 64 s
 
@@ -491,21 +492,9 @@ extern "C" int mmvae_laplace_logratio_bwd(const float* packed_r, const float* z,
 // ---------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void rand_laplace_kernel(float* __restrict__ out, long n,
                                                            uint32_t* __restrict__ state) {
-  const uint32_t key = drop_fmix(state[0] ^ (state[1] * 0x9E3779B1u) ^ 0x1B873593u);
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const uint32_t h = drop_fmix(key + (uint32_t)i * 0x9E3779B1u);
-    const float u = ((float)(h >> 9) + 0.5f) * (1.0f / 4194304.0f) - 1.0f;      // (-1, 1) exactly: never 0 or +-1
-    const float m = -log1pf(-fabsf(u));
-    out[i] = u < 0.f ? -m : m;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const uint32_t ticket = atomicAdd(state + 2, 1u);
-    if (ticket == gridDim.x - 1) {
-      state[2] = 0u;
-      state[1] += 1u;
-    }
-  }
+  const uint32_t key = rand_laplace_key(state);
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) out[i] = rand_laplace_elem(key, i);
+  randn_advance(state);
 }
 extern "C" int mmvae_rand_laplace(float* out, long n, uint32_t* state, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(out && state && n > 0);

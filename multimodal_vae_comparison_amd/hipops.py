@@ -68,6 +68,13 @@ class MoeKBwdArgs(ctypes.Structure):
                 ("dz", c_p * MOE_MAX_MODS), ("dpacked", c_p * MOE_MAX_MODS), ("laplace", c_i * MOE_MAX_MODS)]
 
 
+MIX_MAX_COMPONENTS = 8
+
+
+class LmeRows(ctypes.Structure):
+    _fields_ = [("ll", c_p * MOE_MAX_MODS)]
+
+
 class DregRows(ctypes.Structure):      # also mmvae_dreg_rows_grad (same layout, non-const pointers)
     _fields_ = [("own", c_p * MOE_MAX_MODS), ("cross", c_p * MOE_MAX_MODS), ("lam", c_f * MOE_MAX_MODS)]
 
@@ -269,6 +276,9 @@ SIGNATURES = {
     "mmvae_laplace_logratio_fwd": (c_i, [c_p] * 4 + [c_i, c_i, c_p]),
     "mmvae_laplace_logratio_bwd": (c_i, [c_p] * 4 + [c_i, c_i, c_p]),
     "mmvae_rand_laplace": (c_i, [c_p, c_l, c_p, c_p]),
+    "mmvae_mix_ksample_logw_fwd": (c_i, [c_p, c_u, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p] + [c_i] * 5 + [c_p]),
+    "mmvae_lme_update": (c_i, [c_p, c_p, ctypes.POINTER(LmeRows), c_i, c_u, c_i, c_i, c_p]),
+    "mmvae_lme_finish": (c_i, [c_p, c_p, c_p, c_i, c_l, c_i, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .. import ops
 from .nn_modules import DropoutState
-from .objectives import MultimodalObjective
+from .objectives import MultimodalObjective, recon_rowsum
 from .output_storage import VAEOutput
 
 # the decoders' first dropout-counter advance rides on the first encoder's launch (DropoutState.link;
@@ -57,6 +57,10 @@ class TorchMMVAE(nn.Module):
         # counter-based device noise generator {seed, call counter, ticket} (ops.randn)
         self.register_buffer("_rng_state", torch.tensor([torch.initial_seed() & 0x7FFFFFFF, 0, 0], dtype=torch.int32),
                              persistent=False)
+        # the evaluation draws (estimate_log_likelihood) have a generator state of their own: the training noise stream
+        # does not move when a model is evaluated between two steps
+        self.register_buffer("_eval_rng_state", torch.tensor([(torch.initial_seed() ^ 0x5DEECE66) & 0x7FFFFFFF, 0, 0],
+                                                             dtype=torch.int32), persistent=False)
 
     def set_likelihood_scales(self):
         """mmvae_base.py:41-47"""
@@ -221,6 +225,102 @@ class TorchMMVAE(nn.Module):
     @abc.abstractmethod
     def objective(self, mods):
         pass
+
+    # ---- held-out log-likelihood ---------------------------------------------------------------
+    def _proposal_size(self, n_given):
+        """number of mixture components C of q(z | x_G) for |G| = n_given (mixers with a joint proposal override it)"""
+        raise NotImplementedError(f"{self.modelName}: estimate_log_likelihood has no joint proposal for this mixer "
+                                  f"(poe, moe and mopoe have one; private latents do not)")
+
+    def _proposal(self, mods, given):
+        """-> (comps (C,B,2D) = [loc | scale] of the components of q(z | x_G), C Laplace flags)"""
+        raise NotImplementedError(f"{self.modelName}: estimate_log_likelihood has no joint proposal for this mixer")
+
+    def _given_only(self, mods, given):
+        """the batch with the `data` of every modality outside `given` set to None (masks kept), as the cross-generation
+        calls of forward() take it"""
+        return {m: (mods[m] if m in given else dict(mods[m], data=None)) for m in self.vaes}
+
+    @staticmethod
+    def default_k_chunk(K, C, B):
+        """samples per decoder call: the largest multiple of C that divides K with k_chunk * B <= 1024 rows, at least C
+        (decoder batches stay inside the range the training paths run at, memory does not grow with K)"""
+        best = C
+        for kc in range(C, K + 1, C):
+            if K % kc == 0 and kc * B <= 1024:
+                best = kc
+        return best
+
+    def estimate_log_likelihood(self, mods, K, given=None, targets=None, k_chunk=None, eps=None):
+        """K-sample importance-sampled bound on the held-out log-likelihood, comparable across mixers.
+
+        `given` G (default: every modality whose data is not None) conditions the proposal, `targets` T (default: the
+        same) are the modalities whose likelihood is estimated.
+          proposal  q(z | x_G) = (1/C) sum_c q_c(z), the (loc, scale) pairs this model's forward() / modality_mixing()
+                    hand to Normal / Laplace (the variance-used-as-scale quirk included):
+                    poe: C = 1, the product of the prior expert and the experts of G;  moe: C = |G|, the unimodal
+                    posteriors (Normal | Laplace as `_laplace` says);  mopoe: C = 2^|G| - 1, the subset products;
+          prior     p(z) = Normal(pz_params) = (location, softmax(theta) D);
+          draws     stratified, K % C == 0: sample k comes from component k % C, z[k,b] = loc_c[b] + scale_c[b] eps[k,b];
+          lw0[k,b]  = sum_d log p(z[k,b,d]) - log((1/C) sum_c exp sum_d log q_c(z[k,b,d]));
+          ll_m[k,b] = log p(x_m[b] | z[k,b]) = -recon_rowsum(ltype_m, dec_m(z), x_m), without llik_scaling;
+          joint     = log-mean-exp_k (lw0 + sum_{m in T} ll_m)          <= log p(x_T)        (G = T: the IWAE bound)
+          cond[m]   = log-mean-exp_k ll_m, z ~ q(z | x_G)               (the papers' conditional estimate log p(x_m | x_G))
+          ess       = exp(2 lse_k(w) - lse_k(2 w)) of the joint weights (effective sample size: judge K by it).
+        Returns {"joint": (B,), "cond": {m: (B,)}, "ess": (B,)}, float64.  Needs eval mode (dropout would make the bound
+        meaningless); runs without gradients and leaves the training noise state, dropout counters, gradients and the
+        optimiser alone.  `k_chunk` samples are decoded per call (default_k_chunk); `eps` (K,B,D) replaces the
+        generator (tests).  An optimal_sigma likelihood fits one sigma per decoded (B-row) sample, as the objectives'
+        one-sigma-per-call does, so that the estimate does not depend on k_chunk."""
+        self._proposal_size(0)      # (a mixer without a joint proposal says so before the batch is looked at)
+        names = list(self.vaes.keys())
+        given = [m for m in names if mods[m]["data"] is not None] if given is None else [m for m in names if m in given]
+        targets = list(given) if targets is None else [m for m in names if m in targets]
+        C = self._proposal_size(len(given))
+        if self.training:
+            raise RuntimeError("estimate_log_likelihood needs eval mode (model.eval()): dropout would make the bound "
+                               "meaningless")
+        if not given or not targets or any(mods[m]["data"] is None for m in list(given) + targets):
+            raise ValueError("estimate_log_likelihood: `given` and `targets` must name modalities with data")
+        K = int(K)
+        if K < 1 or K % C != 0:
+            raise ValueError(f"estimate_log_likelihood: K = {K} must be a positive multiple of the proposal's {C} "
+                             f"components (stratified draws)")
+        if len(targets) > ops.H.MOE_MAX_MODS or C > ops.H.MIX_MAX_COMPONENTS:
+            raise NotImplementedError(f"estimate_log_likelihood: {len(targets)} targets / {C} components (up to "
+                                      f"{ops.H.MOE_MAX_MODS} / {ops.H.MIX_MAX_COMPONENTS} are on the MI355X path)")
+        with torch.no_grad():
+            comps, lap = self._proposal(mods, given)
+            _, B, D2 = comps.shape
+            D = D2 // 2
+            kc = self.default_k_chunk(K, C, B) if k_chunk is None else int(k_chunk)
+            if kc < 1 or kc % C != 0 or K % kc != 0:
+                raise ValueError(f"estimate_log_likelihood: k_chunk = {kc} must be a multiple of {C} that divides K = {K}")
+            if eps is not None:
+                eps = eps.to(device=comps.device, dtype=torch.float32).reshape(K, B, D)
+            loc, theta = self._pz_params[0], self._pz_params[1]
+            state = ops.lme_state(len(targets), B, comps.device)
+            for k0 in range(0, K, kc):
+                z, lw0 = ops.mix_ksample_logw(comps, lap, theta, kc, k0, eps=None if eps is None else eps[k0:k0 + kc],
+                                              rng=self._eval_rng_state if eps is None else None,
+                                              advance=k0 + kc == K, prior_loc=loc,
+                                              prior_laplace=self.pz is dist.Laplace)
+                rows = []
+                for m in targets:
+                    vae, mk = self.vaes[m], mods[m]["masks"]
+                    if vae.ltype == "optimal_sigma":
+                        r = torch.cat([recon_rowsum(vae.ltype, vae.dec({"latents": z[k:k + 1], "masks": mk})[0], mods[m])
+                                       for k in range(kc)])
+                    else:
+                        # the kc * B samples as one batch (row k * B + b; the row-sum kernels pair row r with target row
+                        # r % B), text masks repeated -- the form POE.objective decodes its subsets in
+                        out, _ = vae.dec({"latents": z.reshape(1, kc * B, D),
+                                          "masks": None if mk is None else mk.repeat(kc, 1)})
+                        r = recon_rowsum(vae.ltype, out, mods[m], laplace=self._lap(vae))
+                    rows.append(-r.reshape(kc, B))
+                ops.lme_update(state, lw0, rows)
+            out, ess = ops.lme_finish(state, K)
+        return {"joint": out[0], "cond": {m: out[1 + i] for i, m in enumerate(targets)}, "ess": ess}
 
     def product_of_experts(self, mu, logvar, with_prior=False):
         """mmvae_base.py:203-222 on the fused kernel: mu/logvar are lists of (B,D) tensors; returns

@@ -248,6 +248,16 @@ class MoPOE(TorchMMVAE):
         latents["subsets"] = distr_subsets
         return latents
 
+    def _proposal_size(self, n_given):
+        return 2 ** n_given - 1
+
+    def _proposal(self, mods, given):
+        """every non-empty subset of `given`: the subset products modality_mixing() builds (the prior expert joins the
+        subset of ALL modalities only), (mu, variance used as scale)"""
+        subsets = self.modality_mixing(self._given_only(mods, given))["subsets"]
+        comps = torch.stack([torch.cat([mu[0], var[0]], -1) for mu, var in subsets.values()])
+        return comps, [False] * comps.shape[0]
+
     def forward(self, inputs, K=1):
         """mmvae_models.py:351-370"""
         latents = self.modality_mixing(inputs)
@@ -505,6 +515,14 @@ class POE(TorchMMVAE):
         mu, var = self.product_of_experts(mus, lvs, with_prior=True)
         return mu, var, single
 
+    def _proposal_size(self, n_given):
+        return 1
+
+    def _proposal(self, mods, given):
+        """the product of the prior expert and the experts of `given` (modality_mixing), (mu, variance used as scale)"""
+        mu, var, _ = self.modality_mixing(self._given_only(mods, given))
+        return torch.cat([mu, var], -1).unsqueeze(0), [False]
+
     def forward(self, inputs, K=1):
         """mmvae_models.py:189-208"""
         mu, var, single = self.modality_mixing(inputs)
@@ -695,6 +713,15 @@ class MOE(TorchMMVAE):
 
     def modality_mixing(self, mods):
         return self.encode(mods)
+
+    def _proposal_size(self, n_given):
+        return n_given
+
+    def _proposal(self, mods, given):
+        """the unimodal posteriors of `given`: (mu, "logvar" used as scale), Normal | Laplace per modality"""
+        names = list(self.vaes.keys())
+        comps = torch.stack([packed_head(*self.vaes[m].enc(mods[m])) for m in given])
+        return comps, [self._laplace[names.index(m)] for m in given]
 
     def forward(self, x, K=1):
         """mmvae_models.py:80-117, including the cross-generation calls with missing modalities

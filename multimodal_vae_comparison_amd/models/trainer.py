@@ -118,6 +118,17 @@ class MultimodalVAE(nn.Module):
         self._log_losses(loss_d, "test", "Test")
         return loss_d["loss"]
 
+    def estimate_log_likelihood(self, batch, K, given=None, targets=None, k_chunk=None, eps=None):
+        """held-out log-likelihood of `batch` (TorchMMVAE.estimate_log_likelihood: importance-sampled, K samples,
+        comparable across mixers; the model must be in eval mode), logged as test_loglik_joint and test_loglik_mod_<i>
+        (batch means; i = the modality's position, as in Mod_<i>_TestLoss)"""
+        out = self.model.estimate_log_likelihood(batch, K, given=given, targets=targets, k_chunk=k_chunk, eps=eps)
+        self.log("test_loglik_joint", out["joint"].mean(), batch_size=self.config.batch_size)
+        names = list(self.model.vaes.keys())
+        for m, v in out["cond"].items():
+            self.log("test_loglik_mod_{}".format(names.index(m)), v.mean(), batch_size=self.config.batch_size)
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;

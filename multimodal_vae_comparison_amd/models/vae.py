@@ -99,6 +99,10 @@ class VAE(BaseVae):
         return self._pz_params_private[0], \
             F.softmax(self._pz_params_private[1], dim=1) * self._pz_params_private[1].size(-1)
 
+    def estimate_log_likelihood(self, *args, **kwargs):
+        raise NotImplementedError("unimodal VAE: estimate_log_likelihood is built for the multimodal mixers poe, moe and "
+                                  "mopoe (TorchMMVAE.estimate_log_likelihood)")
+
     # ---- the unimodal case: `self.model = vaes["mod_1"]` (models/trainer.py:112-113) ------------------------------
     def objective(self, data):
         """VAE.forward + objective with UnimodalObjective.elbo (models/vae.py:92-119,268-282, models/objectives.py:233-247):
