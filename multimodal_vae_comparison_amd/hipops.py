@@ -415,13 +415,20 @@ def f32c(t):
     return t if t.is_contiguous() else t.contiguous()
 
 
+def device_key(device):
+    """the index per-device tables are keyed by (`cuda` without an index: the current device; any CPU device: 0)"""
+    if device.index is not None:
+        return device.index
+    return torch.cuda.current_device() if device.type == "cuda" else 0
+
+
 _ws = {}
 
 
 def workspace(n_floats, device):
     """Caller-provided scratch for the *_ws_floats() contracts; grows monotonically per device.  Ops on one
     stream run in order, so consecutive ops may share it."""
-    key = (device.index if device.index is not None else torch.cuda.current_device())
+    key = device_key(device)
     t = _ws.get(key)
     if t is None or t.numel() < n_floats:
         t = torch.empty(max(int(n_floats), 1 << 20), dtype=torch.float32, device=device)

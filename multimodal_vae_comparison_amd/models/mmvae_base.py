@@ -127,7 +127,7 @@ class TorchMMVAE(nn.Module):
         """stream per modality: modality `main` stays on the current stream (None), the others get side streams
         (ops.StreamPlan) so that independent towers overlap -- each of them alone cannot fill the chip at batch 128"""
         names = list(self.vaes.keys())
-        key = device.index if device.index is not None else (torch.cuda.current_device() if device.type == "cuda" else 0)
+        key = ops.H.device_key(device)
         ops.StreamPlan.pair.pop(key, None)
         if not (ops.StreamPlan.enabled and device.type == "cuda") or len(names) < 2:
             return [None] * len(names)

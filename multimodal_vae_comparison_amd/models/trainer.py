@@ -24,6 +24,15 @@ FEATURE_DIMS = {
 }
 
 
+def early_adam_from_env():
+    """MMVAE_EARLY_ADAM: 2 (default) = the captured one-GPU step updates the decoders' + prior's range beside the encoders'
+    backward (ops.GradReducer.early_step), 0 = one optimiser launch at the end of the step"""
+    v = os.environ.get("MMVAE_EARLY_ADAM", "2")
+    if v not in ("0", "2"):
+        raise ValueError(f"MMVAE_EARLY_ADAM={v!r}: accepted values are '0' and '2' (default)")
+    return v == "2"
+
+
 class MultimodalVAE(nn.Module):
     def __init__(self, cfg, feature_dims=None, device="cuda"):
         super().__init__()
@@ -191,6 +200,7 @@ class MultimodalVAE(nn.Module):
         graph (GraphInputRing): replay j trains on ring[j % len(ring)], with no runtime call per step but the graph
         launch itself."""
         assert self.optimizer is not None, "call configure_optimizers() first"
+        early_adam = early_adam_from_env()
         # the collective and the 1/world mean come from parallel.setup_replica (dp_world, optimizer.grad_scale), not from
         # this argument: a caller that asks for a multi-rank step without having set the replica up would otherwise train
         # diverging replicas without a word (ADVICE r2)
@@ -275,9 +285,7 @@ class MultimodalVAE(nn.Module):
                     # ... and its second range (decoders, prior) does not wait for the end of the step: MoPOE.
                     # objective_backward runs it behind the fusion's backward (MMVAE_EARLY_ADAM=0: one launch at the end)
                     self.model.early_adam = None
-                    if ops.GradReducer.defer_next and 0 < self.flat.split < self.flat.grad.numel() and \
-                            os.environ.get("MMVAE_EARLY_ADAM", "2") != "0":
-                        ops.GradReducer.early_at = int(os.environ.get("MMVAE_EARLY_ADAM", "2"))
+                    if ops.GradReducer.defer_next and 0 < self.flat.split < self.flat.grad.numel() and early_adam:
                         lo, hi, g0 = self.flat.split, self.flat.grad.numel(), self.flat.grad.data_ptr()
                         self.model.early_adam = (lambda table, lo=lo, hi=hi: self.optimizer.step_early(lo, hi, table),
                                                  g0 + 4 * lo, g0 + 4 * hi)

@@ -57,15 +57,14 @@ class GradReducer:
     side_head = None      # fn(device): see StreamIdlePoint
     _arena = {}
     _state = {}
-    _side = {}        # device key -> {"wgrad": Stream, "tower": Stream}: see StreamPlan below
 
     @classmethod
     def _st(cls, device):
-        key = device.index if device.index is not None else torch.cuda.current_device()
+        key = H.device_key(device)
         st = cls._state.get(key)
         if st is None:
-            st = {"off": 0, "segs": [], "armed": False, "device": device, "keep": [], "used": set(), "pending": [],
-                  "spill": [], "spilled": 0}
+            st = {"off": 0, "segs": [], "armed": False, "device": device, "keep": [], "used": set(), "spill": [],
+                  "spilled": 0}
             cls._state[key] = st
         return key, st
 
@@ -86,10 +85,9 @@ class GradReducer:
             cls.deferred = None
             raise RuntimeError("GradReducer: a deferred fold was never taken by an optimiser step: the split weight "
                                "gradients of the previous backward pass were lost")
-        if st["armed"] or st["segs"] or st["pending"]:
-            st.update(off=0, segs=[], armed=False, keep=[], used=set(), pending=[], spill=[], spilled=0)
-            cls.tail = cls.early_step = None
-            cls.dw_jobs = []
+        if st["armed"] or st["segs"]:
+            st.update(off=0, segs=[], armed=False, keep=[], used=set(), spill=[], spilled=0)
+            cls.tail = None
 
     @classmethod
     def alloc(cls, n_floats, device):
@@ -179,20 +177,29 @@ class GradReducer:
             if b0 < a1:
                 raise RuntimeError(f"GradReducer: fold segments overlap partially: [{a0:#x}, {a1:#x}) and [{b0:#x}, {b1:#x})")
 
+    @staticmethod
+    def _table(segs):
+        t = H.ReduceSegments()
+        for j, (sp, dp, r, ln, sd) in enumerate(segs):
+            t.src[j], t.dst[j], t.rows[j], t.len[j], t.stride[j] = sp, dp, r, ln, sd
+        t.n = len(segs)
+        return t
+
     @classmethod
     def run_side_tail(cls, device):
         fn, cls.side_tail = cls.side_tail, None
         if fn is not None:
             fn(device, [])                      # on the CURRENT stream = the side tower's
 
-    # early_step = (fn, stream, lo, hi): set by MoPOE.objective_backward for a captured one-GPU step -- when the fusion's
-    # backward has been queued on `stream` and handed its gradients over (EarlyStepPoint.backward), every gradient of the flat buffer's
-    # second range [lo, hi) (decoders, prior: FlatParams.split) is final AND stream-ordered in front of this point, so their
-    # fold + Adam update runs here, beside the encoders' backward, instead of in the serial launch at the end of the step
-    # (fn(table of the range's segments or None)).  The range's segments leave the list: nobody else folds them.
-    # (Round 6, measured: queued behind the text encoder's LAST backward launch instead, the 65 MB the update moves landed
-    # on the image encoder's first-layer weight gradient -- 14 -> 26 us -- and gave back what the shorter closing launch won.)
+    # early_step = (fn, stream, lo, hi): set by MoPOE.objective_backward for a captured one-GPU step (MMVAE_EARLY_ADAM=2,
+    # the default; 0: trainer.capture never arms it).  Once the fusion's backward has been queued on `stream` and handed its
+    # gradients over (EarlyStepPoint.backward sets `early_ready`), every gradient of the flat buffer's second range [lo, hi)
+    # (decoders, prior: FlatParams.split) is final AND stream-ordered on `stream`, so their fold + Adam update runs beside
+    # the encoders' backward instead of in the serial launch at the end of the step: run_early_step, called by _txt_wgrad
+    # in front of the weight-gradient launch of the text encoder's layer (fn(table of the range's segments or None)).  The
+    # range's segments leave the list: nobody else folds them.  (The other placements that were measured: DESIGN.md 0.)
     early_step = None
+    early_ready = False
     # data_ptr of a head output -> [its ONE gradient tensor of this backward pass, fusion calls whose backward is still to
     # come]; packed_uses: how many column-range fusion calls read it in this step's forward pass (PoeReparamKL)
     packed_grads, packed_uses = {}, {}
@@ -216,11 +223,6 @@ class GradReducer:
     dw_jobs = []
     dw_open = False       # True from the arming of `early_step` until EarlyStepPoint.backward has queued the parked jobs
     dw_later_enabled = os.environ.get("MMVAE_LINEAR_DW_LATER", "1") == "1"
-    # where the parked launch goes: right behind the fusion's backward (default) or in front of the early optimiser launch
-    # (MMVAE_LINEAR_DW_LATER_AT=adam).  Behind the fusion its 528 workgroups reach the CUs before the image encoder's first
-    # backward kernels, which sit behind a cross-stream wait, and hold that chain up by 8 us; in front of the optimiser
-    # launch it lands, with that launch, on the image encoder's conv2 backward: 383.2 vs 389.4 us (same box, 3 pairs)
-    dw_at_fusion = os.environ.get("MMVAE_LINEAR_DW_LATER_AT", "fusion") == "fusion"
 
     # data_ptr of a preset gradient view -> stream of the launch that last accumulated into it IN PLACE this step
     last_writer = {}
@@ -304,37 +306,25 @@ class GradReducer:
                 with torch.cuda.stream(st):
                     _txt_wgrad(lst)
 
-    # WHERE on the fusion's stream the update is queued (MMVAE_EARLY_ADAM): 1 = right behind the fusion's backward
-    # (EarlyStepPoint), 2 / 3 = in front of / behind the weight-gradient launch of the text encoder's layer, 4 = behind the
-    # text encoder's last backward launch (EmbedPE.backward)
-    early_at = int(os.environ.get("MMVAE_EARLY_ADAM", "2") or 0)
-    early_ready = False
-
     @classmethod
-    def run_early_step(cls, device, at=1):
+    def run_early_step(cls, device):
         es = cls.early_step
-        if es is None or at != cls.early_at or not (cls.early_ready or at == 1):
+        if es is None or not cls.early_ready:
             return
         fn, stream, lo, hi = es
         _, st = cls._st(device)
         if torch.cuda.current_stream(device) != stream:      # (another tower's launch of the same kind)
             return
         cls.early_step = None
-        if st["pending"] or st["spill"] or not cls.defer_next:
+        if st["spill"] or not cls.defer_next:
             return
         inside = cls._merged([sg for sg in st["segs"] if lo <= sg[1] < hi])
         if len(inside) > H.MAX_SEGMENTS or any(sg[1] + 4 * sg[3] > hi for sg in inside):
             return
         st["segs"] = [sg for sg in st["segs"] if not (lo <= sg[1] < hi)]
-        cls.flush_dw()      # (their results belong to the range this launch folds and updates)
-        t = None
-        if inside:
-            t = H.ReduceSegments()
-            for j, (sp, dp, r, ln, sd) in enumerate(inside):
-                t.src[j], t.dst[j], t.rows[j], t.len[j], t.stride[j] = sp, dp, r, ln, sd
-            t.n = len(inside)
-        fn(t)
-
+        # (no parked weight gradient is left here: EarlyStepPoint.backward, which sets `early_ready`, has queued them all
+        # and closed `dw_open`)
+        fn(cls._table(inside) if inside else None)
 
     @classmethod
     def keep(cls, device, *tensors):
@@ -354,30 +344,9 @@ class GradReducer:
             torch.autograd.Variable._execution_engine.queue_callback(lambda: cls.flush(device))
 
     @classmethod
-    def queue(cls, device, launch, *keep):
-        """postpone a weight-gradient launch (nothing but the final reduction reads its output) to the next batch
-        point: one fork for many launches instead of one per launch"""
-        st = cls._st(device)[1]
-        st["pending"].append(launch)
-        st["keep"].extend(t for t in keep if t is not None)
-
-    @classmethod
-    def launch_pending(cls, device):
-        st = cls._st(device)[1]
-        if not st["pending"]:
-            return
-        side = StreamPlan.fork("wgrad", device)
-        st["used"].add(side)
-        with torch.cuda.stream(side):
-            for launch in st["pending"]:
-                launch()
-        st["pending"] = []
-
-    @classmethod
     def flush(cls, device):
-        cls.flush_dw()      # (no early optimiser launch took them with it: here, behind the whole backward pass)
+        cls.flush_dw()      # (no EarlyStepPoint ran behind them: here, behind the whole backward pass)
         cls.tw_flush()      # (each list on the stream it was parked from, in front of the join below)
-        cls.launch_pending(device)
         _, st = cls._st(device)
         cur = torch.cuda.current_stream(device)
         if cls.pre_join is not None:
@@ -393,20 +362,12 @@ class GradReducer:
         tail, cls.tail = cls.tail, None
         defer, cls.defer_next = cls.defer_next, False
         if defer and 0 < len(segs) <= H.MAX_SEGMENTS and not st["spill"]:
-            t = H.ReduceSegments()
-            for j, (sp, dp, r, ln, sd) in enumerate(segs):
-                t.src[j], t.dst[j], t.rows[j], t.len[j], t.stride[j] = sp, dp, r, ln, sd
-            t.n = len(segs)
-            cls.deferred = {"table": t, "tail": tail, "device": device}
+            cls.deferred = {"table": cls._table(segs), "tail": tail, "device": device}
             if tail is not None:
                 tail["done"] = True          # filled by the optimiser's launch
             return
         for i in range(0, len(segs), H.MAX_SEGMENTS):
-            chunk = segs[i:i + H.MAX_SEGMENTS]
-            t = H.ReduceSegments()
-            for j, (sp, dp, r, ln, sd) in enumerate(chunk):
-                t.src[j], t.dst[j], t.rows[j], t.len[j], t.stride[j] = sp, dp, r, ln, sd
-            t.n = len(chunk)
+            t = cls._table(segs[i:i + H.MAX_SEGMENTS])
             if tail is not None and i + H.MAX_SEGMENTS >= len(segs):
                 # the logged loss values ride on the last fold launch as one extra workgroup
                 rp, flat, out, n, B, k = tail["args"]
@@ -416,10 +377,9 @@ class GradReducer:
             else:
                 _call("mmvae_reduce_segments", ctypes.byref(t), H.stream())
         if st["spill"]:        # the step did not fit one chunk: one arena of the full size from the next step on
-            key = device.index if device.index is not None else torch.cuda.current_device()
             st["spill"], st["spilled"] = [], 0
             if not torch.cuda.is_current_stream_capturing():
-                cls._arena[key] = torch.empty(need + (1 << 20), dtype=torch.float32, device=device)
+                cls._arena[H.device_key(device)] = torch.empty(need + (1 << 20), dtype=torch.float32, device=device)
 
 
 class Marks:
@@ -463,25 +423,20 @@ class StreamPlan:
     """Overlap on separate HIP streams (captured into one hipGraph as parallel branches).
 
     At batch 128 every kernel of the step is far too small to fill 256 CUs, so the step time is the length of the
-    dependency chain.  Two independent chains are taken off the critical path:
-      * `wgrad`: every weight-gradient kernel (conv wgrad, dW GEMMs) -- nothing but the end-of-backward reduction
-        consumes its output;
-      * `tower`: the text tower (encoder / decoder, forward and backward) runs beside the image tower.
-    Side streams are forked with events from the stream that produced their inputs and joined before the
-    deferred reduction (GradReducer.flush) / at the fusion and loss points in the mixers."""
+    dependency chain.  One independent chain is taken off the critical path: the text tower (encoder / decoder, forward
+    and backward) runs beside the image tower.  Side streams are forked with events from the stream that produced their
+    inputs and joined before the deferred reduction (GradReducer.flush) / at the fusion and loss points in the mixers."""
 
     # Measured on MI355X / ROCm 7.2, B=128 (DESIGN.md section 5): parallel graph branches DO overlap, but every
     # fork/join costs several microseconds, so only coarse forks pay:
     #   MMVAE_STREAMS=0         1.30 ms/step   single stream
     #   MMVAE_STREAMS=tower     0.99 ms/step   (default) text tower beside image tower: 2 forks + 2 joins per step
-    #   MMVAE_STREAMS=batch     1.06 ms/step   + conv weight gradients queued, launched in two side-stream batches
-    #   MMVAE_STREAMS=conv      1.20 ms/step   + one fork per conv weight-gradient launch
-    #   MMVAE_STREAMS=1         1.30 ms/step   + one fork per weight-gradient launch
+    # (weight gradients on side streams of their own -- the former values batch / conv / 1 -- were slower: 1.06 / 1.20 /
+    # 1.30 ms/step, removed)
     _mode = os.environ.get("MMVAE_STREAMS", "tower")
-    enabled = _mode != "0"
-    batch_wgrad = _mode == "batch"                            # queue conv wgrads, launch them in batches
-    wgrad_enabled = _mode in ("conv", "1")                    # fork per wgrad launch
-    wgrad_linear = _mode == "1"
+    if _mode not in ("0", "tower"):
+        raise ValueError(f"MMVAE_STREAMS={_mode!r}: accepted values are '0' (one stream) and 'tower' (default)")
+    enabled = _mode == "tower"
     # (measured and removed in round 2, DESIGN.md 5b: a conv layer's backward as a data-gradient launch on the tower's
     # stream + a weight-gradient launch on a third stream -- 0.634 ms/step, the graph serialises; and the small-map
     # layers' fused backward as two launches on the same stream -- 0.450 / 0.457 / 0.489 ms for maps <= 4 / 8 / 16)
@@ -489,7 +444,7 @@ class StreamPlan:
 
     @classmethod
     def get(cls, kind, device):
-        key = (kind, device.index if device.index is not None else torch.cuda.current_device())
+        key = (kind, H.device_key(device))
         s = cls._streams.get(key)
         if s is None:
             s = torch.cuda.Stream(device=device)
@@ -501,8 +456,7 @@ class StreamPlan:
     @classmethod
     def other_stream(cls, device):
         """the step's stream that is NOT the current one (None outside a two-stream step)"""
-        key = device.index if device.index is not None else torch.cuda.current_device()
-        pr = cls.pair.get(key)
+        pr = cls.pair.get(H.device_key(device))
         if not pr:
             return None
         cur = torch.cuda.current_stream(device)
@@ -511,24 +465,6 @@ class StreamPlan:
         if cur == pr[1]:
             return pr[0]
         return None
-
-    @classmethod
-    def fork(cls, kind, device):
-        """side stream that has waited for everything enqueued so far on the current stream"""
-        side = cls.get(kind, device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        return side
-
-
-def _wgrad_side(device, *keep):
-    """stream for a weight-gradient launch: the wgrad side stream (forked from the current one) when gradients are
-    deferred, else None (= stay on the current stream)"""
-    if not (StreamPlan.enabled and StreamPlan.wgrad_enabled and GradReducer.enabled):
-        return None
-    side = StreamPlan.fork("wgrad", device)
-    GradReducer.note_stream(device, side)
-    GradReducer.keep(device, *keep)
-    return side
 
 
 def _defer(*grads):
@@ -583,6 +519,18 @@ def _new_like_param(p, g):
     return t, 0, t
 
 
+def _grad_dst(w, gw, gb, has_b, n_bias):
+    """destinations of a layer's weight and bias gradient: (dw, db, accumulate flag of dw, the two values to hand back to
+    autograd).  db is the preset view `gb`, a fresh (n_bias,) tensor, or None for a layer without bias."""
+    dw, acc_w, ret_w = _new_like_param(w, gw)
+    db = ret_b = None
+    if has_b:
+        db = gb
+        if gb is None:
+            db = ret_b = torch.empty(n_bias, device=w.device)
+    return dw, db, acc_w, ret_w, ret_b
+
+
 # ----------------------------------------------------------------------------------------------
 # convolutions
 # ----------------------------------------------------------------------------------------------
@@ -608,13 +556,7 @@ class Conv2dK4S2(Function):
         dy = H.f32c(dy)
         B, Cin, Hin, _ = x.shape
         Cout, Hout = w.shape[0], Hin // 2
-        dw, acc_w, ret_w = _new_like_param(w, gw)
-        db, ret_b = None, None
-        if has_b:
-            if gb is not None:
-                db = gb
-            else:
-                db = ret_b = torch.empty(Cout, device=x.device)
+        dw, db, acc_w, ret_w, ret_b = _grad_dst(w, gw, gb, has_b, Cout)
         nws = H.lib().mmvae_conv_wgrad_ws_floats(B, Cout, Cin, Hout)
         defer = _defer(gw, gb if has_b else gw)
         ws = GradReducer.alloc(nws, x.device) if defer else H.workspace(nws, x.device)
@@ -625,14 +567,8 @@ class Conv2dK4S2(Function):
             _call("mmvae_conv2d_k4s2_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
                   B, Cin, Cout, Hout, in_act, acc, H.stream())
         else:
-            def launch(dy=dy, x=x, dw=dw, db=db, ws=ws):
-                _call("mmvae_conv2d_k4s2_wgrad", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), B, Cin, Cout,
-                      Hout, in_act, acc, H.stream())
-            if defer and StreamPlan.enabled and StreamPlan.batch_wgrad:
-                GradReducer.queue(x.device, launch, dy, x)
-            else:
-                with torch.cuda.stream(_wgrad_side(x.device, dy, x) if defer else None):
-                    launch()
+            _call("mmvae_conv2d_k4s2_wgrad", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), B, Cin, Cout, Hout,
+                  in_act, acc, H.stream())
         if defer:
             _conv_segments(ws, dw, db, B, Cout, Cin, Hout, Cout)
         return dx, ret_w, ret_b, None, None, None
@@ -680,13 +616,7 @@ def _convT_k4s2_bwd(x, w, dy, in_act, gw, gb, has_b, need_dx):
     """dx, dw, db of y = convT2d(act(x), w, b) for dy = d loss / d y (ConvT2dK4S2.backward, ConvT3Bce.backward)"""
     B, Cin, Hin, _ = x.shape
     Cout = w.shape[1]
-    dw, acc_w, ret_w = _new_like_param(w, gw)
-    db, ret_b = None, None
-    if has_b:
-        if gb is not None:
-            db = gb
-        else:
-            db = ret_b = torch.empty(Cout, device=x.device)
+    dw, db, acc_w, ret_w, ret_b = _grad_dst(w, gw, gb, has_b, Cout)
     nws = H.lib().mmvae_conv_wgrad_ws_floats(B, Cin, Cout, Hin)
     defer = _defer(gw, gb if has_b else gw)
     ws = GradReducer.alloc(nws, x.device) if defer else H.workspace(nws, x.device)
@@ -878,13 +808,7 @@ class ConvGeneric(Function):
             _call("mmvae_sigmoid_clamp_bwd" if out_ep == H.EP_SIGMOID_CLAMP else "mmvae_sigmoid_bwd", H.ptr(dy), H.ptr(y),
                   H.ptr(dl), dy.numel(), H.stream())
             dy = dl
-        dw, acc_w, ret_w = _new_like_param(w, gw)
-        db, ret_b = None, None
-        if has_b:
-            if gb is not None:
-                db = gb
-            else:
-                db = ret_b = torch.empty(Cout, device=x.device)
+        dw, db, acc_w, ret_w, ret_b = _grad_dst(w, gw, gb, has_b, Cout)
         pre = "mmvae_convT2d_generic" if transposed else "mmvae_conv2d_generic"
         _call(pre + "_wgrad", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), B, Cin, Cout, Hin, Win, K, stride, pad, in_act,
               acc_w, H.stream())
@@ -1042,13 +966,7 @@ class Linear(Function):
         K = x.shape[-1]
         M = x.numel() // K
         N = w.shape[0]
-        dw, acc_w, ret_w = _new_like_param(w, gw)
-        db, ret_b = None, None
-        if has_b:
-            if gb is not None:
-                db = gb
-            else:
-                db = ret_b = torch.empty(N, device=x.device)
+        dw, db, acc_w, ret_w, ret_b = _grad_dst(w, gw, gb, has_b, N)
         need_dx = ctx.needs_input_grad[0]
         if dy.data_ptr() % 16:
             dy = dy.clone()
@@ -1086,17 +1004,15 @@ class Linear(Function):
             acc = H.ACC_DEFER
         else:
             ws, acc = H.workspace(nws, x.device), acc_w
-        side = None if need_dx else (_wgrad_side(x.device, dy, x) if (defer and StreamPlan.wgrad_linear) else None)
         direct = (gw, gb) if (gw is not None and not (defer and nz > 1)) else ()      # accumulated in place by the launch
         if need_dx:   # data and weight gradients in ONE grouped launch
             GradReducer.writes(x.device, *direct)
             _call("mmvae_linear_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), aux, H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
                   M, N, K, K, in_act, ep, acc, H.stream())
         else:
-            with torch.cuda.stream(side):
-                GradReducer.writes(x.device, *direct)
-                _call("mmvae_linear_bwd_weight", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), M, N, K, K,
-                      in_act, acc, H.stream())
+            GradReducer.writes(x.device, *direct)
+            _call("mmvae_linear_bwd_weight", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), M, N, K, K, in_act, acc,
+                  H.stream())
         if defer and nz > 1:
             GradReducer.add(ws.data_ptr(), dw, nz, N * K, N * K)
             if db is not None:
@@ -1330,9 +1246,6 @@ class PoeReparamKL(Function):
     @staticmethod
     def backward(ctx, _dj, dkl, *dzs):
         gtheta, with_prior, n_z, kl_mask, E, B, D, Dtot, col0, raw = ctx.cfg
-        # batch point: every decoder's backward is done, so the queued decoder weight-gradient kernels can run on
-        # the side stream underneath the encoder backward chains
-        GradReducer.launch_pending(ctx.saved_tensors[0].device)
         theta = ctx.saved_tensors[0]
         packed = ctx.saved_tensors[1:1 + E]
         eps = ctx.saved_tensors[1 + E:]
@@ -1502,7 +1415,8 @@ class EarlyStepPoint(Function):
     that runs on that stream AFTER the fusion's backward has handed its gradients over (the engine records the events the
     other towers' streams wait for when PoeReparamKL.backward returns -- a launch queued inside that function would sit in
     front of them and hold the other tower's encoder backward up: measured, +9 us on both chains).  Every decoder's and the
-    prior's gradient is final and stream-ordered in front of this point: GradReducer.run_early_step."""
+    prior's gradient is final and stream-ordered in front of this point: it opens the way for GradReducer.run_early_step
+    and queues the parked Linear weight gradients (GradReducer.flush_dw)."""
 
     @staticmethod
     def forward(ctx, x):
@@ -1513,9 +1427,7 @@ class EarlyStepPoint(Function):
         GradReducer.early_ready = True   # (a weight-gradient launch on this stream IN FRONT of this point -- a decoder's --
                                          # must not trigger the early optimiser launch: the fusion's backward has not run)
         GradReducer.dw_open = False      # (the encoders' Linear layers behind this point keep their grouped launches)
-        if GradReducer.dw_at_fusion:
-            GradReducer.flush_dw()
-        GradReducer.run_early_step(g.device)
+        GradReducer.flush_dw()
         return g
 
 
@@ -2291,7 +2203,6 @@ class EmbedPE(Function):
             _call("mmvae_embed_pe_bwd", H.ptr(onehot), H.ptr(dx), H.ptr(de), H.ptr(ws), B, T, V, mode, B0, acc, dpc,
                   H.stream())
         GradReducer.run_side_tail(dx.device)      # the text encoder's LAST backward launch: its stream idles from here on
-        GradReducer.run_early_step(dx.device, 4)
         return None, ret, None, None, None, None, None
 
 
@@ -2333,13 +2244,7 @@ def _linear_wgrad(dy2, x2, w, b, gw, gb, x_act=H.ACT_NONE):
     Returns the tensors to hand back to autograd (None when accumulated into the preset gradient views)."""
     M, N = dy2.shape
     K = x2.shape[1]
-    dw, acc_w, ret_w = _new_like_param(w, gw)
-    db, ret_b = None, None
-    if b is not None:
-        if gb is not None:
-            db = gb
-        else:
-            db = ret_b = torch.empty(N, device=dy2.device)
+    dw, db, acc_w, ret_w, ret_b = _grad_dst(w, gw, gb, b is not None, N)
     nws = H.lib().mmvae_linear_bwd_weight_ws_floats(M, N, K)
     nz = H.lib().mmvae_linear_bwd_weight_splits(M, N, K)
     defer = _defer(gw, gb if b is not None else gw)
@@ -2366,8 +2271,8 @@ TXT_WGRAD = True      # (module switch for the tests: False = one launch per wei
 
 def _txt_wgrad(jobs):
     """the weight half of every Linear behind a fused text layer: jobs = [(dy2, x2, w, b, gw, gb)] as _linear_wgrad takes them
-    (round 2's mmvae_linear_bwd_weight_batch -- the same jobs on the split-K GEMM body in one grid -- stays in the C ABI
-    with its unit test, but nothing on the path calls it any more)"""
+    (round 2's mmvae_linear_bwd_weight_batch -- jobs on the split-K GEMM body in one grid -- now serves the parked Linear
+    weight gradients: GradReducer.flush_dw)"""
     lib = H.lib()
     ok = TXT_WGRAD and 1 <= len(jobs) <= H.TXT_WGRAD_MAX and all(
         b is not None and _defer(gw, gb) and dy2.is_contiguous() and x2.is_contiguous() and
@@ -2385,9 +2290,8 @@ def _txt_wgrad(jobs):
         j = arr[i]
         j.dy, j.x, j.ws, j.M, j.N, j.K = H.ptr(dy2), H.ptr(x2), H.ptr(ws), M, N, K
         segs.append((ws, nz, gw, gb, N, K, nws // nz))
-    GradReducer.run_early_step(jobs[0][0].device, 2)
+    GradReducer.run_early_step(jobs[0][0].device)
     _call("mmvae_txt_wgrad", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
-    GradReducer.run_early_step(jobs[0][0].device, 3)
     for ws, nz, gw, gb, N, K, pitch in segs:      # (partial row z: [N * K weight sums | N bias sums] at ws + z * pitch)
         GradReducer.add(ws.data_ptr(), gw, nz, N * K, pitch)
         GradReducer.add(ws.data_ptr() + 4 * N * K, gb, nz, N, pitch)
@@ -3045,31 +2949,29 @@ def adabelief_flat(p, g, m, s, lr, beta1, beta2, eps, step, step_dev=None, grad_
           H.ptr(step_dev), grad_scale, int(zero_grad), H.stream())
 
 
+def _tail_args(tail):
+    """the ELBO assembly that rides on a fold + Adam launch (GradReducer.tail) as that launch's trailing arguments"""
+    if tail is None:
+        return None, None, None, 0, 0, 0
+    rp, flat, out, n, B, k = tail["args"]
+    return ctypes.byref(rp), flat, H.ptr(out), n, B, k
+
+
 def adam_fold_flat(p, g, m, v, vmax, lr, beta1, beta2, eps, step_dev, grad_scale, zero_grad, deferred):
     """GradReducer.deferred + Adam(amsgrad) in one launch (mmvae_adam_fold_flat)"""
     WEIGHT_GEN[0] += 1
-    tail = deferred["tail"]
-    if tail is not None:
-        rp, flat, out, n, B, k = tail["args"]
-        extra = (ctypes.byref(rp), flat, H.ptr(out), n, B, k)
-    else:
-        extra = (None, None, None, 0, 0, 0)
     _call("mmvae_adam_fold_flat", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), lr, beta1, beta2, eps,
-          H.ptr(step_dev), grad_scale, int(zero_grad), ctypes.byref(deferred["table"]), *extra, H.stream())
+          H.ptr(step_dev), grad_scale, int(zero_grad), ctypes.byref(deferred["table"]), *_tail_args(deferred["tail"]),
+          H.stream())
 
 
 def adam_fold_range(p, g, m, v, vmax, lo, hi, advance, lr, beta1, beta2, eps, step_dev, grad_scale, zero_grad, table, tail=None):
     """the same over elements [lo, hi) only, with the segments of `table` (H.ReduceSegments or None) that lie inside
     (mmvae_adam_fold_range); advance: this is the launch that closes the step"""
     WEIGHT_GEN[0] += 1
-    if tail is not None:
-        rp, flat, out, n, B, k = tail["args"]
-        extra = (ctypes.byref(rp), flat, H.ptr(out), n, B, k)
-    else:
-        extra = (None, None, None, 0, 0, 0)
     _call("mmvae_adam_fold_range", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), int(lo), int(hi),
           int(advance), lr, beta1, beta2, eps, H.ptr(step_dev), grad_scale, int(zero_grad),
-          ctypes.byref(table) if table is not None else None, *extra, H.stream())
+          ctypes.byref(table) if table is not None else None, *_tail_args(tail), H.stream())
 
 
 def step_inc(step_dev):
