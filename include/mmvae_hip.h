@@ -791,6 +791,41 @@ int mmvae_lme_update(double* state, const float* lw0, const mmvae_lme_rows* rows
 int mmvae_lme_finish(const double* state, double* out, double* ess, int n_rows, long K, int B, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Latent classification (TorchMMVAE.classify_latents; csrc/probe.hip): linear probes on latent samples, the
+ * reference's Latent_Classifier + CrossEntropyLoss + optim.Adam loop (eval/eval_mnistsvhn.py:24-67,
+ * eval/mnistsvhn_helper.py:180-188).  Forward only for the model: no autograd.
+ *   z (S,N,D) fp32: S packed latent matrices;  labels (A,N) int32: A label rows;
+ *   probes: HOST pointer to (P,3) ints, probe p = (s_p, a_p, C_p): rows z[s_p], labels labels[a_p], C_p classes;
+ *   state (P,3,Cmax (D+1)) fp32: per probe [parameters | exp_avg | exp_avg_sq], each a row-major (Cmax, D+1) matrix
+ *   [W | b] (column D is the bias); classes >= C_p are never read or written.
+ * mmvae_probe_train: one workgroup per probe runs the global steps [step0, step0 + n_steps).  Step t belongs to epoch
+ *   e = t / ceil(N / batch) and covers the positions [i batch, min(N, (i + 1) batch)), i = t % ceil(N / batch), of that
+ *   epoch (the last minibatch of an epoch may be short; its mean runs over the rows it has); position -> row through
+ *   order (order_epochs, N) int32 (values in [0, N), row e is read for epoch e), or NULL = sequential.  Per step:
+ *     logits = z_b W^T + b;  loss = mean_r (logsumexp_c logits - logits[label]);  dlogit = (softmax - onehot) / rows;
+ *     dW = dlogit^T z_b, db = sum_r dlogit;  torch.optim.Adam defaults (betas 0.9 / 0.999, eps 1e-8, no amsgrad, no
+ *     weight decay), bias corrections of step t + 1:  W -= lr / (1 - b1^(t+1)) * m / (sqrt(v) / sqrt(1 - b2^(t+1)) + eps).
+ *   loss (P, n_steps): the mean loss of every step.  The state is read at the start of the launch and written at its end:
+ *   a training split over launches at any step is bit-identical to one launch.  Every sum runs in a fixed order (no
+ *   atomics): two runs are bit-identical, and a probe's result does not depend on the other probes of the launch.
+ * mmvae_probe_eval: pred (P,N) int32 = argmax_c logits (the first maximum), nll (P,N) = the row's cross-entropy against
+ *   labels[a_p] (labels may be NULL: nll is then 0 and a_p is not looked at).
+ * D <= 256, 2 <= C_p <= Cmax <= MMVAE_PROBE_MAX_CLASSES, batch >= 1, 0 <= s_p < S, 0 <= a_p < A,
+ * P <= MMVAE_PROBE_MAX_PROBES; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.  Labels outside [0, C_p)
+ * are the caller's error (the Python binding raises ValueError before the launch).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_PROBE_MAX_CLASSES 32
+#define MMVAE_PROBE_MAX_PROBES 64
+int mmvae_probe_train(float* state, const float* z, const int* labels, const int* order, int order_epochs,
+                      const int* probes, float* loss, int P, int S, int A, int N, int D, int Cmax, int batch, long step0,
+                      int n_steps, float lr, mmvae_stream_t stream);
+/* rows of the latent tile both kernels work on, a function of D alone (the order of the per-step loss sum follows it);
+ * 0 for D outside 1 .. 256 */
+int mmvae_probe_tile_rows(int D);
+int mmvae_probe_eval(const float* state, const float* z, const int* labels, const int* probes, int* pred, float* nll,
+                     int P, int S, int A, int N, int D, int Cmax, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -71,6 +71,9 @@ class MoeKBwdArgs(ctypes.Structure):
 MIX_MAX_COMPONENTS = 8
 
 
+PROBE_MAX_CLASSES, PROBE_MAX_PROBES = 32, 64
+
+
 class LmeRows(ctypes.Structure):
     _fields_ = [("ll", c_p * MOE_MAX_MODS)]
 
@@ -279,6 +282,9 @@ SIGNATURES = {
     "mmvae_mix_ksample_logw_fwd": (c_i, [c_p, c_u, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p] + [c_i] * 5 + [c_p]),
     "mmvae_lme_update": (c_i, [c_p, c_p, ctypes.POINTER(LmeRows), c_i, c_u, c_i, c_i, c_p]),
     "mmvae_lme_finish": (c_i, [c_p, c_p, c_p, c_i, c_l, c_i, c_p]),
+    "mmvae_probe_train": (c_i, [c_p] * 4 + [c_i, ctypes.POINTER(c_i), c_p] + [c_i] * 7 + [c_l, c_i, c_f, c_p]),
+    "mmvae_probe_tile_rows": (c_i, [c_i]),
+    "mmvae_probe_eval": (c_i, [c_p] * 3 + [ctypes.POINTER(c_i), c_p, c_p] + [c_i] * 6 + [c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

@@ -61,6 +61,7 @@ class TorchMMVAE(nn.Module):
         # does not move when a model is evaluated between two steps
         self.register_buffer("_eval_rng_state", torch.tensor([(torch.initial_seed() ^ 0x5DEECE66) & 0x7FFFFFFF, 0, 0],
                                                              dtype=torch.int32), persistent=False)
+        self._eval_draws = False    # latents_for: forward()'s draws come from the evaluation generator
 
     def set_likelihood_scales(self):
         """mmvae_base.py:41-47"""
@@ -114,7 +115,7 @@ class TorchMMVAE(nn.Module):
         if self.eps_override is not None:
             e = self.eps_override.pop(0)
             return e.reshape(B, D).to(device=device, dtype=torch.float32).contiguous()
-        return ops.randn((B, D), self._rng_state)
+        return ops.randn((B, D), self._eval_rng_state if self._eval_draws else self._rng_state)
 
     def _draw_many(self, n, B, D, device):
         """n draws of shape (B, D) in one launch (`eps_override`: n consecutive recorded draws)"""
@@ -321,6 +322,136 @@ class TorchMMVAE(nn.Module):
                 ops.lme_update(state, lw0, rows)
             out, ess = ops.lme_finish(state, K)
         return {"joint": out[0], "cond": {m: out[1 + i] for i, m in enumerate(targets)}, "ess": ess}
+
+    # ---- latent classification ----------------------------------------------------------------
+    def _latents_of(self, x, of):
+        """the latent sample forward(x) stores under latent_samples[of]["latents"], from the same draws in the same
+        order, without running the decoders (every mixer implements it beside its forward())"""
+        raise NotImplementedError(f"{self.modelName}: latents_for is not built for this mixer")
+
+    def latents_for(self, mods, given, of=None):
+        """(B, D): the latent sample that forward() stores under latent_samples["latents"] for modality `of` (default:
+        the first of `given`) when only the modalities in `given` carry data -- the tensor the reference's
+        classify_latents reads (eval/eval_mnistsvhn.py:24-67), K = 1 flattened.  DMVAE: its shared code.
+        Encoders and the mixing only: the decoders are skipped.  Needs eval mode; runs without gradients; the noise comes
+        from the evaluation generator (`_eval_rng_state`), so the training noise state, dropout counters, gradients and
+        the optimiser stay as they are.  With `eps_override` the draws are consumed as forward() consumes them and the
+        result equals forward()'s bit for bit."""
+        names = list(self.vaes.keys())
+        given = [m for m in names if m in (given or [])]
+        if self.training:
+            raise RuntimeError("latents_for needs eval mode (model.eval()): dropout would make the latents a function of "
+                               "the masks")
+        if not given or any(m not in mods or mods[m]["data"] is None for m in given):
+            raise ValueError("latents_for: `given` must name modalities with data")
+        of = given[0] if of is None else of
+        if of not in names:
+            raise ValueError(f"latents_for: `of` = {of!r} is not a modality of this model ({names})")
+        self._eval_draws = True
+        try:
+            with torch.no_grad():
+                z = self._latents_of(self._given_only(mods, given), of)
+        finally:
+            self._eval_draws = False
+        return z.reshape(-1, z.shape[-1])
+
+    def default_given(self):
+        """every single modality, then all of them together"""
+        names = list(self.vaes.keys())
+        return [[n] for n in names] + [names]
+
+    def probe_table(self, n_classes, n_attributes, given=None):
+        """-> (given lists in modality order, their keys "+".join(names), [(s, a, C)]): probe p = s * A + a reads the
+        latent matrix of subset s and label column a, with n_classes[a] classes"""
+        names = list(self.vaes.keys())
+        given = self.default_given() if given is None else [list(g) for g in given]
+        for g in given:
+            if not g or any(m not in names for m in g):
+                raise ValueError(f"classify_latents: `given` entry {g} must name modalities of this model ({names})")
+        given = [[m for m in names if m in g] for g in given]
+        A = int(n_attributes)
+        n_classes = [int(n_classes)] * A if isinstance(n_classes, int) else [int(c) for c in n_classes]
+        if len(n_classes) != A:
+            raise ValueError(f"classify_latents: {len(n_classes)} class counts for {A} label columns")
+        for C in n_classes:
+            if not 2 <= C <= ops.H.PROBE_MAX_CLASSES:
+                raise ValueError(f"classify_latents: {C} classes (2 .. {ops.H.PROBE_MAX_CLASSES} are on the MI355X path)")
+        return given, ["+".join(g) for g in given], [(s, a, n_classes[a]) for s in range(len(given)) for a in range(A)]
+
+    @staticmethod
+    def _label_matrix(batches, what):
+        """labels of an iterable of (batch, labels) -> (A, N) int64 on the host"""
+        cols = []
+        for _, y in batches:
+            y = torch.as_tensor(y).detach().cpu()
+            if y.is_floating_point() or y.dim() not in (1, 2):
+                raise ValueError(f"classify_latents: {what} labels must be an integer (B,) or (B, A) array")
+            cols.append(y.long().reshape(y.shape[0], -1))
+        if not cols:
+            raise ValueError(f"classify_latents: the {what} set is empty")
+        return torch.cat(cols, 0).t().contiguous()
+
+    def classify_latents(self, train, test, n_classes, given=None, epochs=30, batch_size=128, lr=1e-3, seed=0,
+                         shuffle=False, init=None):
+        """Latent classification (eval/eval_mnistsvhn.py:24-67): one linear probe (nn.Linear + CrossEntropyLoss + Adam)
+        per (conditioning subset, label column), trained on the latents `latents_for` gives for the train set and
+        scored on those of the test set.  `train` / `test`: iterables of (batch dict, labels (B,) or (B, A) ints);
+        `n_classes`: an int or one per label column; `given`: modality-name lists (default_given()).
+        Both sets are encoded once per subset into packed (S, N, D) device matrices; the P = S A probes of probe_table()
+        train side by side, one ops.probe_train launch per epoch (`epochs` passes in minibatches of `batch_size`, in
+        sequential order or, `shuffle`, in per-epoch permutations drawn from torch.Generator(seed)); the init is
+        nn.Linear's from the same seed or the (W, b) pairs of `init`.
+        -> {"accuracy": {(given_key, a): float}, "loss": {(given_key, a): float} (mean test cross-entropy),
+            "pred": {(given_key, a): (N_test,) int32}, "train_loss": (P, steps), "state": ..., "probes": [(s, a, C)]}."""
+        if self.training:
+            raise RuntimeError("classify_latents needs eval mode (model.eval()): dropout would make the latents a function "
+                               "of the masks")
+        D = self.n_latents
+        if D > 256:
+            raise ValueError(f"classify_latents: D = {D} latent dimensions (up to 256 are on the MI355X path)")
+        train, test = list(train), list(test)
+        y_tr, y_te = self._label_matrix(train, "train"), self._label_matrix(test, "test")
+        if y_tr.shape[0] != y_te.shape[0]:
+            raise ValueError(f"classify_latents: {y_tr.shape[0]} train label columns, {y_te.shape[0]} test label columns")
+        A = y_tr.shape[0]
+        given, keys, probes = self.probe_table(n_classes, A, given)
+        if len(probes) > ops.H.PROBE_MAX_PROBES:
+            raise ValueError(f"classify_latents: {len(probes)} probes ({len(given)} subsets x {A} label columns); one launch "
+                             f"trains up to {ops.H.PROBE_MAX_PROBES}")
+        for _, a, C in probes[:A]:
+            for y, what in ((y_tr, "train"), (y_te, "test")):
+                if int(y[a].min()) < 0 or int(y[a].max()) >= C:
+                    raise ValueError(f"classify_latents: {what} label column {a} holds labels in [{int(y[a].min())}, "
+                                     f"{int(y[a].max())}], outside [0, {C})")
+        for batch, _ in train + test:
+            for g in given:
+                if any(m not in batch or batch[m]["data"] is None for m in g):
+                    raise ValueError(f"classify_latents: `given` entry {g} names a modality without data")
+        if int(epochs) < 1 or int(batch_size) < 1:
+            raise ValueError(f"classify_latents: epochs = {epochs}, batch_size = {batch_size}")
+        z_tr = torch.stack([torch.cat([self.latents_for(b, g) for b, _ in train]) for g in given]).contiguous()
+        z_te = torch.stack([torch.cat([self.latents_for(b, g) for b, _ in test]) for g in given]).contiguous()
+        dev = z_tr.device
+        l_tr, l_te = y_tr.to(device=dev, dtype=torch.int32), y_te.to(device=dev, dtype=torch.int32)
+        N, P, Cmax = z_tr.shape[1], len(probes), max(C for _, _, C in probes)
+        state = ops.probe_state(P, D, Cmax, dev, init=init, seed=seed)
+        order = None
+        if shuffle:
+            g = torch.Generator().manual_seed(int(seed))
+            order = torch.stack([torch.randperm(N, generator=g) for _ in range(int(epochs))]).to(device=dev,
+                                                                                                 dtype=torch.int32)
+        spe = (N + int(batch_size) - 1) // int(batch_size)
+        curve = torch.cat([ops.probe_train(state, z_tr, l_tr, probes, batch_size, e * spe, spe, lr=lr, order=order,
+                                           validate=False) for e in range(int(epochs))], 1)
+        pred, nll = ops.probe_eval(state, z_te, l_te, probes)
+        pred, nll = pred.cpu(), nll.cpu().double()
+        out = {"accuracy": {}, "loss": {}, "pred": {}, "train_loss": curve, "state": state, "probes": probes}
+        for p, (s, a, _) in enumerate(probes):
+            k = (keys[s], a)
+            out["accuracy"][k] = int((pred[p].long() == y_te[a]).sum()) / float(y_te.shape[1])
+            out["loss"][k] = float(nll[p].mean())
+            out["pred"][k] = pred[p]
+        return out
 
     def product_of_experts(self, mu, logvar, with_prior=False):
         """mmvae_base.py:203-222 on the fused kernel: mu/logvar are lists of (B,D) tensors; returns

@@ -258,8 +258,18 @@ class MoPOE(TorchMMVAE):
         comps = torch.stack([torch.cat([mu[0], var[0]], -1) for mu, var in subsets.values()])
         return comps, [False] * comps.shape[0]
 
+    def _latents_of(self, x, of):
+        """forward()'s z of modality `of`: one draw per modality from the joint, in modality order"""
+        j_mu, j_var = self.modality_mixing(x)["joint"]
+        z = None
+        for mod in self.vaes:
+            eps = self._draw(j_mu.shape[0], j_mu.shape[1], j_mu.device).unsqueeze(0)
+            if mod == of:
+                z = j_mu + j_var * eps
+        return z
+
     def forward(self, inputs, K=1):
-        """mmvae_models.py:351-370"""
+        """mmvae_models.py:351-370.  (`_latents_of` above restates the draws of this method in order: keep them in step.)"""
         latents = self.modality_mixing(inputs)
         qz_d, px_d, z_d, qz_joint = {}, {}, {}, {}
         j_mu, j_var = latents["joint"]
@@ -523,8 +533,13 @@ class POE(TorchMMVAE):
         mu, var, _ = self.modality_mixing(self._given_only(mods, given))
         return torch.cat([mu, var], -1).unsqueeze(0), [False]
 
+    def _latents_of(self, x, of):
+        """forward()'s z: one draw from the product, shared by every modality"""
+        mu, var, _ = self.modality_mixing(x)
+        return mu + var * self._draw(mu.shape[0], mu.shape[1], mu.device).unsqueeze(0)
+
     def forward(self, inputs, K=1):
-        """mmvae_models.py:189-208"""
+        """mmvae_models.py:189-208.  (`_latents_of` above restates the draw of this method: keep them in step.)"""
         mu, var, single = self.modality_mixing(inputs)
         qz_x = normal(mu, var)
         eps = torch.stack([self._draw(mu.shape[0], mu.shape[1], mu.device) for _ in range(K)])
@@ -723,11 +738,27 @@ class MOE(TorchMMVAE):
         comps = torch.stack([packed_head(*self.vaes[m].enc(mods[m])) for m in given])
         return comps, [self._laplace[names.index(m)] for m in given]
 
+    def _latents_of(self, x, of):
+        """forward()'s z of modality `of`: its own posterior's sample, or the first present modality's when it is missing;
+        one draw per present modality, in modality order"""
+        _, filled = self.get_missing_modalities(x)
+        src, z = (of if of in filled else filled[0]), None
+        for m, vae in self.vaes.items():
+            if x[m]["data"] is None:
+                continue
+            if m == src:
+                mu, lv = vae.enc(x[m])
+                z = mu + lv * self._draw(mu.shape[0], mu.shape[1], mu.device).unsqueeze(0)
+            else:      # (its draw is consumed, its encoder is not needed)
+                self._draw(x[m]["data"].shape[0], self.n_latents, x[m]["data"].device)
+        return z
+
     def forward(self, x, K=1):
         """mmvae_models.py:80-117, including the cross-generation calls with missing modalities
         (`data` None, masks kept: models/trainer.py:179-215): a missing modality takes the latent sample of the FIRST
         present one (the reference aliases that modality's dict, :105-108) and is decoded from it under its own masks;
-        every target's cross entry is a fresh one-entry dict, so the last source in dict order wins (:109-114)."""
+        every target's cross entry is a fresh one-entry dict, so the last source in dict order wins (:109-114).
+        (`_latents_of` above restates the draws of this method in order: keep them in step.)"""
         missing, filled = self.get_missing_modalities(x)
         assert len(filled) > 0, "at least one modality must be present for forward call"
         qz, zs, px, cross = {}, {}, {}, {}
@@ -922,12 +953,32 @@ class DMVAE(TorchMMVAE):
     def modality_mixing(self, mods):
         return self.encode(mods)
 
+    def _latents_of(self, x, of):
+        """forward()'s shared code of modality `of` (its own shared posterior, or the first present modality's), with the
+        draws before it consumed in forward()'s order: joint, then per modality shared, private, one per other present"""
+        _, filled = self.get_missing_modalities(x)
+        D = self.n_latents
+        src = of if of in filled else filled[0]
+        mu, lv = self.vaes[src].enc(x[src])
+        mu, lv = mu[:, :D], lv[:, :D]
+        B, dev = mu.shape[0], mu.device
+        self._draw(B, D, dev)                                     # z_joint
+        for n, vae in self.vaes.items():
+            e = self._draw(B, D, dev).unsqueeze(0)                # z_shared
+            if n == of:
+                return mu + lv * e
+            self._draw(B, vae.private_latents, dev)               # z_private
+            for m in filled:
+                if m != n:
+                    self._draw(B, D, dev)                         # cross reconstruction
+
     def forward(self, x, K=1):
         """mmvae_models.py:467-503: the container the evaluation code reads (shared / private posteriors, joint
         posterior, own / joint / cross reconstructions), missing modalities (`data` None, masks kept) included: the
         joint is the product of the PRESENT shared experts; a missing modality samples its shared code from the first
         present modality's posterior and its private code from N(0, I) (:489-493); cross reconstructions from a fresh
-        shared draw of every other present modality (:499-502).  Noise in the reference's draw order."""
+        shared draw of every other present modality (:499-502).  Noise in the reference's draw order.
+        (`_latents_of` above restates the draws of this method in order: keep them in step.)"""
         if K != 1:
             raise NotImplementedError("dmvae.forward: K = 1 only on this path")
         missing, filled = self.get_missing_modalities(x)

@@ -138,6 +138,15 @@ class MultimodalVAE(nn.Module):
             self.log("test_loglik_mod_{}".format(names.index(m)), v.mean(), batch_size=self.config.batch_size)
         return out
 
+    def classify_latents(self, train, test, n_classes, **kwargs):
+        """latent classification accuracy (TorchMMVAE.classify_latents: one linear probe per conditioning subset and
+        label column, trained on chip; the model must be in eval mode), logged as test_latent_acc_<given_key>_<a>"""
+        out = self.model.classify_latents(train, test, n_classes, **kwargs)
+        for (key, a), acc in out["accuracy"].items():
+            self.log("test_latent_acc_{}_{}".format(key, a), torch.tensor(acc, dtype=torch.float64),
+                     batch_size=self.config.batch_size)
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;

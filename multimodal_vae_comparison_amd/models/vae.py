@@ -103,6 +103,13 @@ class VAE(BaseVae):
         raise NotImplementedError("unimodal VAE: estimate_log_likelihood is built for the multimodal mixers poe, moe and "
                                   "mopoe (TorchMMVAE.estimate_log_likelihood)")
 
+    def latents_for(self, *args, **kwargs):
+        raise NotImplementedError("unimodal VAE: latents_for is built for the multimodal mixers (TorchMMVAE.latents_for)")
+
+    def classify_latents(self, *args, **kwargs):
+        raise NotImplementedError("unimodal VAE: classify_latents is built for the multimodal mixers "
+                                  "(TorchMMVAE.classify_latents)")
+
     # ---- the unimodal case: `self.model = vaes["mod_1"]` (models/trainer.py:112-113) ------------------------------
     def objective(self, data):
         """VAE.forward + objective with UnimodalObjective.elbo (models/vae.py:92-119,268-282, models/objectives.py:233-247):
