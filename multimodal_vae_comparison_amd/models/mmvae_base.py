@@ -5,6 +5,7 @@ import numpy as np
 import torch
 import torch.distributions as dist
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .. import ops
 from .nn_modules import DropoutState
@@ -92,6 +93,10 @@ class TorchMMVAE(nn.Module):
         return dist.Laplace(loc, scale, validate_args=False) if self._lap(vae) else normal(loc, scale)
 
     @property
+    def pz_params(self):
+        return self._pz_params[0], F.softmax(self._pz_params[1], dim=1) * self._pz_params[1].size(-1)
+
+    @property
     def latent_factorization(self):
         return any(v.private_latents is not None for v in self.vaes.values())
 
@@ -116,6 +121,11 @@ class TorchMMVAE(nn.Module):
             e = self.eps_override.pop(0)
             return e.reshape(B, D).to(device=device, dtype=torch.float32).contiguous()
         return ops.randn((B, D), self._eval_rng_state if self._eval_draws else self._rng_state)
+
+    def _draws(self, K, B, D, device):
+        """(K, B, D): K consecutive draws of shape (B, D), the K axis forward() hands to the decoders"""
+        e = [self._draw(B, D, device) for _ in range(K)]
+        return e[0].unsqueeze(0) if K == 1 else torch.stack(e)
 
     def _draw_many(self, n, B, D, device):
         """n draws of shape (B, D) in one launch (`eps_override`: n consecutive recorded draws)"""
@@ -182,6 +192,21 @@ class TorchMMVAE(nn.Module):
         for s in streams:
             if s is not None:
                 cur.wait_stream(s)
+
+    def _encode_towers(self, mods):
+        """every tower's encoder on its stream, joined again -> (packed heads [mu | lv] in modality order, the towers'
+        streams (None: the current one), the current stream, the stream every tower really runs on, device)"""
+        dev = next(v["data"] for v in mods.values() if v["data"] is not None).device
+        streams = self._tower_streams(dev)
+        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
+        real = [cur if st is None else st for st in streams]
+        self._fork(streams, dev, mods)
+        packed = []
+        for n, st in zip(self.vaes, streams):
+            with torch.cuda.stream(st):
+                packed.append(packed_head(*self.vaes[n].enc(mods[n])))
+        self._join(streams, dev)
+        return packed, streams, cur, real, dev
 
     # ---- plumbing shared by the mixers ----------------------------------------------------------
     def make_output_dict(self, encoder_dist=None, decoder_dist=None, latent_samples=None, joint_dist=None,
@@ -324,10 +349,16 @@ class TorchMMVAE(nn.Module):
         return {"joint": out[0], "cond": {m: out[1 + i] for i, m in enumerate(targets)}, "ess": ess}
 
     # ---- latent classification ----------------------------------------------------------------
-    def _latents_of(self, x, of):
-        """the latent sample forward(x) stores under latent_samples[of]["latents"], from the same draws in the same
-        order, without running the decoders (every mixer implements it beside its forward())"""
+    def _sample(self, x, K=1, of=None):
+        """Encoders, mixing and draws of forward(x, K), the draws through `_draw` in the reference's order -> (what
+        forward() builds its distributions from, iterable of (modality, z, ...) in modality order: z is what forward()
+        stores under latent_samples[modality]["latents"]).  An iterable that draws while it is read lets forward() decode
+        between the draws, as the reference does.  `of` (latents_for): only that modality's z is wanted."""
         raise NotImplementedError(f"{self.modelName}: latents_for is not built for this mixer")
+
+    def _latents_of(self, x, of):
+        """forward(x)'s latent_samples[of]["latents"] without the decoders (the iterable is read to its end: its draws)"""
+        return {m: z for m, z, *_ in self._sample(x, of=of)[1]}[of]
 
     def latents_for(self, mods, given, of=None):
         """(B, D): the latent sample that forward() stores under latent_samples["latents"] for modality `of` (default:

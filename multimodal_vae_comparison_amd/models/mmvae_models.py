@@ -7,7 +7,6 @@ import os
 from itertools import chain, combinations
 
 import torch
-import torch.nn.functional as F
 
 from .. import ops
 from .mmvae_base import TorchMMVAE, normal, packed_head
@@ -40,10 +39,6 @@ class MoPOE(TorchMMVAE):
         self._require_normal_priors()
         self.subsets = self.set_subsets()
         self.weights = None
-
-    @property
-    def pz_params(self):
-        return self._pz_params[0], F.softmax(self._pz_params[1], dim=1) * self._pz_params[1].size(-1)
 
     def set_subsets(self):
         """mmvae_models.py:279-294: non-empty subsets in itertools.combinations order, keyed 'mod_i_mod_j'"""
@@ -258,27 +253,22 @@ class MoPOE(TorchMMVAE):
         comps = torch.stack([torch.cat([mu[0], var[0]], -1) for mu, var in subsets.values()])
         return comps, [False] * comps.shape[0]
 
-    def _latents_of(self, x, of):
-        """forward()'s z of modality `of`: one draw per modality from the joint, in modality order"""
-        j_mu, j_var = self.modality_mixing(x)["joint"]
-        z = None
-        for mod in self.vaes:
-            eps = self._draw(j_mu.shape[0], j_mu.shape[1], j_mu.device).unsqueeze(0)
-            if mod == of:
-                z = j_mu + j_var * eps
-        return z
+    def _sample(self, x, K=1, of=None):
+        """K draws per modality from the joint, in modality order, each taken when its modality is read (every modality's
+        draw is taken whichever one `of` asks for)"""
+        latents = self.modality_mixing(x)
+        j_mu, j_var = latents["joint"]
+        return latents, ((mod, j_mu + j_var * self._draws(K, *j_mu.shape, j_mu.device)) for mod in self.vaes)
 
     def forward(self, inputs, K=1):
-        """mmvae_models.py:351-370.  (`_latents_of` above restates the draws of this method in order: keep them in step.)"""
-        latents = self.modality_mixing(inputs)
+        """mmvae_models.py:351-370"""
+        latents, zs = self._sample(inputs, K)
         qz_d, px_d, z_d, qz_joint = {}, {}, {}, {}
-        j_mu, j_var = latents["joint"]
-        for mod, vae in self.vaes.items():
+        for mod, z in zs:
+            vae = self.vaes[mod]
             sh = latents["modalities"][mod]["shared"]
             qz_d[mod] = normal(*sh) if sh is not None else None
-            qz_joint[mod] = normal(j_mu, j_var)
-            eps = torch.stack([self._draw(j_mu.shape[0], j_mu.shape[1], j_mu.device) for _ in range(K)])
-            z = j_mu + j_var * eps
+            qz_joint[mod] = normal(*latents["joint"])
             z_d[mod] = {"latents": z, "masks": inputs[mod]["masks"]}
             px_d[mod] = self._px(vae, *vae.dec(z_d[mod]))
         return self.make_output_dict(qz_d, px_d, z_d, qz_joint)
@@ -302,10 +292,6 @@ class POE(TorchMMVAE):
         self.subset_order = None
         self.batch_dropout_towers = True      # decoders with dropout: all subset passes in one call (objective docstring)
         self._job_calls = {}                  # launches of a decoder call the last time it ran (_decoder_lanes)
-
-    @property
-    def pz_params(self):
-        return self._pz_params[0], F.softmax(self._pz_params[1], dim=1) * self._pz_params[1].size(-1)
 
     def _subsets(self):
         names = list(self.vaes.keys())
@@ -533,24 +519,18 @@ class POE(TorchMMVAE):
         mu, var, _ = self.modality_mixing(self._given_only(mods, given))
         return torch.cat([mu, var], -1).unsqueeze(0), [False]
 
-    def _latents_of(self, x, of):
-        """forward()'s z: one draw from the product, shared by every modality"""
-        mu, var, _ = self.modality_mixing(x)
-        return mu + var * self._draw(mu.shape[0], mu.shape[1], mu.device).unsqueeze(0)
+    def _sample(self, x, K=1, of=None):
+        """K draws from the product, shared by every modality"""
+        mu, var, single = self.modality_mixing(x)
+        z = mu + var * self._draws(K, *mu.shape, mu.device)
+        return (normal(mu, var), single), [(mod, z) for mod in x]
 
     def forward(self, inputs, K=1):
-        """mmvae_models.py:189-208.  (`_latents_of` above restates the draw of this method: keep them in step.)"""
-        mu, var, single = self.modality_mixing(inputs)
-        qz_x = normal(mu, var)
-        eps = torch.stack([self._draw(mu.shape[0], mu.shape[1], mu.device) for _ in range(K)])
-        z = mu + var * eps
-        qz_d, px_d, z_d = {}, {}, {}
-        for mod, vae in self.vaes.items():
-            px_d[mod] = normal(*vae.dec({"latents": z, "masks": inputs[mod]["masks"]}))
-        for key in inputs.keys():
-            qz_d[key] = qz_x
-            z_d[key] = {"latents": z, "masks": inputs[key]["masks"]}
-        return self.make_output_dict(single, px_d, z_d, joint_dist=qz_d)
+        """mmvae_models.py:189-208"""
+        (qz_x, single), zs = self._sample(inputs, K)
+        z_d = {key: {"latents": z, "masks": inputs[key]["masks"]} for key, z in zs}
+        px_d = {mod: normal(*vae.dec(z_d[mod])) for mod, vae in self.vaes.items()}
+        return self.make_output_dict(single, px_d, z_d, joint_dist={key: qz_x for key in z_d})
 
 
 class MOE(TorchMMVAE):
@@ -585,10 +565,6 @@ class MOE(TorchMMVAE):
         self._laplace = [v.prior_str == "laplace" for v in self.vaes.values()]
         self.register_buffer("_theta0", torch.zeros(1, n_latents), persistent=False)   # softmax(0)*D = 1: N(0,1)
 
-    @property
-    def pz_params(self):
-        return self._pz_params[0], F.softmax(self._pz_params[1], dim=1) * self._pz_params[1].size(-1)
-
     batch_passes = True      # elbo: a decoder's own + cross pass in one call (objective)
 
     def _draw_k(self, m, K, B, D, dev):
@@ -604,7 +580,6 @@ class MOE(TorchMMVAE):
         self._begin_step()
         names = list(self.vaes.keys())
         M = len(names)
-        dev = next(v["data"] for v in data.values() if v["data"] is not None).device
         # Round 4: the towers on two streams (encoders side by side, decoders + their loss terms side by side; autograd
         # replays every node on its forward stream), and each decoder's own + cross pass as ONE call over 2 B latent
         # samples (rows [0, B) decode z_r, rows [B, 2B) z_o; the row-sum kernels pair output row k with target row k % B).
@@ -612,15 +587,7 @@ class MOE(TorchMMVAE):
         # extracted-mask parity test splits them by pass).  optimal_sigma fits ONE sigma per call: its passes stay apart.
         # The shipped config_cdspritesplus.yml step is a chain of ~260 launches, ~115 of them the text decoder's two
         # op-by-op passes: 4.00 -> 3.4 ms/step.
-        streams = self._tower_streams(dev)
-        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        real = [cur if st is None else st for st in streams]
-        self._fork(streams, dev, data)
-        packed = [None] * M
-        for i, (n, st) in enumerate(zip(names, streams)):
-            with torch.cuda.stream(st):
-                packed[i] = packed_head(*self.vaes[n].enc(data[n]))
-        self._join(streams, dev)
+        packed, streams, cur, real, dev = self._encode_towers(data)
         B, D = packed[0].shape[0], self.n_latents
         zs, kls = [], []
         for i in range(M):
@@ -675,16 +642,7 @@ class MOE(TorchMMVAE):
         self._begin_step()
         names = list(self.vaes.keys())
         M, K, D = len(names), int(self.K), self.n_latents
-        dev = next(v["data"] for v in data.values() if v["data"] is not None).device
-        streams = self._tower_streams(dev)
-        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        real = [cur if st is None else st for st in streams]
-        self._fork(streams, dev, data)
-        packed = [None] * M
-        for i, (n, st) in enumerate(zip(names, streams)):
-            with torch.cuda.stream(st):
-                packed[i] = packed_head(*self.vaes[n].enc(data[n]))
-        self._join(streams, dev)
+        packed, streams, cur, real, dev = self._encode_towers(data)
         B = packed[0].shape[0]
         eps = [self._draw_k(m, K, B, D, dev) for m in range(M)]
         theta = self._pz_params[1]
@@ -738,41 +696,34 @@ class MOE(TorchMMVAE):
         comps = torch.stack([packed_head(*self.vaes[m].enc(mods[m])) for m in given])
         return comps, [self._laplace[names.index(m)] for m in given]
 
-    def _latents_of(self, x, of):
-        """forward()'s z of modality `of`: its own posterior's sample, or the first present modality's when it is missing;
-        one draw per present modality, in modality order"""
+    def _sample(self, x, K=1, of=None):
+        """K draws per present modality from its own posterior, in modality order; a missing modality takes the latent
+        sample of the FIRST present one (the reference aliases that modality's dict, mmvae_models.py:105-108)"""
         _, filled = self.get_missing_modalities(x)
-        src, z = (of if of in filled else filled[0]), None
+        assert len(filled) > 0, "at least one modality must be present for forward call"
+        src = {m: (m if m in filled else filled[0]) for m in self.vaes}
+        qz, drawn = {}, {}
         for m, vae in self.vaes.items():
-            if x[m]["data"] is None:
-                continue
-            if m == src:
+            data = x[m]["data"]
+            if data is None:
+                qz[m] = None
+            elif of is not None and m != src[of]:
+                # (latents_for: a present modality nobody samples from has its draw taken, its encoder is not run)
+                self._draws(K, data.shape[0], self.n_latents, data.device)
+            else:
                 mu, lv = vae.enc(x[m])
-                z = mu + lv * self._draw(mu.shape[0], mu.shape[1], mu.device).unsqueeze(0)
-            else:      # (its draw is consumed, its encoder is not needed)
-                self._draw(x[m]["data"].shape[0], self.n_latents, x[m]["data"].device)
-        return z
+                qz[m] = normal(mu, lv)
+                drawn[m] = mu + lv * self._draws(K, *mu.shape, mu.device)
+        return qz, [(m, drawn[src[m]]) for m in self.vaes if src[m] in drawn]
 
     def forward(self, x, K=1):
         """mmvae_models.py:80-117, including the cross-generation calls with missing modalities
-        (`data` None, masks kept: models/trainer.py:179-215): a missing modality takes the latent sample of the FIRST
-        present one (the reference aliases that modality's dict, :105-108) and is decoded from it under its own masks;
-        every target's cross entry is a fresh one-entry dict, so the last source in dict order wins (:109-114).
-        (`_latents_of` above restates the draws of this method in order: keep them in step.)"""
-        missing, filled = self.get_missing_modalities(x)
-        assert len(filled) > 0, "at least one modality must be present for forward call"
-        qz, zs, px, cross = {}, {}, {}, {}
-        for m, vae in self.vaes.items():
-            if x[m]["data"] is None:
-                qz[m] = None
-                continue
-            mu, lv = vae.enc(x[m])
-            qz[m] = normal(mu, lv)
-            eps = torch.stack([self._draw(mu.shape[0], mu.shape[1], mu.device) for _ in range(K)])
-            zs[m] = {"latents": mu + lv * eps, "masks": x[m]["masks"]}
-        for m in missing:
-            zs[m] = {"latents": zs[filled[0]]["latents"], "masks": x[m]["masks"]}
-        zs = {m: zs[m] for m in self.vaes}                     # modality order, as the reference's dict
+        (`data` None, masks kept: models/trainer.py:179-215): a missing modality is decoded from the sample it borrowed
+        under its own masks; every target's cross entry is a fresh one-entry dict, so the last source in dict order wins
+        (:109-114)."""
+        qz, zs = self._sample(x, K)
+        zs = {m: {"latents": z, "masks": x[m]["masks"]} for m, z in zs}      # modality order, as the reference's dict
+        px, cross = {}, {}
         for m, vae in self.vaes.items():
             px[m] = normal(*vae.dec({"latents": zs[m]["latents"], "masks": x[m]["masks"]}))
         for src, z in zs.items():
@@ -801,10 +752,6 @@ class DMVAE(TorchMMVAE):
         pmax = max(v.private_latents for v in self.vaes.values())
         self.register_buffer("_theta0", torch.zeros(1, pmax), persistent=False)    # N(0,1) prior of the private part
 
-    @property
-    def pz_params(self):
-        return self._pz_params[0], F.softmax(self._pz_params[1], dim=1) * self._pz_params[1].size(-1)
-
     batch_passes = True      # a decoder's own + joint + cross passes in one call (objective)
 
     def objective(self, mods):
@@ -813,20 +760,11 @@ class DMVAE(TorchMMVAE):
         M, D = len(names), self.n_latents
         beta = float(self.obj_fn.beta)
         theta = self._pz_params[1]
-        dev = next(v["data"] for v in mods.values() if v["data"] is not None).device
         # Round 4: towers on two streams (as MOE.objective), and a decoder's passes -- own, joint, cross (one per other
         # modality) -- as ONE call over (2 + (M - 1)) B latent samples (the row-sum kernels pair output row k with target
         # row k % B; a decoder with dropout draws its masks once for all passes; optimal_sigma fits one sigma per call:
         # its passes stay apart).  BASELINE configs[3]: 1.54 -> 1.2 ms/step.
-        streams = self._tower_streams(dev)
-        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        real = [cur if st is None else st for st in streams]
-        self._fork(streams, dev, mods)
-        packed = [None] * M
-        for i, (n, st) in enumerate(zip(names, streams)):
-            with torch.cuda.stream(st):
-                packed[i] = packed_head(*self.vaes[n].enc(mods[n]))
-        self._join(streams, dev)
+        packed, streams, cur, real, dev = self._encode_towers(mods)
         B = packed[0].shape[0]
         P = [self.vaes[n].private_latents for n in names]
         # noise in the reference's draw order (mmvae_models.py:486-502)
@@ -953,65 +891,57 @@ class DMVAE(TorchMMVAE):
     def modality_mixing(self, mods):
         return self.encode(mods)
 
-    def _latents_of(self, x, of):
-        """forward()'s shared code of modality `of` (its own shared posterior, or the first present modality's), with the
-        draws before it consumed in forward()'s order: joint, then per modality shared, private, one per other present"""
+    def _sample(self, x, K=1, of=None):
+        """mmvae_models.py:467-503, missing modalities (`data` None, masks kept) included: the joint is the product of
+        the PRESENT shared experts; a missing modality samples its shared code from the first present modality's
+        posterior and its private code from N(0, I) (:489-493); cross reconstructions from a fresh shared draw of every
+        other present modality (:499-502).  Draws in the reference's order: z_joint, then per modality z_shared,
+        z_private and, as they are read, one (source, z) per other present modality.
+        -> ((posteriors of encode(), joint (mu, variance), z_joint), (modality, z_shared, z_private, cross draws))"""
+        if K != 1:
+            raise NotImplementedError("dmvae.forward: K = 1 only on this path")
         _, filled = self.get_missing_modalities(x)
-        D = self.n_latents
-        src = of if of in filled else filled[0]
-        mu, lv = self.vaes[src].enc(x[src])
-        mu, lv = mu[:, :D], lv[:, :D]
-        B, dev = mu.shape[0], mu.device
-        self._draw(B, D, dev)                                     # z_joint
-        for n, vae in self.vaes.items():
-            e = self._draw(B, D, dev).unsqueeze(0)                # z_shared
-            if n == of:
-                return mu + lv * e
-            self._draw(B, vae.private_latents, dev)               # z_private
-            for m in filled:
-                if m != n:
-                    self._draw(B, D, dev)                         # cross reconstruction
+        assert len(filled) > 0, "at least one modality must be present for forward call"
+        D, first = self.n_latents, x[filled[0]]["data"]
+        src = {n: (n if n in filled else filled[0]) for n in self.vaes}
+        if of is None:
+            enc_d = self.encode(x)
+            joint = self.product_of_experts([enc_d[n]["shared"][0] for n in filled],
+                                            [enc_d[n]["shared"][1] for n in filled])
+        else:      # (latents_for: only the tower `of` samples from is run, the joint's draw is taken without its product)
+            enc_d, joint = self.encode(self._given_only(x, [src[of]])), None
+
+        def draw(post, d):      # a posterior that was not encoded (or does not exist: a missing private code) gives N(0, I)
+            e = self._draw(first.shape[0], d, first.device).unsqueeze(0)
+            return e if post is None else post[0] + post[1] * e
+
+        def per_modality():
+            for n, vae in self.vaes.items():
+                z_shared = draw(enc_d[src[n]]["shared"], D)
+                if n == of:      # (latents_for stops here: the evaluation generator moves no further than this draw)
+                    yield n, z_shared
+                    return
+                z_private = draw(enc_d[n]["private"], vae.private_latents)
+                cross = ((m, draw(enc_d[m]["shared"], D)) for m in filled if m != n)
+                yield n, z_shared, z_private, cross
+                for _ in cross:      # (latents_for: the cross draws nobody decoded are taken all the same)
+                    pass
+        return (enc_d, joint, draw(joint, D)), per_modality()
 
     def forward(self, x, K=1):
         """mmvae_models.py:467-503: the container the evaluation code reads (shared / private posteriors, joint
-        posterior, own / joint / cross reconstructions), missing modalities (`data` None, masks kept) included: the
-        joint is the product of the PRESENT shared experts; a missing modality samples its shared code from the first
-        present modality's posterior and its private code from N(0, I) (:489-493); cross reconstructions from a fresh
-        shared draw of every other present modality (:499-502).  Noise in the reference's draw order.
-        (`_latents_of` above restates the draws of this method in order: keep them in step.)"""
-        if K != 1:
-            raise NotImplementedError("dmvae.forward: K = 1 only on this path")
-        missing, filled = self.get_missing_modalities(x)
-        assert len(filled) > 0, "at least one modality must be present for forward call"
-        D = self.n_latents
-        enc_d = self.encode(x)
-        mu_j, var_j = self.product_of_experts([enc_d[n]["shared"][0] for n in filled],
-                                              [enc_d[n]["shared"][1] for n in filled])
-        B, dev = mu_j.shape[0], mu_j.device
-        draw = lambda d: self._draw(B, d, dev).unsqueeze(0)
-        joint_d = normal(mu_j, var_j)
-        z_joint = mu_j + var_j * draw(D)
+        posterior, own / joint / cross reconstructions); every reconstruction is decoded right behind its draw."""
+        (enc_d, joint, z_joint), zs = self._sample(x, K)
+        joint_d = normal(*joint)
         joint_dist, qz_xs, qz_private, zss, px_zs, joint_px_zs, cross_px_zs = {}, {}, {}, {}, {}, {}, {}
-        for n, vae in self.vaes.items():
-            present = n in filled
+        for n, z_shared, z_private, cross in zs:
+            vae, masks = self.vaes[n], x[n]["masks"]
             joint_dist[n] = joint_d
-            qz_xs[n] = normal(*enc_d[n]["shared"]) if present else None
-            qz_private[n] = normal(*enc_d[n]["private"]) if present else None
-            s_mu, s_lv = enc_d[n if present else filled[0]]["shared"]
-            z_shared = s_mu + s_lv * draw(D)
-            if present:
-                p_mu, p_lv = enc_d[n]["private"]
-                z_private = p_mu + p_lv * draw(vae.private_latents)
-            else:
-                z_private = draw(vae.private_latents)
-            masks = x[n]["masks"]
+            qz_xs[n] = normal(*enc_d[n]["shared"]) if enc_d[n]["shared"] is not None else None
+            qz_private[n] = normal(*enc_d[n]["private"]) if enc_d[n]["private"] is not None else None
             dec = lambda z: self._px(vae, *vae.dec({"latents": torch.cat([z, z_private], -1), "masks": masks}))
             zss[n] = {"latents": z_shared, "masks": masks}
             px_zs[n] = dec(z_shared)
             joint_px_zs[n] = dec(z_joint)
-            cross_px_zs[n] = {}
-            for m in filled:
-                if m != n:
-                    c_mu, c_lv = enc_d[m]["shared"]
-                    cross_px_zs[n][m] = dec(c_mu + c_lv * draw(D))
+            cross_px_zs[n] = {m: dec(z) for m, z in cross}
         return self.make_output_dict(qz_xs, px_zs, zss, joint_dist, qz_private, None, joint_px_zs, cross_px_zs)

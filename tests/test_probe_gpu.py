@@ -387,6 +387,83 @@ def test_latents_for_equals_forward_bit_for_bit(hip_lib, mixing):
         assert not a.requires_grad and bool(torch.isfinite(a).all())
 
 
+def _forward_recording_draws(model, x, K=1):
+    """forward(x, K) -> (its output, the (B, d) shapes it asked `_draw` for, in order)"""
+    shapes, orig = [], model._draw
+
+    def rec(b, d, dev):
+        shapes.append((b, d))
+        return orig(b, d, dev)
+    model._draw = rec
+    try:
+        with torch.no_grad():
+            out = model.forward(x, K=K)
+    finally:
+        del model._draw
+    return out, shapes
+
+
+# the reference's draw order (models/mmvae_models.py: poe :189-208, mopoe :351-370, moe :80-117, dmvae :467-503) for the two
+# modalities of `_model`, keyed by which of them carry data.  S = a latent-wide draw (B, D), P = a private one (B, 4).
+# dmvae: z_joint, then per modality z_shared, z_private and a fresh shared draw of every OTHER PRESENT modality.
+_S, _P = (5, 16), (5, 4)
+REFERENCE_DRAWS = {
+    "poe": {"0": [_S], "1": [_S], "01": [_S]},
+    "mopoe": {"0": [_S, _S], "1": [_S, _S], "01": [_S, _S]},
+    "moe": {"0": [_S], "1": [_S], "01": [_S, _S]},
+    "dmvae": {"0": [_S, _S, _P, _S, _P, _S], "1": [_S, _S, _P, _S, _S, _P], "01": [_S, _S, _P, _S, _S, _P, _S]},
+}
+
+
+@pytest.mark.parametrize("mixing", ["poe", "moe", "mopoe", "dmvae"])
+def test_forward_draw_order_is_the_references(hip_lib, mixing):
+    tr, batch = _model(mixing)
+    model = tr.model
+    names = list(model.vaes.keys())
+    assert len(names) == 2 and model.n_latents == 16
+    for key, want in REFERENCE_DRAWS[mixing].items():
+        x = model._given_only(batch, [names[int(c)] for c in key])
+        _, got = _forward_recording_draws(model, x)
+        print(f"{mixing} given {key}: {got}")
+        assert got == want, f"{mixing} given {key}: {got} != {want}"
+        if mixing != "dmvae":      # K = 2: every entry twice in a row
+            _, got = _forward_recording_draws(model, x, K=2)
+            print(f"{mixing} given {key} K = 2: {got}")
+            assert got == [s for s in want for _ in range(2)], f"{mixing} given {key} K = 2: {got}"
+
+
+@pytest.mark.parametrize("mixing", ["poe", "moe", "mopoe", "dmvae"])
+def test_forward_k2_slices_equal_k1_forward_on_the_same_draws(hip_lib, mixing):
+    tr, batch = _model(mixing)
+    model = tr.model
+    names = list(model.vaes.keys())
+    B, D = 5, model.n_latents
+    if mixing == "dmvae":
+        with pytest.raises(NotImplementedError):
+            model.forward(batch, K=2)
+        return
+    for given in [[n] for n in names] + [names]:
+        x = model._given_only(batch, given)
+        _, shapes = _forward_recording_draws(model, x, K=2)
+        g = torch.Generator().manual_seed(len(given) + 11)
+        eps = [torch.randn(1, b, d, generator=g) for b, d in shapes]      # draws 2 i, 2 i + 1: k = 0, 1 of the i-th block
+        model.eps_override = [e.clone() for e in eps]
+        with torch.no_grad():
+            out2 = model.forward(x, K=2)
+        assert model.eps_override == []
+        for k in range(2):
+            model.eps_override = [e.clone() for e in eps[k::2]]
+            with torch.no_grad():
+                out1 = model.forward(x)
+            assert model.eps_override == []
+            for of in names:
+                z2 = out2.mods[of].latent_samples["latents"]
+                z1 = out1.mods[of].latent_samples["latents"]
+                assert z2.shape == (2, B, D) and z1.shape == (1, B, D), (z2.shape, z1.shape)
+                assert torch.equal(z2[k], z1[0]), f"{mixing} given={given} of={of} k={k}"
+        model.eps_override = None
+
+
 # ---------------------------------------------------------------------------------------------
 # 8. no footprint on training
 # ---------------------------------------------------------------------------------------------
