@@ -826,6 +826,38 @@ int mmvae_probe_eval(const float* state, const float* z, const int* labels, cons
                      int P, int S, int A, int N, int D, int Cmax, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Generation coherence (TorchMMVAE.cross_coherence / joint_coherence; csrc/coherence.hip): the scoring kernels of the
+ * reference's eval/eval_cdsprites.py.  Forward only: no autograd.
+ * mmvae_text_decode_score: logits (N,T,V) fp32 as Dec_TxtTransformer returns it (rows at padding all zero);
+ *   pred (N,T) int32 = the index of the first maximum over V (torch.argmax on finite input; an all-zero row gives 0, the
+ *   space of the alphabet);  with target_ids (N,T) int32 and lengths (N) int32:
+ *   letters[n] = #{t < min(lengths[n], T) : pred[n,t] == target_ids[n,t]} (count_same_letters after its truncation to
+ *   the shorter string; a negative length counts as 0).  target_ids NULL: only pred is written.
+ *   1 <= T <= MMVAE_COH_MAX_STEPS, 2 <= V <= MMVAE_COH_MAX_VOCAB, else MMVAE_ERR_UNSUPPORTED.
+ * mmvae_cls_head: the heads of A attribute classifiers (eval/train_classifiers.py: CNN) in one launch.
+ *   feats (A,N,512): the fourth conv's output BEFORE its ReLU, flattened (channel, y, x);  W1 (A,256,512), b1 (A,256),
+ *   W2 (A,Cmax,256), b2 (A,Cmax);  n_classes: HOST pointer to A ints.  Per classifier a:
+ *     h = relu(relu(feats_a) W1_a^T + b1_a);  logits = h W2_a^T + b2_a over the first n_classes[a] classes;
+ *     pred (A,N) int32 = the first maximum;  logits (A,N,Cmax) (may be NULL; columns >= n_classes[a] are written 0);
+ *   with labels (A,N) int32: correct (A,N) uint8 = (labels >= 0 && pred == labels) -- a label of -1 ("the text names no
+ *   value") is never correct -- and n_correct (N) int32 = sum_a correct[a,n] (zeroed on the stream, then integer
+ *   atomics).  labels NULL: correct / n_correct are not touched.  Plain fp32 FMA accumulation in a fixed order; the
+ *   hidden vector never leaves the registers.
+ *   A <= MMVAE_COH_MAX_CLASSIFIERS, 2 <= n_classes[a] <= Cmax <= MMVAE_COH_MAX_CLASSES, else MMVAE_ERR_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_COH_MAX_STEPS 256
+#define MMVAE_COH_MAX_VOCAB 256
+#define MMVAE_COH_MAX_CLASSIFIERS 8
+#define MMVAE_COH_MAX_CLASSES 8
+#define MMVAE_COH_FEATS 512
+#define MMVAE_COH_HIDDEN 256
+int mmvae_text_decode_score(const float* logits, const int* target_ids, const int* lengths, int* pred, int* letters,
+                            int N, int T, int V, mmvae_stream_t stream);
+int mmvae_cls_head(const float* feats, const float* W1, const float* b1, const float* W2, const float* b2,
+                   const int* n_classes, const int* labels, int* pred, float* logits, unsigned char* correct,
+                   int* n_correct, int A, int N, int Cmax, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

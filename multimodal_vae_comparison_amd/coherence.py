@@ -1,0 +1,268 @@
+"""Generation coherence of the CdSprites+ benchmark (reference: eval/eval_cdsprites.py, eval/train_classifiers.py).
+
+Three parts:
+  * the caption semantics, restated on token ids / strings on the host (which attribute value a caption names, which
+    one a decoded caption spells at the word position its level prescribes, the letter count);
+  * AttributeClassifier / AttributeClassifiers: the reference's image classifiers (one CNN per attribute) on the
+    k4-s2 conv kernels, their heads in one ops.cls_head launch;
+  * the scoring helpers TorchMMVAE.cross_coherence / joint_coherence are built from.
+"""
+import torch
+import torch.nn as nn
+
+from . import hipops as H
+from . import ops
+
+ALPHABET = " abcdefghijklmnopqrstuvwxyz"
+
+# attributes a caption of each level names, in caption order
+LEVEL_ATTRIBUTES = {1: ("shape",), 2: ("size", "shape"), 3: ("size", "color", "shape"),
+                    4: ("size", "color", "shape", "position"),
+                    5: ("size", "color", "shape", "position", "background")}
+# the values a caption is searched for, in search order (the first one found wins: "white" before "red", ...)
+SEARCH_ORDER = {"shape": ("heart", "ellipse", "square"),
+                "size": ("small", "big"),
+                "color": ("white", "red", "yellow", "green", "blue", "pink"),
+                "background": ("on light", "on dark"),
+                "position": ("at top left", "at top right", "at bottom right", "at bottom left")}
+# class index -> value of the image classifiers (the order they were trained with)
+CLASS_NAMES = {"shape": ("square", "ellipse", "heart"),
+               "size": ("big", "small"),
+               "color": ("blue", "green", "red", "yellow", "pink"),
+               "position": ("at top left", "at top right", "at bottom left", "at bottom right"),
+               "background": ("on light", "on dark")}
+# where a decoded caption is read for an attribute: one word index per level, or a run of words joined by spaces
+_WORD_OF = {"size": {1: 0, 2: 0, 3: 0, 4: 0, 5: 0}, "shape": {1: 0, 2: 1, 3: 2, 4: 2, 5: 2}, "color": {3: 1, 4: 1, 5: 1}}
+_WORDS_OF = {"background": (-2, -1), "position": (3, 4, 5, 6)}
+UNKNOWN = "Unknown"
+
+
+def _level_attributes(level):
+    if level not in LEVEL_ATTRIBUTES:
+        raise ValueError(f"coherence: level {level!r} (the CdSprites+ levels are 1 .. 5)")
+    return LEVEL_ATTRIBUTES[level]
+
+
+def ids_to_text(ids, length=None):
+    """token ids -> string over ALPHABET (id 0 is the space); `length`: keep the first `length` symbols"""
+    ids = [int(i) for i in ids]
+    if length is not None:
+        ids = ids[:max(int(length), 0)]
+    return "".join(ALPHABET[i] for i in ids)
+
+
+def text_to_ids(text, T=None):
+    """string -> ids (a symbol outside ALPHABET becomes 0, as an all-zero one-hot row decodes), padded with 0 to T"""
+    ids = [max(ALPHABET.find(ch), 0) for ch in text.lower()]
+    if T is not None:
+        ids = (ids + [0] * T)[:T]
+    return ids
+
+
+def _first_contained(values, text):
+    """the first of `values` (in their order) that occurs in `text` as a SUBSTRING, lower-cased; None if none does"""
+    text = text.lower()
+    for v in values:
+        if v.lower() in text:
+            return v.lower()
+    return None
+
+
+def attribute_in_caption(attribute, caption):
+    """the value of `attribute` a ground-truth caption names: a substring search over the whole caption"""
+    return _first_contained(SEARCH_ORDER[attribute], caption)
+
+
+def attribute_in_decoded(attribute, text, level):
+    """the value of `attribute` a DECODED caption spells at the place its level prescribes: size = word 0, color = word 1,
+    shape = word 0 / 1 / 2 by level, position = words 3 .. 6, background = the last two words (words: split at single
+    spaces, so a double space makes an empty word).  A caption too short for the place gives None."""
+    words = text.split(" ")
+    try:
+        if attribute in _WORDS_OF:
+            part = " ".join([words[i] for i in _WORDS_OF[attribute]])
+        else:
+            part = words[_WORD_OF[attribute][level]]
+    except IndexError:
+        return None
+    return _first_contained(SEARCH_ORDER[attribute], part)
+
+
+def retrieve_attributes(text, level):
+    """the attribute values of a decoded caption joined by spaces, UNKNOWN where none is spelled (joint coherence)"""
+    vals = [attribute_in_decoded(a, text, level) for a in _level_attributes(level)]
+    return " ".join(UNKNOWN if v is None else v for v in vals)
+
+
+def count_same_letters(a, b):
+    """positions at which two strings agree, over the length of the shorter one"""
+    return sum(1 for x, y in zip(a, b) if x == y)
+
+
+def score_decoded_text(level, caption, decoded):
+    """Image -> Text: (strict, features, letters) of one decoded caption against its ground truth.
+    features: share of the level's attributes whose decoded value occurs in the caption (substring);
+    letters: matching positions / len(caption);  strict: 1 iff letters == 1 (NOT "all attributes")."""
+    atts = _level_attributes(level)
+    ok = 0
+    for a in atts:
+        v = attribute_in_decoded(a, decoded, level)
+        ok += int(v is not None and v in caption)
+    letters = count_same_letters(decoded, caption) / len(caption) if len(caption) else 0.0
+    return (1 if letters == 1 else 0), ok / len(atts), letters
+
+
+def caption_labels(level, caption):
+    """Text -> Image: the class index per attribute of the level that the caption asks for; -1 where the caption names no
+    value, or one no classifier has a class for ("white")"""
+    out = []
+    for a in _level_attributes(level):
+        v = attribute_in_caption(a, caption)
+        out.append(CLASS_NAMES[a].index(v) if v in CLASS_NAMES[a] else -1)
+    return out
+
+
+def mean_stats(lists, percentage=True):
+    """the means of several per-sample lists, as percentages"""
+    return [(100.0 if percentage else 1.0) * sum(l) / len(l) for l in lists]
+
+
+# ---- image classifiers ----------------------------------------------------------------------------------------------
+class _Wrapped(nn.Module):
+    """a layer under the key `<name>.module.*` (the reference wraps every layer in DataParallel)"""
+
+    def __init__(self, module):
+        super().__init__()
+        self.module = module
+
+
+class AttributeClassifier(nn.Module):
+    """eval/train_classifiers.py: CNN -- four Conv2d(k4, s2, p1) 3->32->32->32->32 with ReLU, Linear 512->256 + ReLU,
+    Linear 256->n_classes, under the reference's state-dict keys (conv1 / conv2 / conv3 / conv_64 / lin1 / lin2 /
+    fc, each `.module.weight|bias`; lin2 is carried and unused, as there), so its shipped classifier files load with
+    strict=True.  Inference only: the trunk runs on ops.conv2d (the ReLU of layer l applied by layer l + 1 while it
+    stages its input), the head on ops.cls_head."""
+
+    def __init__(self, n_classes):
+        super().__init__()
+        n_classes = int(n_classes)
+        if not 2 <= n_classes <= H.COH_MAX_CLASSES:
+            raise ValueError(f"AttributeClassifier: {n_classes} classes (2 .. {H.COH_MAX_CLASSES} are on the MI355X path)")
+        self.n_classes = n_classes
+        conv = lambda cin: _Wrapped(nn.Conv2d(cin, 32, 4, stride=2, padding=1))
+        self.conv1, self.conv2, self.conv3, self.conv_64 = conv(3), conv(32), conv(32), conv(32)
+        self.lin1 = _Wrapped(nn.Linear(H.COH_FEATS, H.COH_HIDDEN))
+        self.lin2 = _Wrapped(nn.Linear(H.COH_HIDDEN, H.COH_HIDDEN))
+        self.fc = _Wrapped(nn.Linear(H.COH_HIDDEN, n_classes))
+        self.requires_grad_(False)
+
+    def trunk(self, x):
+        """x (N,3,64,64) -> (N,512): the fourth conv's output before its ReLU, flattened (channel, y, x)"""
+        with torch.no_grad():
+            act = H.ACT_NONE
+            for layer in (self.conv1, self.conv2, self.conv3, self.conv_64):
+                x = ops.conv2d(x, layer.module.weight, layer.module.bias, 2, 1, act)
+                act = H.ACT_RELU
+            return x.reshape(x.shape[0], -1)
+
+    def forward(self, x):
+        """logits (N, n_classes) of images x (N,3,64,64) in [0, 1]"""
+        return AttributeClassifiers({"_": self}).predict(x, quantise=False, want_logits=True)["logits"][0]
+
+
+def quantise_images(x_hat):
+    """a decoder output in [0, 1] as the reference's pipeline hands it to the classifiers: x 255, cast to uint8
+    (truncation), / 255 -- floor(255 x) / 255 in fp32 -- and reinterpreted (not permuted) as (N,3,64,64)"""
+    x = torch.floor(x_hat.detach().float() * 255.0).clamp_(0.0, 255.0) / 255.0
+    return x.reshape(-1, 3, 64, 64)
+
+
+class AttributeClassifiers(nn.Module):
+    """{attribute: AttributeClassifier}, scored together: A trunks, ONE head launch"""
+
+    def __init__(self, classifiers):
+        super().__init__()
+        if not classifiers or len(classifiers) > H.COH_MAX_CLASSIFIERS:
+            raise ValueError(f"AttributeClassifiers: {len(classifiers)} classifiers (1 .. {H.COH_MAX_CLASSIFIERS} per launch)")
+        for k, c in classifiers.items():
+            if not isinstance(c, AttributeClassifier):
+                raise TypeError(f"AttributeClassifiers: {k!r} is a {type(c).__name__}, not an AttributeClassifier")
+        self.nets = nn.ModuleDict(classifiers)
+        self._packed = None
+
+    @classmethod
+    def for_level(cls, level):
+        """untrained classifiers of a level's attributes with the reference's class counts (load their state dicts)"""
+        return cls({a: AttributeClassifier(len(CLASS_NAMES[a])) for a in _level_attributes(level)})
+
+    @property
+    def attributes(self):
+        return list(self.nets.keys())
+
+    @property
+    def n_classes(self):
+        return [c.n_classes for c in self.nets.values()]
+
+    def packed_head(self):
+        """(W1 (A,256,512), b1 (A,256), W2 (A,Cmax,256), b2 (A,Cmax)); packed again whenever a head parameter was
+        replaced, moved or written in place"""
+        nets = list(self.nets.values())
+        src = [p for n in nets for p in (n.lin1.module.weight, n.lin1.module.bias, n.fc.module.weight, n.fc.module.bias)]
+        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in src)
+        if self._packed is None or self._packed[0] != key:
+            Cmax = max(self.n_classes)
+            dev = src[0].device
+            W2 = torch.zeros(len(nets), Cmax, H.COH_HIDDEN, device=dev)
+            b2 = torch.zeros(len(nets), Cmax, device=dev)
+            for i, n in enumerate(nets):
+                W2[i, :n.n_classes] = n.fc.module.weight.detach().float()
+                b2[i, :n.n_classes] = n.fc.module.bias.detach().float()
+            self._packed = (key, (torch.stack([n.lin1.module.weight.detach().float() for n in nets]).contiguous(),
+                                  torch.stack([n.lin1.module.bias.detach().float() for n in nets]).contiguous(), W2, b2))
+        return self._packed[1]
+
+    def predict(self, x_hat, labels=None, quantise=True, want_logits=False):
+        """x_hat: decoder output, any shape that reshapes to (N,3,64,64), in [0, 1]; labels (A,N) ints or None (-1: never
+        correct).  -> ops.cls_head's dict: pred (A,N), logits (A,N,Cmax) | None, correct (A,N), n_correct (N,)"""
+        x = quantise_images(x_hat) if quantise else x_hat.detach().float().reshape(-1, 3, 64, 64)
+        x = x.contiguous()
+        feats = torch.stack([n.trunk(x) for n in self.nets.values()]).contiguous()
+        if labels is not None:
+            labels = torch.as_tensor(labels).to(device=x.device, dtype=torch.int32).contiguous()
+            if labels.shape != (len(self.nets), x.shape[0]):
+                raise ValueError(f"AttributeClassifiers.predict: labels {tuple(labels.shape)} for {len(self.nets)} "
+                                 f"classifiers and {x.shape[0]} images")
+        return ops.cls_head(feats, *self.packed_head(), self.n_classes, labels=labels, want_logits=want_logits)
+
+    def names(self, pred):
+        """pred (A,N) -> per image the list of class names, in attribute order"""
+        pred = pred.cpu().tolist()
+        atts = self.attributes
+        return [[CLASS_NAMES[a][pred[i][n]] for i, a in enumerate(atts)] for n in range(len(pred[0]))]
+
+
+def check_classifiers(classifiers, level):
+    """the level's attributes, each with a classifier of the benchmark's class count -> the classifiers in level order"""
+    atts = _level_attributes(level)
+    if not isinstance(classifiers, AttributeClassifiers):
+        raise TypeError("coherence: `classifiers` must be an AttributeClassifiers")
+    missing = [a for a in atts if a not in classifiers.nets]
+    if missing:
+        raise ValueError(f"coherence: level {level} needs classifiers for {list(atts)}; {missing} are missing")
+    for a in atts:
+        if classifiers.nets[a].n_classes != len(CLASS_NAMES[a]):
+            raise ValueError(f"coherence: the {a} classifier has {classifiers.nets[a].n_classes} classes, the benchmark "
+                             f"{len(CLASS_NAMES[a])}")
+    if classifiers.attributes == list(atts):
+        return classifiers
+    return AttributeClassifiers({a: classifiers.nets[a] for a in atts})
+
+
+def score_images(classifiers, level, x_hat, captions):
+    """Text -> Image / joint: classify the decoded images against what the captions name.
+    -> (strict (N,) 0/1 list, features (N,) list of fractions, the cls_head dict)"""
+    atts = _level_attributes(level)
+    labels = torch.tensor([caption_labels(level, c) for c in captions], dtype=torch.int32).t().contiguous()
+    out = classifiers.predict(x_hat, labels=labels)
+    n_ok = out["n_correct"].cpu().tolist()
+    return [int(k == len(atts)) for k in n_ok], [k / len(atts) for k in n_ok], out

@@ -72,6 +72,7 @@ MIX_MAX_COMPONENTS = 8
 
 
 PROBE_MAX_CLASSES, PROBE_MAX_PROBES = 32, 64
+COH_MAX_STEPS, COH_MAX_VOCAB, COH_MAX_CLASSIFIERS, COH_MAX_CLASSES, COH_FEATS, COH_HIDDEN = 256, 256, 8, 8, 512, 256
 
 
 class LmeRows(ctypes.Structure):
@@ -285,6 +286,8 @@ SIGNATURES = {
     "mmvae_probe_train": (c_i, [c_p] * 4 + [c_i, ctypes.POINTER(c_i), c_p] + [c_i] * 7 + [c_l, c_i, c_f, c_p]),
     "mmvae_probe_tile_rows": (c_i, [c_i]),
     "mmvae_probe_eval": (c_i, [c_p] * 3 + [ctypes.POINTER(c_i), c_p, c_p] + [c_i] * 6 + [c_p]),
+    "mmvae_text_decode_score": (c_i, [c_p] * 5 + [c_i] * 3 + [c_p]),
+    "mmvae_cls_head": (c_i, [c_p] * 5 + [ctypes.POINTER(c_i)] + [c_p] * 5 + [c_i] * 3 + [c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

@@ -484,6 +484,136 @@ class TorchMMVAE(nn.Module):
             out["pred"][k] = pred[p]
         return out
 
+    # ---- generation coherence ------------------------------------------------------------------
+    def _image_text(self, image, text):
+        """names of the image and the text modality: as given, else the modality with 64 x 64 x 3 data and the other one"""
+        names = list(self.vaes.keys())
+        if image is None or text is None:
+            is_img = [m for m in names if tuple(self.vaes[m].data_dim) in ((64, 64, 3), (3, 64, 64))]
+            if len(names) != 2 or len(is_img) != 1:
+                raise ValueError(f"coherence: name the `image` and the `text` modality (this model has {names})")
+            image = is_img[0] if image is None else image
+            text = [m for m in names if m != is_img[0]][0] if text is None else text
+        if image not in names or text not in names or image == text:
+            raise ValueError(f"coherence: image = {image!r}, text = {text!r} are not two modalities of this model ({names})")
+        return image, text
+
+    def _coherence_guard(self, what):
+        if self.training:
+            raise RuntimeError(f"{what} needs eval mode (model.eval()): dropout would make the generations a function of "
+                               f"the masks")
+
+    def cross_coherence(self, batches, classifiers, level, image=None, text=None, eps=None):
+        """Cross-generation coherence of the CdSprites+ benchmark (eval/eval_cdsprites.py: calculate_cross_coherency).
+        `batches`: an iterable of batch dicts holding the image and the one-hot text modality; the captions are read from
+        the batches themselves (argmax of the one-hot rows over the mask's length).  `classifiers`: a
+        coherence.AttributeClassifiers with one classifier per attribute of `level` (1 .. 5).  Per batch two forward()
+        calls: only the text given (the decoded image is quantised to 8 bits and classified: does it show what the
+        caption names?) and only the image given, text masks None so that the caption decodes at full length (its
+        argmax string is compared with the caption letter by letter and attribute by attribute).
+        -> {"text_image": [strict %, features %], "image_text": [strict %, features %, letters %], "per_sample": {...},
+            "captions": [...], "decoded": [...]}; Image->Text strict means "every letter right", as in the reference.
+        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
+        tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
+        dropout counters, gradients and the optimiser stay as they are."""
+        from .. import coherence as coh
+        self._coherence_guard("cross_coherence")
+        classifiers = coh.check_classifiers(classifiers, level)
+        image, text = self._image_text(image, text)
+        per = {"text_image_strict": [], "text_image_features": [], "image_text_strict": [], "image_text_features": [],
+               "image_text_letters": []}
+        captions, decoded = [], []
+        saved = self.eps_override
+        self.eps_override = None if eps is None else [e for e in eps]
+        self._eval_draws = True
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    if any(m not in batch or batch[m]["data"] is None for m in (image, text)):
+                        raise ValueError("cross_coherence: every batch must hold the image and the text modality")
+                    onehot, masks = batch[text]["data"], batch[text]["masks"]
+                    if onehot.dim() != 3:
+                        raise ValueError(f"cross_coherence: the text modality must be one-hot (B,T,V), got "
+                                         f"{tuple(onehot.shape)}")
+                    B, T, V = onehot.shape
+                    if V > len(coh.ALPHABET):
+                        raise ValueError(f"cross_coherence: {V} symbols, the captions' alphabet has {len(coh.ALPHABET)}")
+                    onehot = onehot.float().contiguous()
+                    ids, _ = ops.text_decode_score(onehot)
+                    lens = (torch.full((B,), T, dtype=torch.int32, device=onehot.device) if masks is None
+                            else torch.count_nonzero(masks.reshape(B, T), dim=-1).to(torch.int32))
+                    caps = [coh.ids_to_text(i, l) for i, l in zip(ids.cpu().tolist(), lens.cpu().tolist())]
+                    # text -> image
+                    out = self.forward(self._given_only(batch, [text]))
+                    x_hat = out.mods[image].decoder_dist.loc
+                    strict, feats, _ = coh.score_images(classifiers, level, x_hat, caps)
+                    per["text_image_strict"] += strict
+                    per["text_image_features"] += feats
+                    # image -> text, decoded at full length
+                    x = self._given_only(batch, [image])
+                    x[text] = dict(x[text], masks=None)
+                    logits = self.forward(x).mods[text].decoder_dist.loc
+                    logits = logits.reshape(-1, *logits.shape[-2:])[:B].float().contiguous()
+                    Td = logits.shape[1]
+                    tgt = ids[:, :Td] if Td <= T else torch.nn.functional.pad(ids, (0, Td - T))
+                    pred, letters = ops.text_decode_score(logits, tgt.contiguous(), lens.contiguous())
+                    pred, letters, lens_h = pred.cpu().tolist(), letters.cpu().tolist(), lens.cpu().tolist()
+                    for n in range(B):
+                        dec = coh.ids_to_text(pred[n])
+                        _, f, _ = coh.score_decoded_text(level, caps[n], dec)
+                        per["image_text_strict"].append(int(lens_h[n] > 0 and letters[n] == lens_h[n]))
+                        per["image_text_features"].append(f)
+                        per["image_text_letters"].append(letters[n] / lens_h[n] if lens_h[n] else 0.0)
+                        decoded.append(dec)
+                    captions += caps
+        finally:
+            self._eval_draws = False
+            self.eps_override = saved
+        if not captions:
+            raise ValueError("cross_coherence: `batches` is empty")
+        return {"text_image": coh.mean_stats([per["text_image_strict"], per["text_image_features"]]),
+                "image_text": coh.mean_stats([per["image_text_strict"], per["image_text_features"],
+                                              per["image_text_letters"]]),
+                "per_sample": per, "captions": captions, "decoded": decoded}
+
+    def joint_coherence(self, classifiers, level, n=64, image=None, text=None, eps=None):
+        """Joint-generation coherence (eval/eval_cdsprites.py: calculate_joint_coherency): n latents z ~ p(z) =
+        Normal(*pz_params), both modalities decoded from the SAME z (text at full length), the attributes read from the
+        decoded caption at their word positions ("Unknown" never matches) and compared with what the classifiers see in
+        the decoded image.  (The reference draws every modality's latents on its own, from that VAE's N(0, I) --
+        vae.generate_samples once per modality in trainer.save_joint_samples --, so that its image and caption do not
+        share a sample; the metric's definition, one prior sample for both, is what is computed here.)
+        -> {"joint": [strict %, features %], "per_sample": {...}, "decoded": [...], "attributes": [...]}.
+        Needs eval mode; runs without gradients; the draw comes from the evaluation generator, or is `eps` (n, D).
+        Models with private latents (DMVAE) have no joint prior sample to decode: NotImplementedError."""
+        from .. import coherence as coh
+        self._coherence_guard("joint_coherence")
+        if self.latent_factorization:
+            raise NotImplementedError(f"{self.modelName}: joint_coherence is built for the mixers with one shared latent "
+                                      f"space (poe, moe, mopoe); private latents have no joint prior sample")
+        classifiers = coh.check_classifiers(classifiers, level)
+        image, text = self._image_text(image, text)
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"joint_coherence: n = {n}")
+        with torch.no_grad():
+            loc, scale = self.pz_params
+            D = self.n_latents
+            if eps is None:
+                e = ops.randn((n, D), self._eval_rng_state)
+            else:
+                e = eps.to(device=loc.device, dtype=torch.float32).reshape(n, D)
+            z = (loc + scale * e).unsqueeze(0).contiguous()
+            x_hat = self.vaes[image].dec({"latents": z, "masks": None})[0]
+            logits = self.vaes[text].dec({"latents": z, "masks": None})[0]
+            logits = logits.reshape(-1, *logits.shape[-2:]).float().contiguous()
+            pred, _ = ops.text_decode_score(logits)
+            decoded = [coh.ids_to_text(p) for p in pred.cpu().tolist()]
+            atts = [coh.retrieve_attributes(t, level) for t in decoded]
+            strict, feats, _ = coh.score_images(classifiers, level, x_hat, atts)
+        return {"joint": coh.mean_stats([strict, feats]), "per_sample": {"joint_strict": strict, "joint_features": feats},
+                "decoded": decoded, "attributes": atts}
+
     def product_of_experts(self, mu, logvar, with_prior=False):
         """mmvae_base.py:203-222 on the fused kernel: mu/logvar are lists of (B,D) tensors; returns
         (mu, VARIANCE) of the product (the reference returns the variance as `pd_logvar`)."""

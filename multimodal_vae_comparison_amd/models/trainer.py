@@ -147,6 +147,25 @@ class MultimodalVAE(nn.Module):
                      batch_size=self.config.batch_size)
         return out
 
+    def cross_coherence(self, batches, classifiers, level, **kwargs):
+        """cross-generation coherence (TorchMMVAE.cross_coherence; the model must be in eval mode), logged as
+        test_coherence_text_image_{strict,features} and test_coherence_image_text_{strict,features,letters}"""
+        out = self.model.cross_coherence(batches, classifiers, level, **kwargs)
+        for key, names in (("text_image", ("strict", "features")), ("image_text", ("strict", "features", "letters"))):
+            for name, v in zip(names, out[key]):
+                self.log("test_coherence_{}_{}".format(key, name), torch.tensor(v, dtype=torch.float64),
+                         batch_size=self.config.batch_size)
+        return out
+
+    def joint_coherence(self, classifiers, level, **kwargs):
+        """joint-generation coherence (TorchMMVAE.joint_coherence; the model must be in eval mode), logged as
+        test_coherence_joint_{strict,features}"""
+        out = self.model.joint_coherence(classifiers, level, **kwargs)
+        for name, v in zip(("strict", "features"), out["joint"]):
+            self.log("test_coherence_joint_{}".format(name), torch.tensor(v, dtype=torch.float64),
+                     batch_size=self.config.batch_size)
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;
