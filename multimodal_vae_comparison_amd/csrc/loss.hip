@@ -567,13 +567,14 @@ __global__ __launch_bounds__(64) void ce_time_bwd_kernel(const float* __restrict
 // independent loads (the per-column loops above chase T dependent global loads per pass: 25 us at B = 128), the
 // column statistics come out of LDS, and in backward all 256 threads write the gradient tile.
 #define CE_TILE 4096
+#define CE_TILE_V 256      // columns the tile kernels keep statistics for (ops.CE_TILE / CE_TILE_V: tests pin them together)
 __global__ __launch_bounds__(256) void ce_time_fwd_tile_kernel(const float* __restrict__ lg, const float* __restrict__ tg,
                                                               float* __restrict__ loss, float* __restrict__ row, int T,
                                                               int V, float seed, float* __restrict__ dl, int trows) {
   // dl != NULL: every row's upstream gradient is the constant `seed`; the logit gradient is written from the same
   // staged tile (see bce_rowsum_kernel<true>)
   __shared__ float sl[CE_TILE], st[CE_TILE];
-  __shared__ float s_mx[256], s_k[256];
+  __shared__ float s_mx[CE_TILE_V], s_k[CE_TILE_V];
   __shared__ float red[4];
   MMVAE_TRACE_STAMP(29);
   const int b = blockIdx.x, n = T * V;
@@ -617,7 +618,7 @@ __global__ __launch_bounds__(256) void ce_time_bwd_tile_kernel(const float* __re
                                                               const float* __restrict__ g, const float* __restrict__ grow,
                                                               float* __restrict__ dl, int T, int V, int trows) {
   __shared__ float sl[CE_TILE], st[CE_TILE];
-  __shared__ float s_mx[256], s_k[256], s_gv[256];   // per column: max, ts / sum exp, upstream gradient (V <= 256)
+  __shared__ float s_mx[CE_TILE_V], s_k[CE_TILE_V], s_gv[CE_TILE_V];   // per column: max, ts / sum exp, upstream gradient
   const int b = blockIdx.x, n = T * V;
   const float* L = lg + (size_t)b * n;
   const float* Tg = tg + (size_t)(b % trows) * n;
@@ -649,7 +650,7 @@ __global__ __launch_bounds__(256) void ce_time_bwd_tile_kernel(const float* __re
 extern "C" int mmvae_ce_over_time_fwd(const float* logits, const float* target, float* loss, float* row_loss, int B,
                                       int T, int V, int target_rows, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(logits && target && (loss || row_loss) && B > 0 && T > 0 && V > 0 && target_rows > 0);
-  if (T * V <= CE_TILE && V <= 256)
+  if (T * V <= CE_TILE && V <= CE_TILE_V)
     hipLaunchKernelGGL(ce_time_fwd_tile_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, target, loss,
                        row_loss, T, V, 0.f, nullptr, target_rows);
   else
@@ -662,7 +663,7 @@ extern "C" int mmvae_ce_over_time_fwd(const float* logits, const float* target, 
 extern "C" int mmvae_ce_over_time_seeded(const float* logits, const float* target, float* row_loss, float seed,
                                          float* dlogits, int B, int T, int V, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(logits && target && row_loss && dlogits && B > 0 && T > 0 && V > 0);
-  if (!(T * V <= CE_TILE && V <= 256)) return MMVAE_ERR_UNSUPPORTED;
+  if (!(T * V <= CE_TILE && V <= CE_TILE_V)) return MMVAE_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(ce_time_fwd_tile_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, target,
                      (float*)nullptr, row_loss, T, V, seed, dlogits, B);
   return mmvae_launch_status();
@@ -670,7 +671,7 @@ extern "C" int mmvae_ce_over_time_seeded(const float* logits, const float* targe
 extern "C" int mmvae_ce_over_time_bwd(const float* logits, const float* target, const float* g, const float* g_row,
                                       float* dlogits, int B, int T, int V, int target_rows, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(logits && target && (g || g_row) && dlogits && B > 0 && T > 0 && V > 0 && target_rows > 0);
-  if (T * V <= CE_TILE && V <= 256)
+  if (T * V <= CE_TILE && V <= CE_TILE_V)
     hipLaunchKernelGGL(ce_time_bwd_tile_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, target, g, g_row,
                        dlogits, T, V, target_rows);
   else

@@ -25,7 +25,8 @@ MAX_EXPERTS = 8
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GELU = 0, 1, 2, 3
 EP_NONE, EP_RELU, EP_MUL_RELU_MASK, EP_MUL_SILU_GRAD, EP_GELU, EP_MUL_GELU_GRAD, EP_SIGMOID_CLAMP, EP_SIGMOID, EP_ADD_AUX = range(9)
 
-_ERR = {1: "invalid argument", 2: "unsupported shape", 3: "kernel launch failed"}
+ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = 1, 2, 3      # MMVAE_ERR_* of include/mmvae_hip.h
+_ERR = {ERR_ARG: "invalid argument", ERR_UNSUPPORTED: "unsupported shape", ERR_LAUNCH: "kernel launch failed"}
 
 
 class PoeFwdArgs(ctypes.Structure):
@@ -325,12 +326,15 @@ ACC_DEFER = 2
 MAX_SEGMENTS = 64
 
 
+LC_MAX_ROWS, LC_MAX_OUT = 32, 4      # csrc/loss.hip: rows / outputs of one ELBO assembly (mmvae_rowptrs_t, mmvae_gptrs_t)
+
+
 class RowPtrs(ctypes.Structure):
-    _fields_ = [("p", c_p * 32)]
+    _fields_ = [("p", c_p * LC_MAX_ROWS)]
 
 
 class GPtrs(ctypes.Structure):
-    _fields_ = [("g", c_p * 4)]
+    _fields_ = [("g", c_p * LC_MAX_OUT)]
 
 
 INPUT_MAX_MODS = 8

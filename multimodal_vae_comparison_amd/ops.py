@@ -1720,6 +1720,11 @@ def add_pe_dropout(x, pe, T, B, D, drop=None):
     return AddPEDropout.apply(x, pe, T, B, D, drop)
 
 
+# what one workgroup of ce_time_*_tile_kernel stages: CE_TILE / CE_TILE_V of csrc/loss.hip (the seeded launch exists for
+# the tile kernel only)
+CE_TILE, CE_TILE_V = 4096, 256
+
+
 class CeOverTime(Function):
     """category_ce with the softmax over TIME (models/objectives.py:486-500): logits/target (B,T,V) ->
     loss (B,V) [per_v=True] or its row sums (B,)."""
@@ -1736,7 +1741,7 @@ class CeOverTime(Function):
         cs = ConstSeed.current
         ctx.seeded = None
         ctx.trows = trows
-        if cs is not None and not per_v and logits.requires_grad and T * V <= 4096 and V <= 256 and trows == B:
+        if cs is not None and not per_v and logits.requires_grad and T * V <= CE_TILE and V <= CE_TILE_V and trows == B:
             dl = torch.empty_like(logits)
             _call("mmvae_ce_over_time_seeded", H.ptr(logits), H.ptr(target), H.ptr(row), cs.value, H.ptr(dl), B, T, V,
                   H.stream())
@@ -1761,6 +1766,14 @@ class CeOverTime(Function):
         return dl, None, None
 
 
+def _lincomb_fits(n, k):
+    """the library refuses more rows / outputs than its weight table holds (MMVAE_ERR_UNSUPPORTED); the row-pointer
+    table built here has the same size, so the refusal comes before it is filled"""
+    if n > H.LC_MAX_ROWS or k > H.LC_MAX_OUT:
+        raise RuntimeError(f"lincomb_rows: unsupported shape ({n} rows, {k} outputs; at most {H.LC_MAX_ROWS} and "
+                           f"{H.LC_MAX_OUT})")
+
+
 class LincombRows(Function):
     unit_seed_ptr = None      # data_ptr of the trainer's persistent backward seed (a ones scalar), see backward()
 
@@ -1774,7 +1787,7 @@ class LincombRows(Function):
         B = blocks[0].shape[-1]
         rows = [t.numel() // B for t in blocks]
         n, k = sum(rows), len(W)
-        assert n <= 32 and k <= 4
+        _lincomb_fits(n, k)
         rp = H.RowPtrs()
         i = 0
         for t, r in zip(blocks, rows):
@@ -1833,7 +1846,7 @@ def lincomb_rows_args(blocks, W):
     B = blocks[0].shape[-1]
     rows = [t.numel() // B for t in blocks]
     n, k = sum(rows), len(W)
-    assert n <= 32 and k <= 4
+    _lincomb_fits(n, k)
     rp = H.RowPtrs()
     i = 0
     for t, r in zip(blocks, rows):
