@@ -858,6 +858,59 @@ int mmvae_cls_head(const float* feats, const float* W1, const float* b1, const f
                    int* n_correct, int A, int N, int Cmax, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * MNIST-SVHN digit coherence (TorchMMVAE.digit_cross_coherence / digit_joint_coherence; csrc/digits.hip): the
+ * reference's two digit classifiers (eval/mnistsvhn_helper.py:191-226) and the loop that trains them
+ * (eval/eval_mnistsvhn.py:70-120: CrossEntropyLoss + optim.Adam).  All fp32, no autograd.
+ *   MMVAE_DIGIT_MNIST: x (1,28,28) -> conv1 1->10 k5 (10,24,24) -> maxpool 2 -> relu -> conv2 10->20 k5 (20,8,8)
+ *     -> Dropout2d -> maxpool 2 -> relu -> flatten 320 (channel, y, x) -> fc1 320->50 -> relu -> dropout -> fc2 50->10
+ *     -> log_softmax;  21 840 parameters.
+ *   MMVAE_DIGIT_SVHN: x (3,32,32) -> (10,28,28) -> (10,14,14) -> (20,10,10) -> (20,5,5) = 500 -> 50 -> 10;  31 340.
+ *   Packed parameters: conv1.w (10,C,5,5), conv1.b, conv2.w (20,10,5,5), conv2.b, fc1.w (50,flat), fc1.b, fc2.w (10,50),
+ *   fc2.b, each in torch's layout.  state (nets,3,stride) fp32: per network [parameters | exp_avg | exp_avg_sq], stride >=
+ *   the largest parameter count of the launch (elements past a network's count are never read or written).
+ *   kinds: HOST pointer to `nets` ints;  images / labels: HOST arrays of `nets` DEVICE pointers, network i reads
+ *   images[i] (N,C,H,W) fp32 and labels[i] (N) int32 (labels outside [0, 10) are the caller's error).
+ *   Max-pool keeps the FIRST maximum of its window in row-major order and its backward sends the gradient there (torch's
+ *   rule); ReLU's backward passes the gradient where the output is > 0.
+ *   Dropout (training entry points only): mask element = 0 or 1 / (1 - p), drawn by the counter-based hash of
+ *   csrc/common.hpp from (seed, kind, global step, position r of the row inside its minibatch, unit) and nothing else;
+ *   Dropout2d masks the 20 channels of conv2's output, dropout the 50 outputs of relu(fc1).  p = 0: no dropout.
+ * mmvae_digit_eval: logp (nets,N,10) log-probabilities, pred (nets,N) int32 = their first maximum; dropout off.
+ * mmvae_digit_grad: the first half of a training step on the minibatch images[i][0 .. rows): rowloss (nets,rows) =
+ *   -logp[label], grad (nets,stride) = the gradient of mean_r rowloss with the masks of (seed, step).
+ * mmvae_digit_train: the global steps [step0, step0 + n_steps), minibatch schedule and `order` (order_epochs, N) exactly
+ *   as mmvae_probe_train (step t: positions [i batch, min(N, (i + 1) batch)) of epoch t / ceil(N / batch); the mean of a
+ *   short last minibatch runs over the rows it has).  Per step two launches: one workgroup per (image, network) runs
+ *   forward and backward and leaves the image's gradient in its row of ws; the second sums the rows -- four consecutive
+ *   quarters of the minibatch, each in row order, added as (0 + 1) + (2 + 3) -- and applies torch.optim.Adam (defaults:
+ *   betas 0.9 / 0.999, eps 1e-8, no amsgrad), bias corrections of step t + 1:
+ *     p -= lr / (1 - b1^(t+1)) * m / (sqrt(v) / sqrt(1 - b2^(t+1)) + eps).
+ *   loss (nets,n_steps): the mean loss of every step.  No atomics, every sum in a fixed order: two runs, one call or the
+ *   same steps split over several, and a network trained alone or beside the other are bit-identical.
+ *   ws: mmvae_digit_ws_floats(nets, batch, stride) floats (grad: batch = rows), private to the call until it has run.
+ * mmvae_digit_masks: m2d (n_steps,batch,20) and m1 (n_steps,batch,50): the masks mmvae_digit_train / _grad use for the
+ *   steps [step0, step0 + n_steps) of one network kind.
+ * nets <= MMVAE_DIGIT_MAX_NETS, the two kinds, 0 <= p < 1, 1 <= batch, rows <= 65535; anything else returns
+ * MMVAE_ERR_UNSUPPORTED and writes nothing.  The row cap is a budget, not an index limit: ws holds one gradient row of
+ * stride floats per image of the minibatch, 8.2 GB per network at 65535 rows of 31340.
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_DIGIT_MNIST 0
+#define MMVAE_DIGIT_SVHN 1
+#define MMVAE_DIGIT_MAX_NETS 2
+int mmvae_digit_n_params(int kind); /* 21840 / 31340; 0 for an unknown kind */
+size_t mmvae_digit_ws_floats(int nets, int batch, int stride);
+int mmvae_digit_eval(const float* state, const int* kinds, const float* const* images, float* logp, int* pred, int nets,
+                     int stride, long N, mmvae_stream_t stream);
+int mmvae_digit_grad(const float* state, const int* kinds, const float* const* images, const int* const* labels,
+                     float* ws, float* grad, float* rowloss, int nets, int stride, int rows, unsigned seed, long step,
+                     float p, mmvae_stream_t stream);
+int mmvae_digit_train(float* state, const int* kinds, const float* const* images, const int* const* labels,
+                      const int* order, int order_epochs, float* ws, float* loss, int nets, int stride, int N, int batch,
+                      long step0, int n_steps, float lr, unsigned seed, float p, mmvae_stream_t stream);
+int mmvae_digit_masks(float* m2d, float* m1, int kind, unsigned seed, long step0, int n_steps, int batch, float p,
+                      mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

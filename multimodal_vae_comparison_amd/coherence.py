@@ -6,6 +6,9 @@ Three parts:
   * AttributeClassifier / AttributeClassifiers: the reference's image classifiers (one CNN per attribute) on the
     k4-s2 conv kernels, their heads in one ops.cls_head launch;
   * the scoring helpers TorchMMVAE.cross_coherence / joint_coherence are built from.
+For the MNIST-SVHN benchmark (reference: eval/eval_mnistsvhn.py) DigitClassifier / DigitClassifiers at the end of the file:
+the two LeNet-style digit classifiers, trained and scored on csrc/digits.hip (TorchMMVAE.digit_cross_coherence /
+digit_joint_coherence).
 """
 import torch
 import torch.nn as nn
@@ -266,3 +269,150 @@ def score_images(classifiers, level, x_hat, captions):
     out = classifiers.predict(x_hat, labels=labels)
     n_ok = out["n_correct"].cpu().tolist()
     return [int(k == len(atts)) for k in n_ok], [k / len(atts) for k in n_ok], out
+
+
+# ---- MNIST-SVHN digit classifiers (eval/mnistsvhn_helper.py:191-226, eval/eval_mnistsvhn.py:70-120) ---------------------
+class DigitClassifier(nn.Module):
+    """eval/mnistsvhn_helper.py: MNIST_Classifier / SVHN_Classifier -- Conv2d(C, 10, 5), max-pool 2, ReLU, Conv2d(10, 20, 5),
+    Dropout2d, max-pool 2, ReLU, Linear(320 | 500, 50), ReLU, dropout, Linear(50, 10), log_softmax -- under the
+    reference's state-dict keys (conv1 / conv2 / fc1 / fc2, each `.weight|bias`), so a mnist_model.pt / svhn_model.pt it
+    wrote loads with strict=True.  The modules only hold the parameters: forward and training run on csrc/digits.hip
+    (ops.digit_eval / ops.digit_train through DigitClassifiers)."""
+
+    def __init__(self, kind):
+        super().__init__()
+        if kind not in ops.DIGIT_KINDS:
+            raise ValueError(f"DigitClassifier: kind = {kind!r} ('mnist' or 'svhn')")
+        self.kind = kind
+        C, flat = ops.DIGIT_INPUT[kind][0], (320 if kind == "mnist" else 500)
+        self.conv1 = nn.Conv2d(C, 10, kernel_size=5)
+        self.conv2 = nn.Conv2d(10, 20, kernel_size=5)
+        self.fc1 = nn.Linear(flat, 50)
+        self.fc2 = nn.Linear(50, 10)
+        self.requires_grad_(False)
+        self._packed = None
+
+    def packed_state(self):
+        """(1, 3, n_params) device state whose first row holds the packed parameters; packed again whenever a parameter was
+        replaced, moved or written in place"""
+        src = [self.get_parameter(k) for k, _ in ops.digit_param_shapes(self.kind)]
+        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in src)
+        if self._packed is None or self._packed[0] != key:
+            st = torch.zeros(1, 3, ops.DIGIT_N_PARAMS[self.kind], device=src[0].device)
+            st[0, 0] = torch.cat([p.detach().float().reshape(-1) for p in src])
+            self._packed = (key, st)
+        return self._packed[1]
+
+    def images(self, x):
+        """any tensor that holds (N,C,H,W) images -- or (N,32,32,3), as Dec_SVHN returns them: permuted back -- as the
+        contiguous fp32 (N,C,H,W) the kernels read"""
+        C, Hh, Ww = ops.DIGIT_INPUT[self.kind]
+        x = x.detach().float()
+        if C == 3 and tuple(x.shape[-3:]) == (Hh, Ww, C):
+            x = x.reshape(-1, Hh, Ww, C).permute(0, 3, 1, 2)
+        if x.numel() % (C * Hh * Ww) != 0:
+            raise ValueError(f"DigitClassifier({self.kind}): images of shape {tuple(x.shape)}")
+        return x.reshape(-1, C, Hh, Ww).contiguous()
+
+    def forward(self, x):
+        """log-probabilities (N, 10) of images x (N,C,H,W); dropout off (the classifiers score in eval mode)"""
+        return ops.digit_eval(self.packed_state(), [self.kind], [self.images(x)])[0][0]
+
+
+class DigitClassifiers(nn.Module):
+    """The MNIST and the SVHN digit classifier of the MNIST-SVHN coherence metrics, trained and scored together."""
+    KINDS = ("mnist", "svhn")
+
+    def __init__(self, mnist=None, svhn=None):
+        super().__init__()
+        mnist = DigitClassifier("mnist") if mnist is None else mnist
+        svhn = DigitClassifier("svhn") if svhn is None else svhn
+        for k, c in (("mnist", mnist), ("svhn", svhn)):
+            if not isinstance(c, DigitClassifier) or c.kind != k:
+                raise TypeError(f"DigitClassifiers: `{k}` must be a DigitClassifier('{k}')")
+        self.mnist, self.svhn = mnist, svhn
+        self._stacked = None
+
+    def _split(self, batches, what, mnist=None, svhn=None):
+        """an iterable of (batch dict, labels) -> (MNIST images (N,1,28,28), SVHN images (N,3,32,32), labels (N,) int32),
+        on the classifiers' device.  The modalities are `mnist` / `svhn`, else the ones whose rows hold 784 / 3072 values."""
+        from .models.mmvae_base import TorchMMVAE
+        batches = list(batches)
+        y = TorchMMVAE._label_matrix(batches, what, "DigitClassifiers")
+        if y.shape[0] != 1:
+            raise ValueError(f"DigitClassifiers: {y.shape[0]} label columns in the {what} set (one digit label per sample)")
+        if int(y.min()) < 0 or int(y.max()) >= 10:
+            raise ValueError(f"DigitClassifiers: {what} labels in [{int(y.min())}, {int(y.max())}], outside [0, 10)")
+        dev = self.mnist.conv1.weight.device
+        xs = {"mnist": [], "svhn": []}
+        for batch, _ in batches:
+            names = {"mnist": mnist, "svhn": svhn}
+            for k, n_el in (("mnist", 784), ("svhn", 3072)):
+                if names[k] is None:
+                    hit = [m for m, v in batch.items() if v["data"] is not None and v["data"][0].numel() == n_el]
+                    if len(hit) != 1:
+                        raise ValueError(f"DigitClassifiers: name the `{k}` modality (batch holds {list(batch)})")
+                    names[k] = hit[0]
+                if names[k] not in batch or batch[names[k]]["data"] is None:
+                    raise ValueError(f"DigitClassifiers: a {what} batch has no data for modality {names[k]!r}")
+                xs[k].append(getattr(self, k).images(batch[names[k]]["data"]).to(dev))
+        xm, xsv = torch.cat(xs["mnist"]).contiguous(), torch.cat(xs["svhn"]).contiguous()
+        if xm.shape[0] != y.shape[1] or xsv.shape[0] != y.shape[1]:
+            raise ValueError(f"DigitClassifiers: {xm.shape[0]} MNIST / {xsv.shape[0]} SVHN images for {y.shape[1]} labels")
+        return xm, xsv, y[0].to(device=dev, dtype=torch.int32).contiguous()
+
+    def _stacked_state(self):
+        """(2, 3, n_params_max) state with both networks' packed parameters, built again only when one of them was"""
+        packed = [n.packed_state() for n in (self.mnist, self.svhn)]
+        key = tuple(id(p) for p in packed)
+        if self._stacked is None or self._stacked[0] != key:
+            st = torch.zeros(2, 3, ops.DIGIT_N_PARAMS["svhn"], device=packed[0].device)
+            for i, p in enumerate(packed):
+                st[i, 0, :p.shape[-1]] = p[0, 0]
+            self._stacked = (key, st, packed)
+        return self._stacked[1]
+
+    def fit(self, train, epochs, batch_size=128, lr=1e-3, seed=0, p=0.5, shuffle=False, mnist=None, svhn=None):
+        """The reference's training loop (eval/eval_mnistsvhn.py:76-97: CrossEntropyLoss + optim.Adam(lr), minibatches in
+        the loader's order) for both classifiers side by side, from the parameters the modules hold.  `train`: an iterable
+        of (batch dict, labels (B,) ints) as TorchMMVAE.classify_latents takes it.  The images are copied to the device
+        once; every epoch is one ops.digit_train call (`shuffle`: per-epoch permutations from torch.Generator(seed));
+        `seed` also keys the dropout masks, `p` is their rate (the reference's 0.5).
+        -> loss (2, steps): the mean loss of every step, rows mnist / svhn; the trained parameters are written back."""
+        epochs, batch_size = int(epochs), int(batch_size)
+        if epochs < 1 or batch_size < 1:
+            raise ValueError(f"DigitClassifiers.fit: epochs = {epochs}, batch_size = {batch_size}")
+        xm, xs, y = self._split(train, "train", mnist, svhn)
+        dev, N = xm.device, xm.shape[0]
+        nets = [self.mnist, self.svhn]
+        state = ops.digit_state(self.KINDS, dev, init=[{k: v for k, v in n.state_dict().items()} for n in nets])
+        order = None
+        if shuffle:
+            g = torch.Generator().manual_seed(int(seed))
+            order = torch.stack([torch.randperm(N, generator=g) for _ in range(epochs)]).to(device=dev, dtype=torch.int32)
+        spe = (N + batch_size - 1) // batch_size
+        curve = torch.cat([ops.digit_train(state, self.KINDS, [xm, xs], [y, y], batch_size, e * spe, spe, lr=lr, seed=seed,
+                                           p=p, order=order, validate=False) for e in range(epochs)], 1)
+        with torch.no_grad():
+            for i, n in enumerate(nets):
+                for k, v in ops.digit_unpack(n.kind, state[i, 0]).items():
+                    n.get_parameter(k).copy_(v)
+        return curve
+
+    def predict(self, x_mnist=None, x_svhn=None):
+        """the digits the classifiers see: -> {"mnist": (N,) int32 | absent, "svhn": ...} (first maximum of the
+        log-probabilities); both networks in one launch when both image sets have the same length"""
+        if x_mnist is None and x_svhn is None:
+            raise ValueError("DigitClassifiers.predict: no images")
+        given = [(k, getattr(self, k), x) for k, x in (("mnist", x_mnist), ("svhn", x_svhn)) if x is not None]
+        imgs = [n.images(x) for _, n, x in given]
+        if len(given) == 2 and imgs[0].shape[0] == imgs[1].shape[0]:
+            pred = ops.digit_eval(self._stacked_state(), list(self.KINDS), imgs)[1]
+            return {k: pred[i] for i, k in enumerate(self.KINDS)}
+        return {k: ops.digit_eval(n.packed_state(), [k], [x])[1][0] for (k, n, _), x in zip(given, imgs)}
+
+    def accuracy(self, test, mnist=None, svhn=None):
+        """-> {"mnist": share of the test images classified as their label, "svhn": ...} (fractions in [0, 1])"""
+        xm, xs, y = self._split(test, "test", mnist, svhn)
+        pred = self.predict(xm, xs)
+        return {k: float((pred[k] == y).sum()) / y.shape[0] for k in self.KINDS}

@@ -74,6 +74,7 @@ MIX_MAX_COMPONENTS = 8
 
 PROBE_MAX_CLASSES, PROBE_MAX_PROBES = 32, 64
 COH_MAX_STEPS, COH_MAX_VOCAB, COH_MAX_CLASSIFIERS, COH_MAX_CLASSES, COH_FEATS, COH_HIDDEN = 256, 256, 8, 8, 512, 256
+DIGIT_MNIST, DIGIT_SVHN, DIGIT_MAX_NETS = 0, 1, 2      # csrc/digits.hip
 
 
 class LmeRows(ctypes.Structure):
@@ -289,6 +290,14 @@ SIGNATURES = {
     "mmvae_probe_eval": (c_i, [c_p] * 3 + [ctypes.POINTER(c_i), c_p, c_p] + [c_i] * 6 + [c_p]),
     "mmvae_text_decode_score": (c_i, [c_p] * 5 + [c_i] * 3 + [c_p]),
     "mmvae_cls_head": (c_i, [c_p] * 5 + [ctypes.POINTER(c_i)] + [c_p] * 5 + [c_i] * 3 + [c_p]),
+    "mmvae_digit_n_params": (c_i, [c_i]),
+    "mmvae_digit_ws_floats": (c_sz, [c_i] * 3),
+    "mmvae_digit_eval": (c_i, [c_p, ctypes.POINTER(c_i), ctypes.POINTER(c_p), c_p, c_p, c_i, c_i, c_l, c_p]),
+    "mmvae_digit_grad": (c_i, [c_p, ctypes.POINTER(c_i)] + [ctypes.POINTER(c_p)] * 2 + [c_p] * 3 + [c_i] * 3 +
+                         [c_u, c_l, c_f, c_p]),
+    "mmvae_digit_train": (c_i, [c_p, ctypes.POINTER(c_i)] + [ctypes.POINTER(c_p)] * 2 + [c_p, c_i, c_p, c_p] + [c_i] * 4 +
+                          [c_l, c_i, c_f, c_u, c_f, c_p]),
+    "mmvae_digit_masks": (c_i, [c_p, c_p, c_i, c_u, c_l, c_i, c_i, c_f, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

@@ -410,16 +410,16 @@ class TorchMMVAE(nn.Module):
         return given, ["+".join(g) for g in given], [(s, a, n_classes[a]) for s in range(len(given)) for a in range(A)]
 
     @staticmethod
-    def _label_matrix(batches, what):
-        """labels of an iterable of (batch, labels) -> (A, N) int64 on the host"""
+    def _label_matrix(batches, what, who="classify_latents"):
+        """labels of an iterable of (batch, labels) -> (A, N) int64 on the host; `who` names the caller in the errors"""
         cols = []
         for _, y in batches:
             y = torch.as_tensor(y).detach().cpu()
             if y.is_floating_point() or y.dim() not in (1, 2):
-                raise ValueError(f"classify_latents: {what} labels must be an integer (B,) or (B, A) array")
+                raise ValueError(f"{who}: {what} labels must be an integer (B,) or (B, A) array")
             cols.append(y.long().reshape(y.shape[0], -1))
         if not cols:
-            raise ValueError(f"classify_latents: the {what} set is empty")
+            raise ValueError(f"{who}: the {what} set is empty")
         return torch.cat(cols, 0).t().contiguous()
 
     def classify_latents(self, train, test, n_classes, given=None, epochs=30, batch_size=128, lr=1e-3, seed=0,
@@ -613,6 +613,109 @@ class TorchMMVAE(nn.Module):
             strict, feats, _ = coh.score_images(classifiers, level, x_hat, atts)
         return {"joint": coh.mean_stats([strict, feats]), "per_sample": {"joint_strict": strict, "joint_features": feats},
                 "decoded": decoded, "attributes": atts}
+
+    # ---- MNIST-SVHN digit coherence ------------------------------------------------------------
+    def _mnist_svhn(self, mnist, svhn):
+        """names of the MNIST and the SVHN modality: as given, else the ones with 28 x 28 x 1 / 32 x 32 x 3 data"""
+        names = list(self.vaes.keys())
+        out = []
+        for given, dims, what in ((mnist, ((28, 28, 1), (1, 28, 28)), "mnist"), (svhn, ((32, 32, 3), (3, 32, 32)), "svhn")):
+            if given is None:
+                hit = [m for m in names if tuple(self.vaes[m].data_dim) in dims]
+                if len(hit) != 1:
+                    raise ValueError(f"digit coherence: name the `{what}` modality (this model has {names})")
+                given = hit[0]
+            out.append(given)
+        if out[0] not in names or out[1] not in names or out[0] == out[1]:
+            raise ValueError(f"digit coherence: mnist = {out[0]!r}, svhn = {out[1]!r} are not two modalities of this model "
+                             f"({names})")
+        return out
+
+    @staticmethod
+    def _digit_classifiers(classifiers):
+        from .. import coherence as coh
+        if not isinstance(classifiers, coh.DigitClassifiers):
+            raise TypeError("digit coherence: `classifiers` must be a coherence.DigitClassifiers")
+        return classifiers
+
+    def digit_cross_coherence(self, batches, classifiers, mnist=None, svhn=None, eps=None, reconstruct=False):
+        """Cross-generation coherence of the MNIST-SVHN benchmark (eval/eval_mnistsvhn.py:122-154).  `batches`: an
+        iterable of (batch dict, digit labels (B,) ints); `classifiers`: a trained coherence.DigitClassifiers.  Per batch
+        two forward() calls: only SVHN given -- the decoded MNIST image is classified -- and only MNIST given -- the
+        decoded SVHN image, permuted back to NCHW, is classified; a sample counts when the classifier reads the batch's
+        label.  That is the metric as defined.  The reference's code builds the two one-modality copies of the batch and
+        then forwards the FULL batch both times (lines 134-140), so that it scores reconstructions; `reconstruct=True`
+        does that literally.
+        -> {"svhn_mnist": %, "mnist_svhn": %, "per_sample": {"svhn_mnist": [0/1], "mnist_svhn": [0/1]},
+            "pred": {"svhn_mnist": (N,) int32, "mnist_svhn": (N,) int32}, "labels": (N,) int64}.
+        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
+        tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
+        dropout counters, gradients and the optimiser stay as they are."""
+        self._coherence_guard("digit_cross_coherence")
+        classifiers = self._digit_classifiers(classifiers)
+        mnist, svhn = self._mnist_svhn(mnist, svhn)
+        batches = list(batches)
+        if not batches:
+            raise ValueError("digit_cross_coherence: `batches` is empty")
+        y = self._label_matrix(batches, "test", "digit_cross_coherence")
+        if y.shape[0] != 1 or int(y.min()) < 0 or int(y.max()) >= 10:
+            raise ValueError("digit_cross_coherence: one digit label in [0, 10) per sample")
+        pred = {"svhn_mnist": [], "mnist_svhn": []}
+        saved = self.eps_override
+        self.eps_override = None if eps is None else [e for e in eps]
+        self._eval_draws = True
+        try:
+            with torch.no_grad():
+                for batch, _ in batches:
+                    if any(m not in batch or batch[m]["data"] is None for m in (mnist, svhn)):
+                        raise ValueError("digit_cross_coherence: every batch must hold the MNIST and the SVHN modality")
+                    B = batch[mnist]["data"].shape[0]
+                    out = self.forward(batch if reconstruct else self._given_only(batch, [svhn]))
+                    x_m = classifiers.mnist.images(out.mods[mnist].decoder_dist.loc)[:B]
+                    pred["svhn_mnist"].append(classifiers.predict(x_mnist=x_m)["mnist"])
+                    out = self.forward(batch if reconstruct else self._given_only(batch, [mnist]))
+                    x_s = classifiers.svhn.images(out.mods[svhn].decoder_dist.loc)[:B]
+                    pred["mnist_svhn"].append(classifiers.predict(x_svhn=x_s)["svhn"])
+        finally:
+            self._eval_draws = False
+            self.eps_override = saved
+        pred = {k: torch.cat(v).cpu() for k, v in pred.items()}
+        per = {k: (v.long() == y[0]).int().tolist() for k, v in pred.items()}
+        return {"svhn_mnist": 100.0 * sum(per["svhn_mnist"]) / y.shape[1],
+                "mnist_svhn": 100.0 * sum(per["mnist_svhn"]) / y.shape[1], "per_sample": per, "pred": pred, "labels": y[0]}
+
+    def digit_joint_coherence(self, classifiers, n=1000, eps=None, mnist=None, svhn=None):
+        """Joint-generation coherence of the MNIST-SVHN benchmark (eval/eval_mnistsvhn.py:157-180): n latents z ~ p(z) =
+        Normal(*pz_params), both images decoded from the SAME z, the score is the share of samples in which the two digit
+        classifiers read the same digit.  The decoded SVHN image (n,32,32,3) is permuted back to (n,3,32,32); the
+        reference RESHAPES it instead (`.reshape(-1,3,32,32)`, line 170), which hands its classifier scrambled pixels --
+        the metric's definition is what is computed here.
+        -> {"joint": %, "per_sample": [0/1], "pred": {"mnist": (n,) int32, "svhn": (n,) int32}}.
+        Needs eval mode; runs without gradients; the draw comes from the evaluation generator, or is `eps` (n, D).
+        Models with private latents (DMVAE) have no joint prior sample to decode: NotImplementedError."""
+        self._coherence_guard("digit_joint_coherence")
+        if self.latent_factorization:
+            raise NotImplementedError(f"{self.modelName}: digit_joint_coherence is built for the mixers with one shared "
+                                      f"latent space (poe, moe, mopoe); private latents have no joint prior sample")
+        classifiers = self._digit_classifiers(classifiers)
+        mnist, svhn = self._mnist_svhn(mnist, svhn)
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"digit_joint_coherence: n = {n}")
+        with torch.no_grad():
+            loc, scale = self.pz_params
+            D = self.n_latents
+            if eps is None:
+                e = ops.randn((n, D), self._eval_rng_state)
+            else:
+                e = eps.to(device=loc.device, dtype=torch.float32).reshape(n, D)
+            z = (loc + scale * e).unsqueeze(0).contiguous()
+            x_m = self.vaes[mnist].dec({"latents": z, "masks": None})[0]
+            x_s = self.vaes[svhn].dec({"latents": z, "masks": None})[0]
+            pred = classifiers.predict(x_mnist=x_m, x_svhn=x_s)
+        pred = {k: v.cpu() for k, v in pred.items()}
+        same = (pred["mnist"] == pred["svhn"]).int().tolist()
+        return {"joint": 100.0 * sum(same) / n, "per_sample": same, "pred": pred}
 
     def product_of_experts(self, mu, logvar, with_prior=False):
         """mmvae_base.py:203-222 on the fused kernel: mu/logvar are lists of (B,D) tensors; returns

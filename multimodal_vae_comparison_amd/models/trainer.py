@@ -166,6 +166,23 @@ class MultimodalVAE(nn.Module):
                      batch_size=self.config.batch_size)
         return out
 
+    def digit_cross_coherence(self, batches, classifiers, **kwargs):
+        """MNIST-SVHN cross-generation coherence (TorchMMVAE.digit_cross_coherence; the model must be in eval mode), logged
+        as test_coherence_svhn_mnist and test_coherence_mnist_svhn"""
+        out = self.model.digit_cross_coherence(batches, classifiers, **kwargs)
+        for key in ("svhn_mnist", "mnist_svhn"):
+            self.log("test_coherence_{}".format(key), torch.tensor(out[key], dtype=torch.float64),
+                     batch_size=self.config.batch_size)
+        return out
+
+    def digit_joint_coherence(self, classifiers, **kwargs):
+        """MNIST-SVHN joint-generation coherence (TorchMMVAE.digit_joint_coherence; the model must be in eval mode),
+        logged as test_coherence_digit_joint"""
+        out = self.model.digit_joint_coherence(classifiers, **kwargs)
+        self.log("test_coherence_digit_joint", torch.tensor(out["joint"], dtype=torch.float64),
+                 batch_size=self.config.batch_size)
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;

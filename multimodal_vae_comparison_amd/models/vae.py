@@ -118,6 +118,14 @@ class VAE(BaseVae):
         raise NotImplementedError("unimodal VAE: joint_coherence is built for the multimodal mixers "
                                   "(TorchMMVAE.joint_coherence)")
 
+    def digit_cross_coherence(self, *args, **kwargs):
+        raise NotImplementedError("unimodal VAE: digit_cross_coherence is built for the multimodal mixers "
+                                  "(TorchMMVAE.digit_cross_coherence)")
+
+    def digit_joint_coherence(self, *args, **kwargs):
+        raise NotImplementedError("unimodal VAE: digit_joint_coherence is built for the multimodal mixers "
+                                  "(TorchMMVAE.digit_joint_coherence)")
+
     # ---- the unimodal case: `self.model = vaes["mod_1"]` (models/trainer.py:112-113) ------------------------------
     def objective(self, data):
         """VAE.forward + objective with UnimodalObjective.elbo (models/vae.py:92-119,268-282, models/objectives.py:233-247):
