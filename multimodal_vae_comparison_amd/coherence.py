@@ -5,10 +5,10 @@ Three parts:
     one a decoded caption spells at the word position its level prescribes, the letter count);
   * AttributeClassifier / AttributeClassifiers: the reference's image classifiers (one CNN per attribute) on the
     k4-s2 conv kernels, their heads in one ops.cls_head launch;
-  * the scoring helpers TorchMMVAE.cross_coherence / joint_coherence are built from.
+  * the scoring helpers TorchMMVAE.cross_coherence / joint_coherence (models/evaluation.py) are built from.
 For the MNIST-SVHN benchmark (reference: eval/eval_mnistsvhn.py) DigitClassifier / DigitClassifiers at the end of the file:
 the two LeNet-style digit classifiers, trained and scored on csrc/digits.hip (TorchMMVAE.digit_cross_coherence /
-digit_joint_coherence).
+digit_joint_coherence).  Nothing here imports the models: they import this module.
 """
 import torch
 import torch.nn as nn
@@ -131,6 +131,11 @@ def mean_stats(lists, percentage=True):
 
 
 # ---- image classifiers ----------------------------------------------------------------------------------------------
+def _cache_key(params):
+    """changes whenever one of `params` was replaced, moved or written in place: what a packed copy of them is kept under"""
+    return tuple((p.data_ptr(), p._version, str(p.device)) for p in params)
+
+
 class _Wrapped(nn.Module):
     """a layer under the key `<name>.module.*` (the reference wraps every layer in DataParallel)"""
 
@@ -211,7 +216,7 @@ class AttributeClassifiers(nn.Module):
         replaced, moved or written in place"""
         nets = list(self.nets.values())
         src = [p for n in nets for p in (n.lin1.module.weight, n.lin1.module.bias, n.fc.module.weight, n.fc.module.bias)]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in src)
+        key = _cache_key(src)
         if self._packed is None or self._packed[0] != key:
             Cmax = max(self.n_classes)
             dev = src[0].device
@@ -296,7 +301,7 @@ class DigitClassifier(nn.Module):
         """(1, 3, n_params) device state whose first row holds the packed parameters; packed again whenever a parameter was
         replaced, moved or written in place"""
         src = [self.get_parameter(k) for k, _ in ops.digit_param_shapes(self.kind)]
-        key = tuple((p.data_ptr(), p._version, str(p.device)) for p in src)
+        key = _cache_key(src)
         if self._packed is None or self._packed[0] != key:
             st = torch.zeros(1, 3, ops.DIGIT_N_PARAMS[self.kind], device=src[0].device)
             st[0, 0] = torch.cat([p.detach().float().reshape(-1) for p in src])
@@ -336,9 +341,8 @@ class DigitClassifiers(nn.Module):
     def _split(self, batches, what, mnist=None, svhn=None):
         """an iterable of (batch dict, labels) -> (MNIST images (N,1,28,28), SVHN images (N,3,32,32), labels (N,) int32),
         on the classifiers' device.  The modalities are `mnist` / `svhn`, else the ones whose rows hold 784 / 3072 values."""
-        from .models.mmvae_base import TorchMMVAE
         batches = list(batches)
-        y = TorchMMVAE._label_matrix(batches, what, "DigitClassifiers")
+        y = ops.label_matrix(batches, what, "DigitClassifiers")
         if y.shape[0] != 1:
             raise ValueError(f"DigitClassifiers: {y.shape[0]} label columns in the {what} set (one digit label per sample)")
         if int(y.min()) < 0 or int(y.max()) >= 10:
@@ -386,10 +390,7 @@ class DigitClassifiers(nn.Module):
         dev, N = xm.device, xm.shape[0]
         nets = [self.mnist, self.svhn]
         state = ops.digit_state(self.KINDS, dev, init=[{k: v for k, v in n.state_dict().items()} for n in nets])
-        order = None
-        if shuffle:
-            g = torch.Generator().manual_seed(int(seed))
-            order = torch.stack([torch.randperm(N, generator=g) for _ in range(epochs)]).to(device=dev, dtype=torch.int32)
+        order = ops.epoch_orders(N, epochs, seed, dev, shuffle)
         spe = (N + batch_size - 1) // batch_size
         curve = torch.cat([ops.digit_train(state, self.KINDS, [xm, xs], [y, y], batch_size, e * spe, spe, lr=lr, seed=seed,
                                            p=p, order=order, validate=False) for e in range(epochs)], 1)

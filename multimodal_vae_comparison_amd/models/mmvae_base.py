@@ -8,8 +8,9 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from .evaluation import EvaluationMixin
 from .nn_modules import DropoutState
-from .objectives import MultimodalObjective, recon_rowsum
+from .objectives import MultimodalObjective
 from .output_storage import VAEOutput
 
 # the decoders' first dropout-counter advance rides on the first encoder's launch (DropoutState.link;
@@ -33,9 +34,9 @@ def packed_head(mu, lv):
     return torch.cat([mu, lv], dim=-1).contiguous()
 
 
-class TorchMMVAE(nn.Module):
+class TorchMMVAE(EvaluationMixin, nn.Module):
     """mmvae_base.py:12-240.  Plugin contract: subclass, implement modality_mixing(mods) and
-    objective(mods) -> {"loss": scalar, ["reconstruction_loss": ..., "kld": ...]}."""
+    objective(mods) -> {"loss": scalar, ["reconstruction_loss": ..., "kld": ...]}.  Metrics: EvaluationMixin."""
 
     def __init__(self, vaes, n_latents: int, obj: str, beta=1, K=1):
         super().__init__()
@@ -58,11 +59,11 @@ class TorchMMVAE(nn.Module):
         # counter-based device noise generator {seed, call counter, ticket} (ops.randn)
         self.register_buffer("_rng_state", torch.tensor([torch.initial_seed() & 0x7FFFFFFF, 0, 0], dtype=torch.int32),
                              persistent=False)
-        # the evaluation draws (estimate_log_likelihood) have a generator state of their own: the training noise stream
+        # the evaluation draws (models/evaluation.py) have a generator state of their own: the training noise stream
         # does not move when a model is evaluated between two steps
         self.register_buffer("_eval_rng_state", torch.tensor([(torch.initial_seed() ^ 0x5DEECE66) & 0x7FFFFFFF, 0, 0],
                                                              dtype=torch.int32), persistent=False)
-        self._eval_draws = False    # latents_for: forward()'s draws come from the evaluation generator
+        self._eval_draws = False    # EvaluationMixin._eval_noise: the draws come from the evaluation generator
 
     def set_likelihood_scales(self):
         """mmvae_base.py:41-47"""
@@ -115,12 +116,17 @@ class TorchMMVAE(nn.Module):
             DropoutState.link(*groups)
 
     # ---- noise ----------------------------------------------------------------------------------
+    def _noise_state(self, evaluation=False):
+        """the generator state a draw comes from -- the one place that decides it: the evaluation generator's inside an
+        evaluation call (`_eval_draws`, or `evaluation`: the caller is one by definition), else the training one's"""
+        return self._eval_rng_state if evaluation or self._eval_draws else self._rng_state
+
     def _draw(self, B, D, device):
         """one standard-normal draw of shape (B, D): replayed from `eps_override` or from the device generator"""
         if self.eps_override is not None:
             e = self.eps_override.pop(0)
             return e.reshape(B, D).to(device=device, dtype=torch.float32).contiguous()
-        return ops.randn((B, D), self._eval_rng_state if self._eval_draws else self._rng_state)
+        return ops.randn((B, D), self._noise_state())
 
     def _draws(self, K, B, D, device):
         """(K, B, D): K consecutive draws of shape (B, D), the K axis forward() hands to the decoders"""
@@ -131,7 +137,7 @@ class TorchMMVAE(nn.Module):
         """n draws of shape (B, D) in one launch (`eps_override`: n consecutive recorded draws)"""
         if self.eps_override is not None:
             return [self._draw(B, D, device) for _ in range(n)]
-        return list(ops.randn((n, B, D), self._rng_state).unbind(0))
+        return list(ops.randn((n, B, D), self._noise_state()).unbind(0))
 
     # ---- tower-level concurrency -------------------------------------------------------------------
     def _tower_streams(self, device, main=0):
@@ -251,471 +257,6 @@ class TorchMMVAE(nn.Module):
     @abc.abstractmethod
     def objective(self, mods):
         pass
-
-    # ---- held-out log-likelihood ---------------------------------------------------------------
-    def _proposal_size(self, n_given):
-        """number of mixture components C of q(z | x_G) for |G| = n_given (mixers with a joint proposal override it)"""
-        raise NotImplementedError(f"{self.modelName}: estimate_log_likelihood has no joint proposal for this mixer "
-                                  f"(poe, moe and mopoe have one; private latents do not)")
-
-    def _proposal(self, mods, given):
-        """-> (comps (C,B,2D) = [loc | scale] of the components of q(z | x_G), C Laplace flags)"""
-        raise NotImplementedError(f"{self.modelName}: estimate_log_likelihood has no joint proposal for this mixer")
-
-    def _given_only(self, mods, given):
-        """the batch with the `data` of every modality outside `given` set to None (masks kept), as the cross-generation
-        calls of forward() take it"""
-        return {m: (mods[m] if m in given else dict(mods[m], data=None)) for m in self.vaes}
-
-    @staticmethod
-    def default_k_chunk(K, C, B):
-        """samples per decoder call: the largest multiple of C that divides K with k_chunk * B <= 1024 rows, at least C
-        (decoder batches stay inside the range the training paths run at, memory does not grow with K)"""
-        best = C
-        for kc in range(C, K + 1, C):
-            if K % kc == 0 and kc * B <= 1024:
-                best = kc
-        return best
-
-    def estimate_log_likelihood(self, mods, K, given=None, targets=None, k_chunk=None, eps=None):
-        """K-sample importance-sampled bound on the held-out log-likelihood, comparable across mixers.
-
-        `given` G (default: every modality whose data is not None) conditions the proposal, `targets` T (default: the
-        same) are the modalities whose likelihood is estimated.
-          proposal  q(z | x_G) = (1/C) sum_c q_c(z), the (loc, scale) pairs this model's forward() / modality_mixing()
-                    hand to Normal / Laplace (the variance-used-as-scale quirk included):
-                    poe: C = 1, the product of the prior expert and the experts of G;  moe: C = |G|, the unimodal
-                    posteriors (Normal | Laplace as `_laplace` says);  mopoe: C = 2^|G| - 1, the subset products;
-          prior     p(z) = Normal(pz_params) = (location, softmax(theta) D);
-          draws     stratified, K % C == 0: sample k comes from component k % C, z[k,b] = loc_c[b] + scale_c[b] eps[k,b];
-          lw0[k,b]  = sum_d log p(z[k,b,d]) - log((1/C) sum_c exp sum_d log q_c(z[k,b,d]));
-          ll_m[k,b] = log p(x_m[b] | z[k,b]) = -recon_rowsum(ltype_m, dec_m(z), x_m), without llik_scaling;
-          joint     = log-mean-exp_k (lw0 + sum_{m in T} ll_m)          <= log p(x_T)        (G = T: the IWAE bound)
-          cond[m]   = log-mean-exp_k ll_m, z ~ q(z | x_G)               (the papers' conditional estimate log p(x_m | x_G))
-          ess       = exp(2 lse_k(w) - lse_k(2 w)) of the joint weights (effective sample size: judge K by it).
-        Returns {"joint": (B,), "cond": {m: (B,)}, "ess": (B,)}, float64.  Needs eval mode (dropout would make the bound
-        meaningless); runs without gradients and leaves the training noise state, dropout counters, gradients and the
-        optimiser alone.  `k_chunk` samples are decoded per call (default_k_chunk); `eps` (K,B,D) replaces the
-        generator (tests).  An optimal_sigma likelihood fits one sigma per decoded (B-row) sample, as the objectives'
-        one-sigma-per-call does, so that the estimate does not depend on k_chunk."""
-        self._proposal_size(0)      # (a mixer without a joint proposal says so before the batch is looked at)
-        names = list(self.vaes.keys())
-        given = [m for m in names if mods[m]["data"] is not None] if given is None else [m for m in names if m in given]
-        targets = list(given) if targets is None else [m for m in names if m in targets]
-        C = self._proposal_size(len(given))
-        if self.training:
-            raise RuntimeError("estimate_log_likelihood needs eval mode (model.eval()): dropout would make the bound "
-                               "meaningless")
-        if not given or not targets or any(mods[m]["data"] is None for m in list(given) + targets):
-            raise ValueError("estimate_log_likelihood: `given` and `targets` must name modalities with data")
-        K = int(K)
-        if K < 1 or K % C != 0:
-            raise ValueError(f"estimate_log_likelihood: K = {K} must be a positive multiple of the proposal's {C} "
-                             f"components (stratified draws)")
-        if len(targets) > ops.H.MOE_MAX_MODS or C > ops.H.MIX_MAX_COMPONENTS:
-            raise NotImplementedError(f"estimate_log_likelihood: {len(targets)} targets / {C} components (up to "
-                                      f"{ops.H.MOE_MAX_MODS} / {ops.H.MIX_MAX_COMPONENTS} are on the MI355X path)")
-        with torch.no_grad():
-            comps, lap = self._proposal(mods, given)
-            _, B, D2 = comps.shape
-            D = D2 // 2
-            kc = self.default_k_chunk(K, C, B) if k_chunk is None else int(k_chunk)
-            if kc < 1 or kc % C != 0 or K % kc != 0:
-                raise ValueError(f"estimate_log_likelihood: k_chunk = {kc} must be a multiple of {C} that divides K = {K}")
-            if eps is not None:
-                eps = eps.to(device=comps.device, dtype=torch.float32).reshape(K, B, D)
-            loc, theta = self._pz_params[0], self._pz_params[1]
-            state = ops.lme_state(len(targets), B, comps.device)
-            for k0 in range(0, K, kc):
-                z, lw0 = ops.mix_ksample_logw(comps, lap, theta, kc, k0, eps=None if eps is None else eps[k0:k0 + kc],
-                                              rng=self._eval_rng_state if eps is None else None,
-                                              advance=k0 + kc == K, prior_loc=loc,
-                                              prior_laplace=self.pz is dist.Laplace)
-                rows = []
-                for m in targets:
-                    vae, mk = self.vaes[m], mods[m]["masks"]
-                    if vae.ltype == "optimal_sigma":
-                        r = torch.cat([recon_rowsum(vae.ltype, vae.dec({"latents": z[k:k + 1], "masks": mk})[0], mods[m])
-                                       for k in range(kc)])
-                    else:
-                        # the kc * B samples as one batch (row k * B + b; the row-sum kernels pair row r with target row
-                        # r % B), text masks repeated -- the form POE.objective decodes its subsets in
-                        out, _ = vae.dec({"latents": z.reshape(1, kc * B, D),
-                                          "masks": None if mk is None else mk.repeat(kc, 1)})
-                        r = recon_rowsum(vae.ltype, out, mods[m], laplace=self._lap(vae))
-                    rows.append(-r.reshape(kc, B))
-                ops.lme_update(state, lw0, rows)
-            out, ess = ops.lme_finish(state, K)
-        return {"joint": out[0], "cond": {m: out[1 + i] for i, m in enumerate(targets)}, "ess": ess}
-
-    # ---- latent classification (DESIGN.md section 7b) ----------------------------------------------------------------
-    def _sample(self, x, K=1, of=None):
-        """Encoders, mixing and draws of forward(x, K), the draws through `_draw` in the reference's order -> (what
-        forward() builds its distributions from, iterable of (modality, z, ...) in modality order: z is what forward()
-        stores under latent_samples[modality]["latents"]).  An iterable that draws while it is read lets forward() decode
-        between the draws, as the reference does.  `of` (latents_for): only that modality's z is wanted."""
-        raise NotImplementedError(f"{self.modelName}: latents_for is not built for this mixer")
-
-    def _latents_of(self, x, of):
-        """forward(x)'s latent_samples[of]["latents"] without the decoders (the iterable is read to its end: its draws)"""
-        return {m: z for m, z, *_ in self._sample(x, of=of)[1]}[of]
-
-    def latents_for(self, mods, given, of=None):
-        """(B, D): the latent sample that forward() stores under latent_samples["latents"] for modality `of` (default:
-        the first of `given`) when only the modalities in `given` carry data -- the tensor the reference's
-        classify_latents reads (eval/eval_mnistsvhn.py:24-67), K = 1 flattened.  DMVAE: its shared code.
-        Encoders and the mixing only: the decoders are skipped.  Needs eval mode; runs without gradients; the noise comes
-        from the evaluation generator (`_eval_rng_state`), so the training noise state, dropout counters, gradients and
-        the optimiser stay as they are.  With `eps_override` the draws are consumed as forward() consumes them and the
-        result equals forward()'s bit for bit."""
-        names = list(self.vaes.keys())
-        given = [m for m in names if m in (given or [])]
-        if self.training:
-            raise RuntimeError("latents_for needs eval mode (model.eval()): dropout would make the latents a function of "
-                               "the masks")
-        if not given or any(m not in mods or mods[m]["data"] is None for m in given):
-            raise ValueError("latents_for: `given` must name modalities with data")
-        of = given[0] if of is None else of
-        if of not in names:
-            raise ValueError(f"latents_for: `of` = {of!r} is not a modality of this model ({names})")
-        self._eval_draws = True
-        try:
-            with torch.no_grad():
-                z = self._latents_of(self._given_only(mods, given), of)
-        finally:
-            self._eval_draws = False
-        return z.reshape(-1, z.shape[-1])
-
-    def default_given(self):
-        """every single modality, then all of them together"""
-        names = list(self.vaes.keys())
-        return [[n] for n in names] + [names]
-
-    def probe_table(self, n_classes, n_attributes, given=None):
-        """-> (given lists in modality order, their keys "+".join(names), [(s, a, C)]): probe p = s * A + a reads the
-        latent matrix of subset s and label column a, with n_classes[a] classes"""
-        names = list(self.vaes.keys())
-        given = self.default_given() if given is None else [list(g) for g in given]
-        for g in given:
-            if not g or any(m not in names for m in g):
-                raise ValueError(f"classify_latents: `given` entry {g} must name modalities of this model ({names})")
-        given = [[m for m in names if m in g] for g in given]
-        A = int(n_attributes)
-        n_classes = [int(n_classes)] * A if isinstance(n_classes, int) else [int(c) for c in n_classes]
-        if len(n_classes) != A:
-            raise ValueError(f"classify_latents: {len(n_classes)} class counts for {A} label columns")
-        for C in n_classes:
-            if not 2 <= C <= ops.H.PROBE_MAX_CLASSES:
-                raise ValueError(f"classify_latents: {C} classes (2 .. {ops.H.PROBE_MAX_CLASSES} are on the MI355X path)")
-        return given, ["+".join(g) for g in given], [(s, a, n_classes[a]) for s in range(len(given)) for a in range(A)]
-
-    @staticmethod
-    def _label_matrix(batches, what, who="classify_latents"):
-        """labels of an iterable of (batch, labels) -> (A, N) int64 on the host; `who` names the caller in the errors"""
-        cols = []
-        for _, y in batches:
-            y = torch.as_tensor(y).detach().cpu()
-            if y.is_floating_point() or y.dim() not in (1, 2):
-                raise ValueError(f"{who}: {what} labels must be an integer (B,) or (B, A) array")
-            cols.append(y.long().reshape(y.shape[0], -1))
-        if not cols:
-            raise ValueError(f"{who}: the {what} set is empty")
-        return torch.cat(cols, 0).t().contiguous()
-
-    def classify_latents(self, train, test, n_classes, given=None, epochs=30, batch_size=128, lr=1e-3, seed=0,
-                         shuffle=False, init=None):
-        """Latent classification (eval/eval_mnistsvhn.py:24-67): one linear probe (nn.Linear + CrossEntropyLoss + Adam)
-        per (conditioning subset, label column), trained on the latents `latents_for` gives for the train set and
-        scored on those of the test set.  `train` / `test`: iterables of (batch dict, labels (B,) or (B, A) ints);
-        `n_classes`: an int or one per label column; `given`: modality-name lists (default_given()).
-        Both sets are encoded once per subset into packed (S, N, D) device matrices; the P = S A probes of probe_table()
-        train side by side, one ops.probe_train launch per epoch (`epochs` passes in minibatches of `batch_size`, in
-        sequential order or, `shuffle`, in per-epoch permutations drawn from torch.Generator(seed)); the init is
-        nn.Linear's from the same seed or the (W, b) pairs of `init`.
-        -> {"accuracy": {(given_key, a): float}, "loss": {(given_key, a): float} (mean test cross-entropy),
-            "pred": {(given_key, a): (N_test,) int32}, "train_loss": (P, steps), "state": ..., "probes": [(s, a, C)]}."""
-        if self.training:
-            raise RuntimeError("classify_latents needs eval mode (model.eval()): dropout would make the latents a function "
-                               "of the masks")
-        D = self.n_latents
-        if D > 256:
-            raise ValueError(f"classify_latents: D = {D} latent dimensions (up to 256 are on the MI355X path)")
-        train, test = list(train), list(test)
-        y_tr, y_te = self._label_matrix(train, "train"), self._label_matrix(test, "test")
-        if y_tr.shape[0] != y_te.shape[0]:
-            raise ValueError(f"classify_latents: {y_tr.shape[0]} train label columns, {y_te.shape[0]} test label columns")
-        A = y_tr.shape[0]
-        given, keys, probes = self.probe_table(n_classes, A, given)
-        if len(probes) > ops.H.PROBE_MAX_PROBES:
-            raise ValueError(f"classify_latents: {len(probes)} probes ({len(given)} subsets x {A} label columns); one launch "
-                             f"trains up to {ops.H.PROBE_MAX_PROBES}")
-        for _, a, C in probes[:A]:
-            for y, what in ((y_tr, "train"), (y_te, "test")):
-                if int(y[a].min()) < 0 or int(y[a].max()) >= C:
-                    raise ValueError(f"classify_latents: {what} label column {a} holds labels in [{int(y[a].min())}, "
-                                     f"{int(y[a].max())}], outside [0, {C})")
-        for batch, _ in train + test:
-            for g in given:
-                if any(m not in batch or batch[m]["data"] is None for m in g):
-                    raise ValueError(f"classify_latents: `given` entry {g} names a modality without data")
-        if int(epochs) < 1 or int(batch_size) < 1:
-            raise ValueError(f"classify_latents: epochs = {epochs}, batch_size = {batch_size}")
-        z_tr = torch.stack([torch.cat([self.latents_for(b, g) for b, _ in train]) for g in given]).contiguous()
-        z_te = torch.stack([torch.cat([self.latents_for(b, g) for b, _ in test]) for g in given]).contiguous()
-        dev = z_tr.device
-        l_tr, l_te = y_tr.to(device=dev, dtype=torch.int32), y_te.to(device=dev, dtype=torch.int32)
-        N, P, Cmax = z_tr.shape[1], len(probes), max(C for _, _, C in probes)
-        state = ops.probe_state(P, D, Cmax, dev, init=init, seed=seed)
-        order = None
-        if shuffle:
-            g = torch.Generator().manual_seed(int(seed))
-            order = torch.stack([torch.randperm(N, generator=g) for _ in range(int(epochs))]).to(device=dev,
-                                                                                                 dtype=torch.int32)
-        spe = (N + int(batch_size) - 1) // int(batch_size)
-        curve = torch.cat([ops.probe_train(state, z_tr, l_tr, probes, batch_size, e * spe, spe, lr=lr, order=order,
-                                           validate=False) for e in range(int(epochs))], 1)
-        pred, nll = ops.probe_eval(state, z_te, l_te, probes)
-        pred, nll = pred.cpu(), nll.cpu().double()
-        out = {"accuracy": {}, "loss": {}, "pred": {}, "train_loss": curve, "state": state, "probes": probes}
-        for p, (s, a, _) in enumerate(probes):
-            k = (keys[s], a)
-            out["accuracy"][k] = int((pred[p].long() == y_te[a]).sum()) / float(y_te.shape[1])
-            out["loss"][k] = float(nll[p].mean())
-            out["pred"][k] = pred[p]
-        return out
-
-    # ---- generation coherence (DESIGN.md section 7c) ------------------------------------------------------------------
-    def _image_text(self, image, text):
-        """names of the image and the text modality: as given, else the modality with 64 x 64 x 3 data and the other one"""
-        names = list(self.vaes.keys())
-        if image is None or text is None:
-            is_img = [m for m in names if tuple(self.vaes[m].data_dim) in ((64, 64, 3), (3, 64, 64))]
-            if len(names) != 2 or len(is_img) != 1:
-                raise ValueError(f"coherence: name the `image` and the `text` modality (this model has {names})")
-            image = is_img[0] if image is None else image
-            text = [m for m in names if m != is_img[0]][0] if text is None else text
-        if image not in names or text not in names or image == text:
-            raise ValueError(f"coherence: image = {image!r}, text = {text!r} are not two modalities of this model ({names})")
-        return image, text
-
-    def _coherence_guard(self, what):
-        if self.training:
-            raise RuntimeError(f"{what} needs eval mode (model.eval()): dropout would make the generations a function of "
-                               f"the masks")
-
-    def cross_coherence(self, batches, classifiers, level, image=None, text=None, eps=None):
-        """Cross-generation coherence of the CdSprites+ benchmark (eval/eval_cdsprites.py: calculate_cross_coherency).
-        `batches`: an iterable of batch dicts holding the image and the one-hot text modality; the captions are read from
-        the batches themselves (argmax of the one-hot rows over the mask's length).  `classifiers`: a
-        coherence.AttributeClassifiers with one classifier per attribute of `level` (1 .. 5).  Per batch two forward()
-        calls: only the text given (the decoded image is quantised to 8 bits and classified: does it show what the
-        caption names?) and only the image given, text masks None so that the caption decodes at full length (its
-        argmax string is compared with the caption letter by letter and attribute by attribute).
-        -> {"text_image": [strict %, features %], "image_text": [strict %, features %, letters %], "per_sample": {...},
-            "captions": [...], "decoded": [...]}; Image->Text strict means "every letter right", as in the reference.
-        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
-        tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
-        dropout counters, gradients and the optimiser stay as they are."""
-        from .. import coherence as coh
-        self._coherence_guard("cross_coherence")
-        classifiers = coh.check_classifiers(classifiers, level)
-        image, text = self._image_text(image, text)
-        per = {"text_image_strict": [], "text_image_features": [], "image_text_strict": [], "image_text_features": [],
-               "image_text_letters": []}
-        captions, decoded = [], []
-        saved = self.eps_override
-        self.eps_override = None if eps is None else [e for e in eps]
-        self._eval_draws = True
-        try:
-            with torch.no_grad():
-                for batch in batches:
-                    if any(m not in batch or batch[m]["data"] is None for m in (image, text)):
-                        raise ValueError("cross_coherence: every batch must hold the image and the text modality")
-                    onehot, masks = batch[text]["data"], batch[text]["masks"]
-                    if onehot.dim() != 3:
-                        raise ValueError(f"cross_coherence: the text modality must be one-hot (B,T,V), got "
-                                         f"{tuple(onehot.shape)}")
-                    B, T, V = onehot.shape
-                    if V > len(coh.ALPHABET):
-                        raise ValueError(f"cross_coherence: {V} symbols, the captions' alphabet has {len(coh.ALPHABET)}")
-                    onehot = onehot.float().contiguous()
-                    ids, _ = ops.text_decode_score(onehot)
-                    lens = (torch.full((B,), T, dtype=torch.int32, device=onehot.device) if masks is None
-                            else torch.count_nonzero(masks.reshape(B, T), dim=-1).to(torch.int32))
-                    caps = [coh.ids_to_text(i, l) for i, l in zip(ids.cpu().tolist(), lens.cpu().tolist())]
-                    # text -> image
-                    out = self.forward(self._given_only(batch, [text]))
-                    x_hat = out.mods[image].decoder_dist.loc
-                    strict, feats, _ = coh.score_images(classifiers, level, x_hat, caps)
-                    per["text_image_strict"] += strict
-                    per["text_image_features"] += feats
-                    # image -> text, decoded at full length
-                    x = self._given_only(batch, [image])
-                    x[text] = dict(x[text], masks=None)
-                    logits = self.forward(x).mods[text].decoder_dist.loc
-                    logits = logits.reshape(-1, *logits.shape[-2:])[:B].float().contiguous()
-                    Td = logits.shape[1]
-                    tgt = ids[:, :Td] if Td <= T else torch.nn.functional.pad(ids, (0, Td - T))
-                    pred, letters = ops.text_decode_score(logits, tgt.contiguous(), lens.contiguous())
-                    pred, letters, lens_h = pred.cpu().tolist(), letters.cpu().tolist(), lens.cpu().tolist()
-                    for n in range(B):
-                        dec = coh.ids_to_text(pred[n])
-                        _, f, _ = coh.score_decoded_text(level, caps[n], dec)
-                        per["image_text_strict"].append(int(lens_h[n] > 0 and letters[n] == lens_h[n]))
-                        per["image_text_features"].append(f)
-                        per["image_text_letters"].append(letters[n] / lens_h[n] if lens_h[n] else 0.0)
-                        decoded.append(dec)
-                    captions += caps
-        finally:
-            self._eval_draws = False
-            self.eps_override = saved
-        if not captions:
-            raise ValueError("cross_coherence: `batches` is empty")
-        return {"text_image": coh.mean_stats([per["text_image_strict"], per["text_image_features"]]),
-                "image_text": coh.mean_stats([per["image_text_strict"], per["image_text_features"],
-                                              per["image_text_letters"]]),
-                "per_sample": per, "captions": captions, "decoded": decoded}
-
-    def joint_coherence(self, classifiers, level, n=64, image=None, text=None, eps=None):
-        """Joint-generation coherence (eval/eval_cdsprites.py: calculate_joint_coherency): n latents z ~ p(z) =
-        Normal(*pz_params), both modalities decoded from the SAME z (text at full length), the attributes read from the
-        decoded caption at their word positions ("Unknown" never matches) and compared with what the classifiers see in
-        the decoded image.  (The reference draws every modality's latents on its own, from that VAE's N(0, I) --
-        vae.generate_samples once per modality in trainer.save_joint_samples --, so that its image and caption do not
-        share a sample; the metric's definition, one prior sample for both, is what is computed here.)
-        -> {"joint": [strict %, features %], "per_sample": {...}, "decoded": [...], "attributes": [...]}.
-        Needs eval mode; runs without gradients; the draw comes from the evaluation generator, or is `eps` (n, D).
-        Models with private latents (DMVAE) have no joint prior sample to decode: NotImplementedError."""
-        from .. import coherence as coh
-        self._coherence_guard("joint_coherence")
-        if self.latent_factorization:
-            raise NotImplementedError(f"{self.modelName}: joint_coherence is built for the mixers with one shared latent "
-                                      f"space (poe, moe, mopoe); private latents have no joint prior sample")
-        classifiers = coh.check_classifiers(classifiers, level)
-        image, text = self._image_text(image, text)
-        n = int(n)
-        if n < 1:
-            raise ValueError(f"joint_coherence: n = {n}")
-        with torch.no_grad():
-            loc, scale = self.pz_params
-            D = self.n_latents
-            if eps is None:
-                e = ops.randn((n, D), self._eval_rng_state)
-            else:
-                e = eps.to(device=loc.device, dtype=torch.float32).reshape(n, D)
-            z = (loc + scale * e).unsqueeze(0).contiguous()
-            x_hat = self.vaes[image].dec({"latents": z, "masks": None})[0]
-            logits = self.vaes[text].dec({"latents": z, "masks": None})[0]
-            logits = logits.reshape(-1, *logits.shape[-2:]).float().contiguous()
-            pred, _ = ops.text_decode_score(logits)
-            decoded = [coh.ids_to_text(p) for p in pred.cpu().tolist()]
-            atts = [coh.retrieve_attributes(t, level) for t in decoded]
-            strict, feats, _ = coh.score_images(classifiers, level, x_hat, atts)
-        return {"joint": coh.mean_stats([strict, feats]), "per_sample": {"joint_strict": strict, "joint_features": feats},
-                "decoded": decoded, "attributes": atts}
-
-    # ---- MNIST-SVHN digit coherence (DESIGN.md section 7d) ------------------------------------------------------------
-    def _mnist_svhn(self, mnist, svhn):
-        """names of the MNIST and the SVHN modality: as given, else the ones with 28 x 28 x 1 / 32 x 32 x 3 data"""
-        names = list(self.vaes.keys())
-        out = []
-        for given, dims, what in ((mnist, ((28, 28, 1), (1, 28, 28)), "mnist"), (svhn, ((32, 32, 3), (3, 32, 32)), "svhn")):
-            if given is None:
-                hit = [m for m in names if tuple(self.vaes[m].data_dim) in dims]
-                if len(hit) != 1:
-                    raise ValueError(f"digit coherence: name the `{what}` modality (this model has {names})")
-                given = hit[0]
-            out.append(given)
-        if out[0] not in names or out[1] not in names or out[0] == out[1]:
-            raise ValueError(f"digit coherence: mnist = {out[0]!r}, svhn = {out[1]!r} are not two modalities of this model "
-                             f"({names})")
-        return out
-
-    @staticmethod
-    def _digit_classifiers(classifiers):
-        from .. import coherence as coh
-        if not isinstance(classifiers, coh.DigitClassifiers):
-            raise TypeError("digit coherence: `classifiers` must be a coherence.DigitClassifiers")
-        return classifiers
-
-    def digit_cross_coherence(self, batches, classifiers, mnist=None, svhn=None, eps=None, reconstruct=False):
-        """Cross-generation coherence of the MNIST-SVHN benchmark (eval/eval_mnistsvhn.py:122-154).  `batches`: an
-        iterable of (batch dict, digit labels (B,) ints); `classifiers`: a trained coherence.DigitClassifiers.  Per batch
-        two forward() calls: only SVHN given -- the decoded MNIST image is classified -- and only MNIST given -- the
-        decoded SVHN image, permuted back to NCHW, is classified; a sample counts when the classifier reads the batch's
-        label.  That is the metric as defined.  The reference's code builds the two one-modality copies of the batch and
-        then forwards the FULL batch both times (lines 134-140), so that it scores reconstructions; `reconstruct=True`
-        does that literally.
-        -> {"svhn_mnist": %, "mnist_svhn": %, "per_sample": {"svhn_mnist": [0/1], "mnist_svhn": [0/1]},
-            "pred": {"svhn_mnist": (N,) int32, "mnist_svhn": (N,) int32}, "labels": (N,) int64}.
-        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
-        tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
-        dropout counters, gradients and the optimiser stay as they are."""
-        self._coherence_guard("digit_cross_coherence")
-        classifiers = self._digit_classifiers(classifiers)
-        mnist, svhn = self._mnist_svhn(mnist, svhn)
-        batches = list(batches)
-        if not batches:
-            raise ValueError("digit_cross_coherence: `batches` is empty")
-        y = self._label_matrix(batches, "test", "digit_cross_coherence")
-        if y.shape[0] != 1 or int(y.min()) < 0 or int(y.max()) >= 10:
-            raise ValueError("digit_cross_coherence: one digit label in [0, 10) per sample")
-        pred = {"svhn_mnist": [], "mnist_svhn": []}
-        saved = self.eps_override
-        self.eps_override = None if eps is None else [e for e in eps]
-        self._eval_draws = True
-        try:
-            with torch.no_grad():
-                for batch, _ in batches:
-                    if any(m not in batch or batch[m]["data"] is None for m in (mnist, svhn)):
-                        raise ValueError("digit_cross_coherence: every batch must hold the MNIST and the SVHN modality")
-                    B = batch[mnist]["data"].shape[0]
-                    out = self.forward(batch if reconstruct else self._given_only(batch, [svhn]))
-                    x_m = classifiers.mnist.images(out.mods[mnist].decoder_dist.loc)[:B]
-                    pred["svhn_mnist"].append(classifiers.predict(x_mnist=x_m)["mnist"])
-                    out = self.forward(batch if reconstruct else self._given_only(batch, [mnist]))
-                    x_s = classifiers.svhn.images(out.mods[svhn].decoder_dist.loc)[:B]
-                    pred["mnist_svhn"].append(classifiers.predict(x_svhn=x_s)["svhn"])
-        finally:
-            self._eval_draws = False
-            self.eps_override = saved
-        pred = {k: torch.cat(v).cpu() for k, v in pred.items()}
-        per = {k: (v.long() == y[0]).int().tolist() for k, v in pred.items()}
-        return {"svhn_mnist": 100.0 * sum(per["svhn_mnist"]) / y.shape[1],
-                "mnist_svhn": 100.0 * sum(per["mnist_svhn"]) / y.shape[1], "per_sample": per, "pred": pred, "labels": y[0]}
-
-    def digit_joint_coherence(self, classifiers, n=1000, eps=None, mnist=None, svhn=None):
-        """Joint-generation coherence of the MNIST-SVHN benchmark (eval/eval_mnistsvhn.py:157-180): n latents z ~ p(z) =
-        Normal(*pz_params), both images decoded from the SAME z, the score is the share of samples in which the two digit
-        classifiers read the same digit.  The decoded SVHN image (n,32,32,3) is permuted back to (n,3,32,32); the
-        reference RESHAPES it instead (`.reshape(-1,3,32,32)`, line 170), which hands its classifier scrambled pixels --
-        the metric's definition is what is computed here.
-        -> {"joint": %, "per_sample": [0/1], "pred": {"mnist": (n,) int32, "svhn": (n,) int32}}.
-        Needs eval mode; runs without gradients; the draw comes from the evaluation generator, or is `eps` (n, D).
-        Models with private latents (DMVAE) have no joint prior sample to decode: NotImplementedError."""
-        self._coherence_guard("digit_joint_coherence")
-        if self.latent_factorization:
-            raise NotImplementedError(f"{self.modelName}: digit_joint_coherence is built for the mixers with one shared "
-                                      f"latent space (poe, moe, mopoe); private latents have no joint prior sample")
-        classifiers = self._digit_classifiers(classifiers)
-        mnist, svhn = self._mnist_svhn(mnist, svhn)
-        n = int(n)
-        if n < 1:
-            raise ValueError(f"digit_joint_coherence: n = {n}")
-        with torch.no_grad():
-            loc, scale = self.pz_params
-            D = self.n_latents
-            if eps is None:
-                e = ops.randn((n, D), self._eval_rng_state)
-            else:
-                e = eps.to(device=loc.device, dtype=torch.float32).reshape(n, D)
-            z = (loc + scale * e).unsqueeze(0).contiguous()
-            x_m = self.vaes[mnist].dec({"latents": z, "masks": None})[0]
-            x_s = self.vaes[svhn].dec({"latents": z, "masks": None})[0]
-            pred = classifiers.predict(x_mnist=x_m, x_svhn=x_s)
-        pred = {k: v.cpu() for k, v in pred.items()}
-        same = (pred["mnist"] == pred["svhn"]).int().tolist()
-        return {"joint": 100.0 * sum(same) / n, "per_sample": same, "pred": pred}
 
     def product_of_experts(self, mu, logvar, with_prior=False):
         """mmvae_base.py:203-222 on the fused kernel: mu/logvar are lists of (B,D) tensors; returns

@@ -127,60 +127,56 @@ class MultimodalVAE(nn.Module):
         self._log_losses(loss_d, "test", "Test")
         return loss_d["loss"]
 
+    def _log_metrics(self, pairs):
+        """(name, value) pairs of an evaluation metric, logged with the config's batch size (floats as float64 tensors)"""
+        for name, v in pairs:
+            self.log(name, v if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float64),
+                     batch_size=self.config.batch_size)
+
     def estimate_log_likelihood(self, batch, K, given=None, targets=None, k_chunk=None, eps=None):
         """held-out log-likelihood of `batch` (TorchMMVAE.estimate_log_likelihood: importance-sampled, K samples,
         comparable across mixers; the model must be in eval mode), logged as test_loglik_joint and test_loglik_mod_<i>
         (batch means; i = the modality's position, as in Mod_<i>_TestLoss)"""
         out = self.model.estimate_log_likelihood(batch, K, given=given, targets=targets, k_chunk=k_chunk, eps=eps)
-        self.log("test_loglik_joint", out["joint"].mean(), batch_size=self.config.batch_size)
         names = list(self.model.vaes.keys())
-        for m, v in out["cond"].items():
-            self.log("test_loglik_mod_{}".format(names.index(m)), v.mean(), batch_size=self.config.batch_size)
+        self._log_metrics([("test_loglik_joint", out["joint"].mean())] +
+                          [("test_loglik_mod_{}".format(names.index(m)), v.mean()) for m, v in out["cond"].items()])
         return out
 
     def classify_latents(self, train, test, n_classes, **kwargs):
         """latent classification accuracy (TorchMMVAE.classify_latents: one linear probe per conditioning subset and
         label column, trained on chip; the model must be in eval mode), logged as test_latent_acc_<given_key>_<a>"""
         out = self.model.classify_latents(train, test, n_classes, **kwargs)
-        for (key, a), acc in out["accuracy"].items():
-            self.log("test_latent_acc_{}_{}".format(key, a), torch.tensor(acc, dtype=torch.float64),
-                     batch_size=self.config.batch_size)
+        self._log_metrics(("test_latent_acc_{}_{}".format(key, a), acc) for (key, a), acc in out["accuracy"].items())
         return out
 
     def cross_coherence(self, batches, classifiers, level, **kwargs):
         """cross-generation coherence (TorchMMVAE.cross_coherence; the model must be in eval mode), logged as
         test_coherence_text_image_{strict,features} and test_coherence_image_text_{strict,features,letters}"""
         out = self.model.cross_coherence(batches, classifiers, level, **kwargs)
-        for key, names in (("text_image", ("strict", "features")), ("image_text", ("strict", "features", "letters"))):
-            for name, v in zip(names, out[key]):
-                self.log("test_coherence_{}_{}".format(key, name), torch.tensor(v, dtype=torch.float64),
-                         batch_size=self.config.batch_size)
+        self._log_metrics(("test_coherence_{}_{}".format(key, name), v) for key in ("text_image", "image_text")
+                          for name, v in zip(("strict", "features", "letters"), out[key]))
         return out
 
     def joint_coherence(self, classifiers, level, **kwargs):
         """joint-generation coherence (TorchMMVAE.joint_coherence; the model must be in eval mode), logged as
         test_coherence_joint_{strict,features}"""
         out = self.model.joint_coherence(classifiers, level, **kwargs)
-        for name, v in zip(("strict", "features"), out["joint"]):
-            self.log("test_coherence_joint_{}".format(name), torch.tensor(v, dtype=torch.float64),
-                     batch_size=self.config.batch_size)
+        self._log_metrics(("test_coherence_joint_{}".format(name), v) for name, v in zip(("strict", "features"), out["joint"]))
         return out
 
     def digit_cross_coherence(self, batches, classifiers, **kwargs):
         """MNIST-SVHN cross-generation coherence (TorchMMVAE.digit_cross_coherence; the model must be in eval mode), logged
         as test_coherence_svhn_mnist and test_coherence_mnist_svhn"""
         out = self.model.digit_cross_coherence(batches, classifiers, **kwargs)
-        for key in ("svhn_mnist", "mnist_svhn"):
-            self.log("test_coherence_{}".format(key), torch.tensor(out[key], dtype=torch.float64),
-                     batch_size=self.config.batch_size)
+        self._log_metrics(("test_coherence_{}".format(key), out[key]) for key in ("svhn_mnist", "mnist_svhn"))
         return out
 
     def digit_joint_coherence(self, classifiers, **kwargs):
         """MNIST-SVHN joint-generation coherence (TorchMMVAE.digit_joint_coherence; the model must be in eval mode),
         logged as test_coherence_digit_joint"""
         out = self.model.digit_joint_coherence(classifiers, **kwargs)
-        self.log("test_coherence_digit_joint", torch.tensor(out["joint"], dtype=torch.float64),
-                 batch_size=self.config.batch_size)
+        self._log_metrics([("test_coherence_digit_joint", out["joint"])])
         return out
 
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------

@@ -31,6 +31,19 @@ class DencoderFactory(object):
         return enc_obj, dec_obj
 
 
+# the evaluation metrics of TorchMMVAE (models/evaluation.py) -> whom each is built for: a unimodal VAE refuses them by name
+MIXER_METRICS = dict.fromkeys(("latents_for", "classify_latents", "cross_coherence", "joint_coherence",
+                               "digit_cross_coherence", "digit_joint_coherence"), "the multimodal mixers")
+MIXER_METRICS["estimate_log_likelihood"] = "the multimodal mixers poe, moe and mopoe"
+
+
+def _mixers_only(name, whom):
+    def stub(self, *args, **kwargs):
+        raise NotImplementedError(f"unimodal VAE: {name} is built for {whom} (TorchMMVAE.{name})")
+    stub.__name__ = name
+    return stub
+
+
 class BaseVae(nn.Module):
     """vae.py:33-59"""
 
@@ -99,33 +112,6 @@ class VAE(BaseVae):
         return self._pz_params_private[0], \
             F.softmax(self._pz_params_private[1], dim=1) * self._pz_params_private[1].size(-1)
 
-    def estimate_log_likelihood(self, *args, **kwargs):
-        raise NotImplementedError("unimodal VAE: estimate_log_likelihood is built for the multimodal mixers poe, moe and "
-                                  "mopoe (TorchMMVAE.estimate_log_likelihood)")
-
-    def latents_for(self, *args, **kwargs):
-        raise NotImplementedError("unimodal VAE: latents_for is built for the multimodal mixers (TorchMMVAE.latents_for)")
-
-    def classify_latents(self, *args, **kwargs):
-        raise NotImplementedError("unimodal VAE: classify_latents is built for the multimodal mixers "
-                                  "(TorchMMVAE.classify_latents)")
-
-    def cross_coherence(self, *args, **kwargs):
-        raise NotImplementedError("unimodal VAE: cross_coherence is built for the multimodal mixers "
-                                  "(TorchMMVAE.cross_coherence)")
-
-    def joint_coherence(self, *args, **kwargs):
-        raise NotImplementedError("unimodal VAE: joint_coherence is built for the multimodal mixers "
-                                  "(TorchMMVAE.joint_coherence)")
-
-    def digit_cross_coherence(self, *args, **kwargs):
-        raise NotImplementedError("unimodal VAE: digit_cross_coherence is built for the multimodal mixers "
-                                  "(TorchMMVAE.digit_cross_coherence)")
-
-    def digit_joint_coherence(self, *args, **kwargs):
-        raise NotImplementedError("unimodal VAE: digit_joint_coherence is built for the multimodal mixers "
-                                  "(TorchMMVAE.digit_joint_coherence)")
-
     # ---- the unimodal case: `self.model = vaes["mod_1"]` (models/trainer.py:112-113) ------------------------------
     def objective(self, data):
         """VAE.forward + objective with UnimodalObjective.elbo (models/vae.py:92-119,268-282, models/objectives.py:233-247):
@@ -156,3 +142,7 @@ class VAE(BaseVae):
         rec = recon_rowsum(self.ltype, out, x)
         loss = ops.lincomb_rows([rec, kl[1]], [[1.0, float(B) * float(self.beta)]])
         return {"loss": loss[0], "kld": kl[1], "reconstruction_loss": -rec}
+
+
+for _name, _whom in MIXER_METRICS.items():
+    setattr(VAE, _name, _mixers_only(_name, _whom))

@@ -3107,6 +3107,46 @@ def lme_finish(state, K):
     return out, ess
 
 
+# ---- host helpers of the evaluation metrics: labels, and the minibatch `order` of probe_train / digit_train -------------------
+def label_matrix(batches, what, who):
+    """labels of an iterable of (batch, labels) -> (A, N) int64 on the host; `who` names the caller in the errors"""
+    cols = []
+    for _, y in batches:
+        y = torch.as_tensor(y).detach().cpu()
+        if y.is_floating_point() or y.dim() not in (1, 2):
+            raise ValueError(f"{who}: {what} labels must be an integer (B,) or (B, A) array")
+        cols.append(y.long().reshape(y.shape[0], -1))
+    if not cols:
+        raise ValueError(f"{who}: the {what} set is empty")
+    return torch.cat(cols, 0).t().contiguous()
+
+
+def epoch_orders(N, epochs, seed, device, shuffle=True):
+    """the `order` argument of probe_train / digit_train: (epochs, N) int32 on `device`, one permutation of the N rows per
+    epoch drawn from torch.Generator(seed); None -- sequential minibatches -- when not shuffling"""
+    if not shuffle:
+        return None
+    g = torch.Generator().manual_seed(int(seed))
+    return torch.stack([torch.randperm(N, generator=g) for _ in range(int(epochs))]).to(device=device, dtype=torch.int32)
+
+
+def _check_order(who, order, N, batch, step0, n_steps, validate, check_labels):
+    """`order` of probe_train / digit_train: (E,N) contiguous int32, E epochs enough for the steps [step0, step0 + n_steps);
+    under `validate` the caller's `check_labels()`, then every entry a row in [0, N).  -> E (0: sequential, no `order`)"""
+    E = 0
+    if order is not None:
+        assert order.dim() == 2 and order.dtype == torch.int32 and order.is_contiguous() and order.shape[1] == N
+        E = order.shape[0]
+        spe = (N + batch - 1) // batch
+        if (step0 + n_steps - 1) // spe >= E:
+            raise ValueError(f"{who}: steps up to {step0 + n_steps} need more than the {E} epochs of `order`")
+    if validate:
+        check_labels()
+        if order is not None and (int(order.min()) < 0 or int(order.max()) >= N):
+            raise ValueError(f"{who}: `order` holds rows outside [0, N)")
+    return E
+
+
 # ---- latent classification (csrc/probe.hip): linear probes trained on chip, forward only, no autograd ---------------------
 def _probe_table(probes, Cmax):
     """[(s, a, C)] -> the host (P,3) int table of the C ABI.  The class counts are checked here (ValueError names them);
@@ -3185,17 +3225,8 @@ def probe_train(state, z, labels, probes, batch, step0, n_steps, lr=1e-3, order=
     assert labels.dim() == 2 and labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape[1] == N
     if int(batch) < 1 or int(n_steps) < 1 or int(step0) < 0:
         raise ValueError(f"probe_train: batch = {batch}, step0 = {step0}, n_steps = {n_steps}")
-    E = 0
-    if order is not None:
-        assert order.dim() == 2 and order.dtype == torch.int32 and order.is_contiguous() and order.shape[1] == N
-        E = order.shape[0]
-        spe = (N + int(batch) - 1) // int(batch)
-        if (int(step0) + int(n_steps) - 1) // spe >= E:
-            raise ValueError(f"probe_train: steps up to {int(step0) + int(n_steps)} need more than the {E} epochs of `order`")
-    if validate:
-        probe_check_labels(labels, probes)
-        if order is not None and (int(order.min()) < 0 or int(order.max()) >= N):
-            raise ValueError("probe_train: `order` holds rows outside [0, N)")
+    E = _check_order("probe_train", order, N, int(batch), int(step0), int(n_steps), validate,
+                     lambda: probe_check_labels(labels, probes))
     for s, a, C in probes:
         if not (0 <= s < S and 0 <= a < labels.shape[0]):
             raise ValueError(f"probe table: probe ({s}, {a}, {C}) outside {S} latent matrices / {labels.shape[0]} label rows")
@@ -3429,17 +3460,7 @@ def digit_train(state, kinds, images, labels, batch, step0, n_steps, lr=1e-3, se
     batch, step0, n_steps = int(batch), int(step0), int(n_steps)
     if not 1 <= batch <= 65535 or n_steps < 1 or step0 < 0 or N < 1:
         raise ValueError(f"digit_train: batch = {batch}, step0 = {step0}, n_steps = {n_steps}, N = {N}")
-    E = 0
-    if order is not None:
-        assert order.dim() == 2 and order.dtype == torch.int32 and order.is_contiguous() and order.shape[1] == N
-        E = order.shape[0]
-        spe = (N + batch - 1) // batch
-        if (step0 + n_steps - 1) // spe >= E:
-            raise ValueError(f"digit_train: steps up to {step0 + n_steps} need more than the {E} epochs of `order`")
-    if validate:
-        digit_check_labels(labels)
-        if order is not None and (int(order.min()) < 0 or int(order.max()) >= N):
-            raise ValueError("digit_train: `order` holds rows outside [0, N)")
+    E = _check_order("digit_train", order, N, batch, step0, n_steps, validate, lambda: digit_check_labels(labels))
     nets, stride, dev = len(kinds), state.shape[2], state.device
     ws = H.workspace(H.lib().mmvae_digit_ws_floats(nets, batch, stride), dev)
     loss = torch.empty(nets, n_steps, device=dev)
