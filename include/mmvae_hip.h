@@ -293,7 +293,8 @@ int mmvae_head_softmax_bwd(const float* h, float* dh, int B, int D, mmvae_stream
  *                  inside PoE.  eps, z, dz are contiguous (B,D).
  *   with_prior   : 0 = product of the experts only; 1 = add the N(0,1) expert (mu 0, logvar 0);
  *                  2 = no product (E must be 1): the "joint" is expert 0 itself with sigma = its lv -- the
- *                  per-modality posteriors of MoE (models/mmvae_models.py:96-100).
+ *                  per-modality posteriors of MoE (models/mmvae_models.py:96-100).  Not with raw_heads
+ *                  (MMVAE_ERR_ARG, both directions): lv_0 is the scale as it stands.
  *   n_z draws    : z[i] = mu_J + var_J * eps[i]   (eps[i], z[i] : (B,D))
  *   kl (n_kl,B)  : row j < E: sum_d KL(N(mu_j, sigma=lv_j) || p) if kl_mask bit j set;
  *                  row E    : sum_d KL(N(mu_J, sigma=var_J) || p) if kl_mask bit E set; p = N(0, softmax(theta)*D)

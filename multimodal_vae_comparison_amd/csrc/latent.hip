@@ -317,7 +317,9 @@ __global__ __launch_bounds__(256) void poe_bwd_kernel(mmvae_poe_bwd_args a, cons
           if (d < D) {
             const size_t oi = (size_t)b * ld + d;
             const float sv = expf(a.lv[e][oi] - umx[e]) * uinv[e];
-            a.dlv[e][oi] = sv * (a.dlv[e][oi] - dot);
+            // (D == 1: the softmax of one logit is the constant 1 and du is 0; s = lv - 1e-6 in `dot` is rounded, and
+            // s (dlv - s dlv) came out as 6e-8 dlv)
+            a.dlv[e][oi] = D == 1 ? 0.f : sv * (a.dlv[e][oi] - dot);
           }
         }
       }
@@ -584,7 +586,7 @@ __global__ __launch_bounds__(256) void poe_bwd_fast_kernel(mmvae_poe_bwd_args a,
     for (int e = 0; e < E; ++e) {
       if (raw) {      // through lv = softmax(u) + 1e-6:  du = s (dlv - sum(s dlv)),  s = lv - 1e-6
         const float dot = wave_sum(live ? (lv[e] - 1e-6f) * dlv[e] : 0.f);
-        dlv[e] = sv[e] * (dlv[e] - dot);
+        dlv[e] = D == 1 ? 0.f : sv[e] * (dlv[e] - dot);      // (one column: du is 0, see poe_bwd_kernel)
       }
       if (live) a.dlv[e][oi] = ((acc_packed >> e) & 1u) ? a.dlv[e][oi] + dlv[e] : dlv[e];
     }
@@ -626,6 +628,9 @@ extern "C" int mmvae_poe_reparam_kl_fwd(const mmvae_poe_fwd_args* a, const float
   MMVAE_CHECK_ARG(a && theta && joint && B > 0 && D > 0 && E > 0 && ld_in >= D);
   if (E > MMVAE_MAX_EXPERTS || n_z > MMVAE_MAX_EXPERTS || D > 64 * POE_SLOTS) return MMVAE_ERR_UNSUPPORTED;
   if (with_prior == 2 && E != 1) return MMVAE_ERR_ARG;
+  // (the pass-through posterior takes lv_0 as its scale as it stands: a raw logit is none, and the forward kernels would
+  // read the logit where the backward kernels read its softmax)
+  if (with_prior == 2 && raw_heads) return MMVAE_ERR_ARG;
   if (kl_mask && !kl) return MMVAE_ERR_ARG;
   if (!poe_fast_visit(E, n_z, D, [&](auto e, auto z) {
         hipLaunchKernelGGL((poe_fwd_fast_kernel<decltype(e)::value, decltype(z)::value>), dim3(poe_blocks(B)), dim3(256),
@@ -650,6 +655,7 @@ extern "C" int mmvae_poe_reparam_kl_bwd_acc(const mmvae_poe_bwd_args* a, const f
                                             unsigned acc_packed, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(a && theta && ws && B > 0 && D > 0 && E > 0 && ld_in >= D);
   if (acc_packed && raw_heads) return MMVAE_ERR_ARG;      // (the raw-head form uses the gradient tensor as scratch)
+  if (with_prior == 2 && (E != 1 || raw_heads)) return MMVAE_ERR_ARG;      // (as the forward entry)
   if (E > MMVAE_MAX_EXPERTS || n_z > MMVAE_MAX_EXPERTS || D > 64 * POE_SLOTS) return MMVAE_ERR_UNSUPPORTED;
   const int nb = poe_blocks(B);
   const bool one_launch = dtheta && ticket;

@@ -1456,6 +1456,7 @@ def poe_reparam_kl(theta, packed, eps, with_prior, kl_mask, gtheta=None, cols=No
     eps: the n_z noise tensors, or -- with rng = the device generator state (ops.randn) -- their NUMBER: the fusion
     kernel then draws them itself (same values as ops.randn((n_z, B, D), rng))"""
     assert not (raw and cols is not None), "raw heads: the softmax runs over the full head width"
+    assert not (raw and int(with_prior) == 2), "raw heads: the pass-through posterior (with_prior = 2) takes lv as its scale"
     if rng is not None:
         out = PoeReparamKL.apply(theta, gtheta, with_prior, int(eps), kl_mask, len(packed), cols, raw, rng, *packed)
     else:

@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import poe_reference as PR
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -436,31 +438,13 @@ def test_head_softmax(ops):
     check(hg.grad, hr.grad, 1e-5, "dh")
 
 
-def _poe_ref(theta, packed, eps, with_prior, kl_mask):
-    D = theta.shape[1]
-    sp = F.softmax(theta, dim=1) * D
-    mus = [p[:, :D] for p in packed]
-    lvs = [p[:, D:] for p in packed]
-    T = [1.0 / (torch.exp(l) + 1e-8) for l in lvs]
-    P = sum(T) + (1.0 / (1.0 + 1e-8) if with_prior else 0.0)
-    muJ = sum(m * t for m, t in zip(mus, T)) / P
-    varJ = 1.0 / P
-
-    def kl(mu, s):
-        vr = (s / sp) ** 2
-        return (0.5 * (vr + (mu / sp) ** 2 - 1 - vr.log())).sum(-1)
-
-    E = len(packed)
-    rows = [kl(m, l) if kl_mask >> e & 1 else torch.zeros(m.shape[0], dtype=m.dtype) for e, (m, l) in enumerate(zip(mus, lvs))]
-    rows.append(kl(muJ, varJ) if kl_mask >> E & 1 else torch.zeros(muJ.shape[0], dtype=muJ.dtype))
-    z = torch.stack([muJ + varJ * e for e in eps]) if eps else torch.zeros(0, *muJ.shape)
-    return torch.stack([muJ, varJ]), torch.stack(rows), z
-
-
 @pytest.mark.parametrize("E,n_z,with_prior,kl_mask,B,D", [(2, 2, True, 0b111, 128, 32), (1, 1, True, 0b10, 7, 8),
                                                           (3, 3, True, 0b1111, 130, 42), (2, 0, False, 0, 5, 16),
                                                           (2, 1, True, 0b100, 300, 70)])
 def test_poe_reparam_kl(ops, E, n_z, with_prior, kl_mask, B, D):
+    """against the float64 restatement of tests/poe_reference.py, part by part (joint mean and variance, each KL row, each
+    z_i, each expert's dmu and dlv half, dtheta: every one on its own maximum); tests/test_poe_fusion_gpu.py holds the
+    rest of the op's forms"""
     g = torch.Generator().manual_seed(E * 100 + B)
     packed = [torch.cat([torch.randn(B, D, generator=g), F.softmax(torch.randn(B, D, generator=g), -1) + 1e-6], -1)
               for _ in range(E)]
@@ -468,25 +452,18 @@ def test_poe_reparam_kl(ops, E, n_z, with_prior, kl_mask, B, D):
     theta = torch.randn(1, D, generator=g) * 0.3
     gkl = torch.randn(E + 1, B, generator=g)
     gz = torch.randn(n_z, B, D, generator=g)
-    pr = [p.double().requires_grad_(True) for p in packed]
-    tr = theta.double().requires_grad_(True)
-    jr, klr, zr = _poe_ref(tr, pr, [e.double() for e in eps], with_prior, kl_mask)
-    tot = (klr * gkl.double()).sum() + ((zr * gz.double()).sum() if n_z else 0.0)
+    c = PR.Case(f"E{E}-nz{n_z}-D{D}-B{B}", E, n_z, D, B, int(with_prior), kl_mask)
+    ref = PR.run_reference(c, {"heads": packed, "eps": eps, "theta": theta, "gkl": gkl, "gz": gz})
     pg = [p.to(DEV).requires_grad_(True) for p in packed]
     tg = theta.to(DEV).requires_grad_(True)
     j, kl, z = ops.poe_reparam_kl(tg, pg, [e.to(DEV) for e in eps], with_prior, kl_mask)
-    check(j, jr, 1e-5, "joint")
-    check(kl, klr, 2e-5, "kl")
-    if n_z:
-        check(torch.stack(z), zr, 1e-5, "z")
+    parts = PR.Parts(c.name)
+    PR.check_forward(parts, c, j, kl, z, ref)
     if kl_mask or n_z:
-        tot.backward()
         totg = (kl * gkl.to(DEV)).sum() + ((torch.stack(z) * gz.to(DEV)).sum() if n_z else 0.0)
         totg.backward()
-        for e in range(E):
-            check(pg[e].grad, pr[e].grad, 5e-5, f"dpacked[{e}]")
-        if kl_mask:
-            check(tg.grad, tr.grad, 5e-5, "dtheta")
+        PR.check_backward(parts, c, [p.grad for p in pg], tg.grad if kl_mask else None, ref)
+    parts.done()
 
 
 @pytest.mark.parametrize("n_z,B,D", [(2, 128, 32), (3, 7, 9)])
