@@ -912,6 +912,45 @@ int mmvae_digit_masks(float* m2d, float* m1, int kind, unsigned seed, long step0
                       mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Latent analysis (TorchMMVAE.analyse_latents; csrc/tsne.hip): the exact t-SNE embedding of the latent samples, which the
+ * reference draws with sklearn.manifold.TSNE on 250 samples per modality (visualization.py: t_sne, called from
+ * models/trainer.py:242-272).  The arithmetic is scikit-learn's method="exact" path; eps = 2.220446049250313e-16.
+ *   mmvae_tsne_sqdist: D2 (N,N) fp32, D2[i,j] = sum_d (x_id - x_jd)^2 summed directly in double (no Gram trick) and
+ *     rounded to fp32; zero diagonal, symmetric bit for bit.
+ *   mmvae_tsne_joint_p: per row the binary search of _binary_search_perplexity in double (beta = 1, bracket (-inf, inf),
+ *     at most 100 steps; p_j = exp(-D2[i,j] beta), s = sum_{j != i} p_j, s = 1e-8 if s == 0, H = log s + beta sum_j D2[i,j]
+ *     p_j / s, stop at |H - log perplexity| <= 1e-5, else double / halve beta or take the midpoint of the bracket);
+ *     info (N,4) doubles = the beta the returned row was computed with, its s, sum_j p_j / s, the steps taken.
+ *     P (N, ldp) fp32, ldp = mmvae_tsne_ld(N) (N rounded up to 4; the pad columns are written 0):
+ *     P_ij = max((c_ij + c_ji) / max(sum, eps), eps), c_ij = p_j / s of row i, P_ii = 0; sum = 2 sum_i info[i,2] reduced in a
+ *     fixed order into total[0].  Symmetric bit for bit.
+ *   One iteration `it` (0-based): ex = 12, momentum 0.5 for it < switch_it (scikit-learn: 250), then 1 and 0.8;
+ *     w_ij = 1 / (1 + |y_i - y_j|^2), Z = sum_{i != j} w_ij, g_i = 4 sum_j (ex P_ij - w_ij / Z) w_ij (y_i - y_j),
+ *     KL = sum_{i != j} ex P_ij log(max(ex P_ij, eps) Z / w_ij); gains += 0.2 where upd g < 0, *= 0.8 elsewhere, >= 0.01;
+ *     upd = momentum upd - lr gains g; y += upd.  (Q_ij = w_ij / Z without scikit-learn's clamp at eps: the two differ
+ *     only for pairs with w_ij / Z < eps.)  Pair terms in fp32, every sum over pairs accumulated in double.
+ *   state (3,N,2) fp32 = Y | upd | gains; ws: mmvae_tsne_ws_doubles(N) doubles, private to the call until it has run.
+ *   mmvae_tsne_forces: the first half of iteration `it`: g (N,2) fp32, kz = (KL, Z) doubles; the state is not written.
+ *   mmvae_tsne_run: the iterations [it0, it0 + n_iter), two launches each; log (n_iter,2) doubles = (KL, |g|_2) of every
+ *     iteration, KL only where (it + 1) % kl_every == 0 (NaN elsewhere: the logarithms are the costly part of a pair).
+ *   No atomics, every sum in a fixed order: two runs, and one call or the same iterations split over several, are
+ *   bit-identical.  MMVAE_TSNE_MIN_POINTS <= N <= MMVAE_TSNE_MAX_POINTS (P is 1 GB there), D <= MMVAE_TSNE_MAX_DIM;
+ *   anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_TSNE_MAX_POINTS 16384
+#define MMVAE_TSNE_MAX_DIM 256
+#define MMVAE_TSNE_MIN_POINTS 4
+int mmvae_tsne_ld(int N); /* 0 for N outside the limits */
+size_t mmvae_tsne_ws_doubles(int N);
+int mmvae_tsne_sqdist(const float* X, float* D2, int N, int D, mmvae_stream_t stream);
+int mmvae_tsne_joint_p(const float* D2, double perplexity, float* P, int ldp, double* info, double* total, int N,
+                       mmvae_stream_t stream);
+int mmvae_tsne_forces(const float* state, const float* P, int ldp, double* ws, float* g, double* kz, int N, long it,
+                      long switch_it, mmvae_stream_t stream);
+int mmvae_tsne_run(float* state, const float* P, int ldp, double* ws, double* log, int N, long it0, int n_iter,
+                   long switch_it, double lr, int kl_every, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -19,6 +19,7 @@ c_l = ctypes.c_long
 c_f = ctypes.c_float
 c_u = ctypes.c_uint
 c_sz = ctypes.c_size_t
+c_d = ctypes.c_double
 
 MAX_EXPERTS = 8
 
@@ -75,6 +76,7 @@ MIX_MAX_COMPONENTS = 8
 PROBE_MAX_CLASSES, PROBE_MAX_PROBES = 32, 64
 COH_MAX_STEPS, COH_MAX_VOCAB, COH_MAX_CLASSIFIERS, COH_MAX_CLASSES, COH_FEATS, COH_HIDDEN = 256, 256, 8, 8, 512, 256
 DIGIT_MNIST, DIGIT_SVHN, DIGIT_MAX_NETS = 0, 1, 2      # csrc/digits.hip
+TSNE_MAX_POINTS, TSNE_MAX_DIM, TSNE_MIN_POINTS = 16384, 256, 4      # csrc/tsne.hip
 
 
 class LmeRows(ctypes.Structure):
@@ -298,6 +300,12 @@ SIGNATURES = {
     "mmvae_digit_train": (c_i, [c_p, ctypes.POINTER(c_i)] + [ctypes.POINTER(c_p)] * 2 + [c_p, c_i, c_p, c_p] + [c_i] * 4 +
                           [c_l, c_i, c_f, c_u, c_f, c_p]),
     "mmvae_digit_masks": (c_i, [c_p, c_p, c_i, c_u, c_l, c_i, c_i, c_f, c_p]),
+    "mmvae_tsne_ld": (c_i, [c_i]),
+    "mmvae_tsne_ws_doubles": (c_sz, [c_i]),
+    "mmvae_tsne_sqdist": (c_i, [c_p, c_p, c_i, c_i, c_p]),
+    "mmvae_tsne_joint_p": (c_i, [c_p, c_d, c_p, c_i, c_p, c_p, c_i, c_p]),
+    "mmvae_tsne_forces": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_l, c_l, c_p]),
+    "mmvae_tsne_run": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_l, c_i, c_l, c_d, c_i, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

@@ -1,8 +1,9 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7d) as a mixin: held-out log-likelihood, latent
-classification, CdSprites+ and MNIST-SVHN generation coherence.  What they share is here once: the guard (`_need_eval`),
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7e) as a mixin: held-out log-likelihood, latent
+classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis.  What they share is here once: the guard (`_need_eval`),
 the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality lookup
 (`_find_modalities`).  The mixers override the hooks `_proposal_size`, `_proposal` and `_sample`."""
 import contextlib
+import itertools
 
 import torch
 import torch.distributions as dist
@@ -447,3 +448,69 @@ class EvaluationMixin:
         pred = {k: v.cpu() for k, v in pred.items()}
         same = (pred["mnist"] == pred["svhn"]).int().tolist()
         return {"joint": 100.0 * sum(same) / z.shape[1], "per_sample": same, "pred": pred}
+
+    # ---- latent analysis ---------------------------------------------------------------------------
+    def _unimodal(self, head):
+        """{modality: (loc, scale, family)} of the unimodal posteriors forward() builds, from what `_sample` returns
+        first"""
+        raise NotImplementedError(f"{self.modelName}: analyse_latents is not built for this mixer")
+
+    @staticmethod
+    def _kl_rows(p, q):
+        """torch's closed form of KL(p || q) per dimension, or NotImplementedError naming the pair"""
+        if (type(p), type(q)) not in dist.kl._KL_REGISTRY:
+            raise NotImplementedError(f"analyse_latents: torch has no closed form for KL({type(p).__name__} || "
+                                      f"{type(q).__name__}); the reference's 100-sample estimate is not restated")
+        return dist.kl_divergence(p, q)
+
+    def analyse_latents(self, batches, perplexity=30.0, max_iter=1000, seed=123, init=None):
+        """The arithmetic of the reference's analyse_data (models/trainer.py:242-272), returned as tensors; plotting stays
+        with the caller.  `batches`: an iterable of batch dicts with every modality given.  Per batch the encoders, the
+        mixing and the draws of forward() run (the decoders are skipped, as in latents_for); collected are, per modality,
+        the tensor forward() stores under latent_samples[m]["latents"] and the (loc, scale) of its unimodal posterior.
+          kl[m]      (N,D) = KL(q(z|x_m) || p(z)) per dimension, p(z) = pz(*pz_params)                  (utils.make_kl_df)
+          j[m, m']   (N,D) = (KL(q_m || q_m') + KL(q_m' || q_m)) / 2 per pair of modalities, in modality order
+                     with torch's closed forms on the device; a pair of families without one raises NotImplementedError
+                     (the reference falls back to a 100-sample estimate there)
+          tsne       one ops.tsne_embed(perplexity, max_iter, seed, init) over the concatenation of all modalities' latents
+                     in modality order, as visualization.t_sne concatenates them, + "modality" (M N,) int32: the
+                     modality index of every embedded point
+        -> {"latents": {m: (N,D)}, "kl": {m: (N,D)}, "j": {(m, m'): (N,D)}, "tsne": {...}}.
+        Two deviations from the reference: the embedding follows the exact gradient, not the Barnes-Hut approximation
+        (angle 0.5) of sklearn.manifold.TSNE's default method, so that coordinates are not comparable point by point with
+        the reference's plot -- the objective is --, and it embeds every sample given, not 250; DMVAE embeds its shared
+        code, as in latents_for.
+        Needs eval mode; runs without gradients; the noise comes from the evaluation generator, so that the training noise
+        state, the dropout counters, gradients and the optimiser stay as they are.  With `eps_override` the draws are
+        consumed as forward() consumes them and `latents` equals what forward() stores, bit for bit."""
+        self._need_eval("analyse_latents", _LATENTS)
+        names, batches = list(self.vaes.keys()), list(batches)
+        # (scikit-learn's check, before anything runs: the point count is known from the batches)
+        rows = sum(max((len(v["data"]) for v in b.values() if v["data"] is not None), default=0) for b in batches)
+        ops.tsne_check_perplexity(perplexity, len(names) * rows)
+        zs, locs, scales, family = ({m: [] for m in names} for _ in range(4))
+        with self._eval_noise(keep_override=True):
+            for batch in batches:
+                if any(m not in batch or batch[m]["data"] is None for m in names):
+                    raise ValueError("analyse_latents: every batch must hold every modality")
+                head, drawn = self._sample(batch)
+                for m, z, *_ in drawn:
+                    zs[m].append(z.reshape(-1, z.shape[-1])[:, :self.n_latents])
+                for m, (loc, scale, fam) in self._unimodal(head).items():
+                    locs[m].append(loc)
+                    scales[m].append(scale)
+                    family[m] = fam
+            if not zs[names[0]]:
+                raise ValueError("analyse_latents: `batches` is empty")
+            z = {m: torch.cat(zs[m]).float().contiguous() for m in names}
+            q = {m: family[m](torch.cat(locs[m]), torch.cat(scales[m]), validate_args=False) for m in names}
+            pz = self.pz(*self.pz_params, validate_args=False)
+            kl = {m: self._kl_rows(q[m], pz) for m in names}
+            j = {(a, b): 0.5 * (self._kl_rows(q[a], q[b]) + self._kl_rows(q[b], q[a]))
+                 for a, b in itertools.combinations(names, 2)}
+            N = z[names[0]].shape[0]
+            tsne = ops.tsne_embed(torch.cat([z[m] for m in names]), perplexity=perplexity, max_iter=max_iter, seed=seed,
+                                  init=init)
+            tsne["modality"] = torch.arange(len(names), dtype=torch.int32, device=tsne["embedding"].device) \
+                .repeat_interleave(N)
+        return {"latents": z, "kl": kl, "j": j, "tsne": tsne}

@@ -7,6 +7,7 @@ import os
 from itertools import chain, combinations
 
 import torch
+import torch.distributions as dist
 
 from .. import ops
 from .mmvae_base import TorchMMVAE, normal, packed_head
@@ -259,6 +260,9 @@ class MoPOE(TorchMMVAE):
         latents = self.modality_mixing(x)
         j_mu, j_var = latents["joint"]
         return latents, ((mod, j_mu + j_var * self._draws(K, *j_mu.shape, j_mu.device)) for mod in self.vaes)
+
+    def _unimodal(self, head):
+        return {m: (*q["shared"], dist.Normal) for m, q in head["modalities"].items() if q["shared"] is not None}
 
     def forward(self, inputs, K=1):
         """mmvae_models.py:351-370"""
@@ -525,6 +529,9 @@ class POE(TorchMMVAE):
         z = mu + var * self._draws(K, *mu.shape, mu.device)
         return (normal(mu, var), single), [(mod, z) for mod in x]
 
+    def _unimodal(self, head):
+        return {m: (q.loc, q.scale, dist.Normal) for m, q in head[1].items()}
+
     def forward(self, inputs, K=1):
         """mmvae_models.py:189-208"""
         (qz_x, single), zs = self._sample(inputs, K)
@@ -715,6 +722,12 @@ class MOE(TorchMMVAE):
                 qz[m] = normal(mu, lv)
                 drawn[m] = mu + lv * self._draws(K, *mu.shape, mu.device)
         return qz, [(m, drawn[src[m]]) for m in self.vaes if src[m] in drawn]
+
+    def _unimodal(self, head):
+        """(the reference builds these posteriors with the VAE's own `qz_x`: Laplace under `prior: laplace`)"""
+        names = list(self.vaes.keys())
+        return {m: (q.loc, q.scale, dist.Laplace if self._laplace[names.index(m)] else dist.Normal)
+                for m, q in head.items() if q is not None}
 
     def forward(self, x, K=1):
         """mmvae_models.py:80-117, including the cross-generation calls with missing modalities
@@ -927,6 +940,9 @@ class DMVAE(TorchMMVAE):
                 for _ in cross:      # (latents_for: the cross draws nobody decoded are taken all the same)
                     pass
         return (enc_d, joint, draw(joint, D)), per_modality()
+
+    def _unimodal(self, head):
+        return {m: (*q["shared"], dist.Normal) for m, q in head[0].items() if q["shared"] is not None}
 
     def forward(self, x, K=1):
         """mmvae_models.py:467-503: the container the evaluation code reads (shared / private posteriors, joint

@@ -179,6 +179,16 @@ class MultimodalVAE(nn.Module):
         self._log_metrics([("test_coherence_digit_joint", out["joint"])])
         return out
 
+    def analyse_latents(self, batches, **kwargs):
+        """the arithmetic of the reference's analyse_data (TorchMMVAE.analyse_latents: per-dimension KL table and the exact
+        t-SNE embedding of every modality's latent samples; the model must be in eval mode), logged as val_kl_mod_<i> (the
+        mean over samples of the KL to the prior, summed over the dimensions) and val_tsne_kl"""
+        out = self.model.analyse_latents(batches, **kwargs)
+        names = list(self.model.vaes.keys())
+        self._log_metrics([("val_kl_mod_{}".format(names.index(m)), v.sum(-1).mean()) for m, v in out["kl"].items()] +
+                          [("val_tsne_kl", out["tsne"]["kl_divergence"])])
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;
