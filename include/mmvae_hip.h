@@ -32,7 +32,8 @@ enum {
   MMVAE_OK = 0,
   MMVAE_ERR_ARG = 1,         /* null pointer / non-positive size */
   MMVAE_ERR_UNSUPPORTED = 2, /* shape outside what the kernels are built for */
-  MMVAE_ERR_LAUNCH = 3       /* hipGetLastError() != hipSuccess after launch */
+  MMVAE_ERR_LAUNCH = 3,      /* hipGetLastError() != hipSuccess after launch */
+  MMVAE_ERR_NO_CONVERGENCE = 4 /* an iteration reached its cap (mmvae_sym_eig: MMVAE_EIG_MAX_SWEEPS sweeps) */
 };
 
 /* input transform applied to an operand while it is staged into LDS */
@@ -877,6 +878,7 @@ int mmvae_cls_head(const float* feats, const float* W1, const float* b1, const f
  *   csrc/common.hpp from (seed, kind, global step, position r of the row inside its minibatch, unit) and nothing else;
  *   Dropout2d masks the 20 channels of conv2's output, dropout the 50 outputs of relu(fc1).  p = 0: no dropout.
  * mmvae_digit_eval: logp (nets,N,10) log-probabilities, pred (nets,N) int32 = their first maximum; dropout off.
+ * mmvae_digit_hidden: hidden (nets,N,50) = relu(fc1), the eval kernel's body up to that layer; dropout off.
  * mmvae_digit_grad: the first half of a training step on the minibatch images[i][0 .. rows): rowloss (nets,rows) =
  *   -logp[label], grad (nets,stride) = the gradient of mean_r rowloss with the masks of (seed, step).
  * mmvae_digit_train: the global steps [step0, step0 + n_steps), minibatch schedule and `order` (order_epochs, N) exactly
@@ -902,6 +904,8 @@ int mmvae_digit_n_params(int kind); /* 21840 / 31340; 0 for an unknown kind */
 size_t mmvae_digit_ws_floats(int nets, int batch, int stride);
 int mmvae_digit_eval(const float* state, const int* kinds, const float* const* images, float* logp, int* pred, int nets,
                      int stride, long N, mmvae_stream_t stream);
+int mmvae_digit_hidden(const float* state, const int* kinds, const float* const* images, float* hidden, int nets,
+                       int stride, long N, mmvae_stream_t stream);
 int mmvae_digit_grad(const float* state, const int* kinds, const float* const* images, const int* const* labels,
                      float* ws, float* grad, float* rowloss, int nets, int stride, int rows, unsigned seed, long step,
                      float p, mmvae_stream_t stream);
@@ -949,6 +953,57 @@ int mmvae_tsne_forces(const float* state, const float* P, int ldp, double* ws, f
                       long switch_it, mmvae_stream_t stream);
 int mmvae_tsne_run(float* state, const float* P, int ldp, double* ws, double* log, int N, long it0, int n_iter,
                    long switch_it, double lr, int kl_every, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Frechet distance of generated images (TorchMMVAE.frechet_distances; csrc/frechet.hip): the arithmetic of the
+ * reference's calculate_frechet_distance (eval/fid_score.py:203-257),
+ *   d^2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2,
+ * over feature vectors, everything in double, no atomics, every sum in a fixed order: two runs give the same bits.
+ *   Moments, streaming.  state: mmvae_frechet_state_doubles(F) = 1 + F + F F doubles = n | mean (F) | M2 (F,F), all 0
+ *     before the first batch.  mmvae_frechet_update folds X (nb,F) fp32: the batch mean (rows summed in double: four
+ *     consecutive quarters, each in row order, added as (0 + 1) + (2 + 3)), the centred scatter sum_r (x_r - mean_b)
+ *     (x_r - mean_b)^T as one tiled SYRK on v_mfma_f64_16x16x4_f64 (rows converted and centred in double on load; the
+ *     tiles on and above the diagonal are computed, the others mirrored; k runs over the rows in order, no K-split), and
+ *     Chan's merge in its epilogue: delta = mean_b - mean, M2 += scatter + delta delta^T n nb / (n + nb), then
+ *     mean += delta nb / (n + nb), n += nb.  ws: F doubles.  Memory does not grow with the number of rows.
+ *     mmvae_frechet_finish: mu = mean, sigma = M2 / (n - 1) (np.cov); n is the caller's copy of state[0], n >= 2.
+ *   mmvae_f64_gemm: C = A B (trans_b = 0) or A B^T on row-major (F,F) doubles, the same MFMA tile routine (64 x 64 per
+ *     workgroup, k in steps of 4 in order); C must not alias A or B.
+ *   mmvae_sym_eig: one-sided (Hestenes) Jacobi on A <- S (symmetric, row-major: its rows are the columns the sweeps
+ *     rotate), V <- I.  Round-robin ordering over n = F + (F odd) columns: a sweep is n - 1 steps of n / 2 disjoint
+ *     pairs, pair k of step s = (n - 1, s) for k = 0, ((s + k) mod (n - 1), (s - k) mod (n - 1)) for k >= 1; a pair that
+ *     touches the padding column F is skipped.  One launch per step; one wave per pair for F <= 256, one workgroup of
+ *     four waves above (mmvae_sym_eig_waves_per_pair).  Per pair a = |A_p|^2, b = |A_q|^2, c = A_p . A_q (per-thread
+ *     strided partials, a shuffle butterfly, four waves added as (0 + 1) + (2 + 3)); rotate when c != 0 and
+ *     c^2 > 1e-30 a b: zeta = (b - a) / (2 c), t = sign(zeta) / (|zeta| + sqrt(1 + zeta^2)) (0 when zeta overflows),
+ *     cs = 1 / sqrt(1 + t^2), sn = cs t, (A_p, A_q) <- (cs A_p - sn A_q, sn A_p + cs A_q), the same on V.  A rotation is
+ *     COUNTED only when a and b both exceed floor^2 = (F 2^-52 max_j |S_j|)^2 (a zero row of S never converges by the
+ *     relative rule alone); the sweeps stop after the first one without a counted rotation.  The host reads one
+ *     integer per sweep (the call synchronises the stream).  Reaching max_sweeps <= MMVAE_EIG_MAX_SWEEPS returns
+ *     MMVAE_ERR_NO_CONVERGENCE.  values (F) = |A_j| (the eigenvalues of a positive semi-definite S, in no particular
+ *     order); Vc (F,F) or NULL (values only: the same rotations, the same bits): Vc[j F + i] = V[i][j], column j the
+ *     eigenvector of values[j]; sweeps, rotations (max_sweeps): HOST ints, the sweeps run and the counted rotations of
+ *     each.  ws: mmvae_sym_eig_ws_doubles(F) = F F + 2 F + 64 doubles.
+ *   mmvae_frechet_distance: (lambda, V) of sigma1; R = diag(sqrt(lambda)) V^T; T = sigma2 R^T; G = R T; the singular
+ *     values of G, values only; tr (S1 S2)^1/2 = sum_j sqrt(sigma_j(G)).  out (5) doubles on the device = d^2,
+ *     tr covmean, |mu1 - mu2|^2, tr S1, tr S2 (thread t of 256 sums the terms t, t + 256, ..., the partials are added in
+ *     thread order); sweeps (2): HOST ints.  ws: mmvae_frechet_ws_doubles(F) = mmvae_sym_eig_ws_doubles(F) + 2 F F + 2 F.
+ *   1 <= F <= MMVAE_FRECHET_MAX_F, nb >= 1, n >= 2; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.  The
+ *   size helpers are host functions (0 outside the limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_FRECHET_MAX_F 2048
+#define MMVAE_EIG_MAX_SWEEPS 30
+size_t mmvae_frechet_state_doubles(int F);
+size_t mmvae_sym_eig_ws_doubles(int F);
+size_t mmvae_frechet_ws_doubles(int F);
+int mmvae_sym_eig_waves_per_pair(int F); /* 1 or 4; 0 outside the limits */
+int mmvae_frechet_update(double* state, const float* X, double* ws, long nb, int F, mmvae_stream_t stream);
+int mmvae_frechet_finish(const double* state, double* mu, double* sigma, long n, int F, mmvae_stream_t stream);
+int mmvae_f64_gemm(const double* A, const double* B, double* C, int F, int trans_b, mmvae_stream_t stream);
+int mmvae_sym_eig(const double* S, double* ws, double* Vc, double* values, int* sweeps, int* rotations, int F,
+                  int max_sweeps, mmvae_stream_t stream);
+int mmvae_frechet_distance(const double* mu1, const double* sigma1, const double* mu2, const double* sigma2, double* ws,
+                           double* out, int* sweeps, int F, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)

@@ -178,6 +178,15 @@ class AttributeClassifier(nn.Module):
         return AttributeClassifiers({"_": self}).predict(x, quantise=False, want_logits=True)["logits"][0]
 
 
+def attribute_features(classifier):
+    """an AttributeClassifier's 512-d trunk as a feature extractor of TorchMMVAE.frechet_distances: x -> (N, 512).  The
+    images are taken as they are -- no 8-bit quantisation, as the reference's FID path takes tensors (and floor(255 x) on
+    real data stored as k / 255 can land on k - 1)."""
+    if not isinstance(classifier, AttributeClassifier):
+        raise TypeError(f"attribute_features: a {type(classifier).__name__}, not an AttributeClassifier")
+    return lambda x: classifier.trunk(x.detach().float().reshape(-1, 3, 64, 64).contiguous())
+
+
 def quantise_images(x_hat):
     """a decoder output in [0, 1] as the reference's pipeline hands it to the classifiers: x 255, cast to uint8
     (truncation), / 255 -- floor(255 x) / 255 in fp32 -- and reinterpreted (not permuted) as (N,3,64,64)"""
@@ -318,6 +327,10 @@ class DigitClassifier(nn.Module):
         if x.numel() % (C * Hh * Ww) != 0:
             raise ValueError(f"DigitClassifier({self.kind}): images of shape {tuple(x.shape)}")
         return x.reshape(-1, C, Hh, Ww).contiguous()
+
+    def features(self, x):
+        """(N, 50): relu(fc1), the hidden layer, dropout off -- a feature extractor of TorchMMVAE.frechet_distances"""
+        return ops.digit_hidden(self.packed_state(), [self.kind], [self.images(x)])[0]
 
     def forward(self, x):
         """log-probabilities (N, 10) of images x (N,C,H,W); dropout off (the classifiers score in eval mode)"""

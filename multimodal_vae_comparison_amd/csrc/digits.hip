@@ -68,11 +68,12 @@ __device__ __forceinline__ float digit_max4(float a, float b, float c, float d, 
 
 // The whole network on one image.  par: the packed parameters; x: the image; row: the image's position in its minibatch
 // (dropout masks); gout (NPAR): the image's gradient of inv_rows * loss (TRAIN only).
-template <class G, bool TRAIN>
+template <class G, bool TRAIN, bool HIDDEN_ONLY = false>
 __device__ __forceinline__ void digit_body(float* lds, const float* __restrict__ par, const float* __restrict__ x,
                                            int label, float inv_rows, const DropKey k2d, const DropKey k1, uint32_t row,
                                            float* __restrict__ gout, float* __restrict__ rowloss,
-                                           float* __restrict__ logp_out, int* __restrict__ pred_out) {
+                                           float* __restrict__ logp_out, int* __restrict__ pred_out,
+                                           float* __restrict__ hid_out = nullptr) {
   constexpr int H = G::H, CIN = G::CIN, P1 = G::P1, P2 = G::P2, PP1 = P1 * P1, PP2 = P2 * P2, FLAT = G::FLAT;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float* xs = lds + G::L_X;
@@ -163,8 +164,10 @@ __device__ __forceinline__ void digit_body(float* lds, const float* __restrict__
       const float md = TRAIN ? drop_mul(k1, row * 50u + (uint32_t)j) : 1.0f;
       h1[j] = fmaxf(h, 0.f) * md;
       hm[j] = h > 0.f ? md : 0.f;
+      if (HIDDEN_ONLY) hid_out[j] = h1[j];
     }
   }
+  if (HIDDEN_ONLY) return;      // (mmvae_digit_hidden: relu(fc1) is the output)
   __syncthreads();
 
   // fc2
@@ -287,9 +290,10 @@ __device__ __forceinline__ void digit_body(float* lds, const float* __restrict__
   }
 }
 
-// grid (rows, nets).  TRAIN: row r of the minibatch is image ord[r] (or pos0 + r); its gradient goes to
+// grid (rows, nets).  HIDDEN (eval only): `logp` is the (nets, N, 50) output of relu(fc1) and nothing else is written.
+// TRAIN: row r of the minibatch is image ord[r] (or pos0 + r); its gradient goes to
 // ws[(net * ws_rows + r) * stride ...], its loss to rowloss[net * ws_rows + r].  Eval: log-probs and prediction of image r.
-template <bool TRAIN>
+template <bool TRAIN, bool HIDDEN = false>
 __global__ __launch_bounds__(DG_THREADS) void digit_image_kernel(DigitTable tab, const float* __restrict__ state,
                                                                  int stride, const int* __restrict__ ord, int pos0,
                                                                  int rows, int ws_rows, uint32_t seed, long step, float p,
@@ -312,6 +316,15 @@ __global__ __launch_bounds__(DG_THREADS) void digit_image_kernel(DigitTable tab,
     label = tab.y[net][img];
     gout = ws + ((size_t)net * ws_rows + r) * stride;
     rl = rowloss + (size_t)net * ws_rows + r;
+  } else if (HIDDEN) {
+    float* hid = logp + ((size_t)net * N + r) * 50;
+    if (kind == MMVAE_DIGIT_MNIST)
+      digit_body<DigitM, false, true>(lds, par, tab.x[net] + img * DigitM::NX, 0, 1.0f, k2d, k1, (uint32_t)r, nullptr,
+                                      nullptr, nullptr, nullptr, hid);
+    else
+      digit_body<DigitS, false, true>(lds, par, tab.x[net] + img * DigitS::NX, 0, 1.0f, k2d, k1, (uint32_t)r, nullptr,
+                                      nullptr, nullptr, nullptr, hid);
+    return;
   } else {
     lp = logp + ((size_t)net * N + r) * 10;
     pr = pred + (size_t)net * N + r;
@@ -419,6 +432,19 @@ extern "C" int mmvae_digit_eval(const float* state, const int* kinds, const floa
   if (rc != MMVAE_OK) return rc;
   hipLaunchKernelGGL(digit_image_kernel<false>, dim3((unsigned)N, nets), dim3(DG_THREADS), 0, (hipStream_t)stream, t, state,
                      stride, (const int*)nullptr, 0, 1, 0, 0u, 0l, 0.f, (float*)nullptr, (float*)nullptr, logp, pred, N);
+  return mmvae_launch_status();
+}
+
+extern "C" int mmvae_digit_hidden(const float* state, const int* kinds, const float* const* images, float* hidden,
+                                  int nets, int stride, long N, mmvae_stream_t stream) {
+  MMVAE_CHECK_ARG(state && kinds && images && hidden && N > 0);
+  if (N > 0x7FFFFFFFl) return MMVAE_ERR_UNSUPPORTED;
+  DigitTable t = {};
+  const int rc = digit_table(kinds, images, nullptr, nets, stride, &t);
+  if (rc != MMVAE_OK) return rc;
+  hipLaunchKernelGGL((digit_image_kernel<false, true>), dim3((unsigned)N, nets), dim3(DG_THREADS), 0, (hipStream_t)stream,
+                     t, state, stride, (const int*)nullptr, 0, 1, 0, 0u, 0l, 0.f, (float*)nullptr, (float*)nullptr, hidden,
+                     (int*)nullptr, N);
   return mmvae_launch_status();
 }
 

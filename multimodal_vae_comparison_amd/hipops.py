@@ -26,8 +26,9 @@ MAX_EXPERTS = 8
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_GELU = 0, 1, 2, 3
 EP_NONE, EP_RELU, EP_MUL_RELU_MASK, EP_MUL_SILU_GRAD, EP_GELU, EP_MUL_GELU_GRAD, EP_SIGMOID_CLAMP, EP_SIGMOID, EP_ADD_AUX = range(9)
 
-ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH = 1, 2, 3      # MMVAE_ERR_* of include/mmvae_hip.h
-_ERR = {ERR_ARG: "invalid argument", ERR_UNSUPPORTED: "unsupported shape", ERR_LAUNCH: "kernel launch failed"}
+ERR_ARG, ERR_UNSUPPORTED, ERR_LAUNCH, ERR_NO_CONVERGENCE = 1, 2, 3, 4      # MMVAE_ERR_* of include/mmvae_hip.h
+_ERR = {ERR_ARG: "invalid argument", ERR_UNSUPPORTED: "unsupported shape", ERR_LAUNCH: "kernel launch failed",
+        ERR_NO_CONVERGENCE: "no convergence within the iteration cap"}
 
 
 class PoeFwdArgs(ctypes.Structure):
@@ -77,6 +78,7 @@ PROBE_MAX_CLASSES, PROBE_MAX_PROBES = 32, 64
 COH_MAX_STEPS, COH_MAX_VOCAB, COH_MAX_CLASSIFIERS, COH_MAX_CLASSES, COH_FEATS, COH_HIDDEN = 256, 256, 8, 8, 512, 256
 DIGIT_MNIST, DIGIT_SVHN, DIGIT_MAX_NETS = 0, 1, 2      # csrc/digits.hip
 TSNE_MAX_POINTS, TSNE_MAX_DIM, TSNE_MIN_POINTS = 16384, 256, 4      # csrc/tsne.hip
+FRECHET_MAX_F, EIG_MAX_SWEEPS = 2048, 30      # csrc/frechet.hip
 
 
 class LmeRows(ctypes.Structure):
@@ -295,6 +297,7 @@ SIGNATURES = {
     "mmvae_digit_n_params": (c_i, [c_i]),
     "mmvae_digit_ws_floats": (c_sz, [c_i] * 3),
     "mmvae_digit_eval": (c_i, [c_p, ctypes.POINTER(c_i), ctypes.POINTER(c_p), c_p, c_p, c_i, c_i, c_l, c_p]),
+    "mmvae_digit_hidden": (c_i, [c_p, ctypes.POINTER(c_i), ctypes.POINTER(c_p), c_p, c_i, c_i, c_l, c_p]),
     "mmvae_digit_grad": (c_i, [c_p, ctypes.POINTER(c_i)] + [ctypes.POINTER(c_p)] * 2 + [c_p] * 3 + [c_i] * 3 +
                          [c_u, c_l, c_f, c_p]),
     "mmvae_digit_train": (c_i, [c_p, ctypes.POINTER(c_i)] + [ctypes.POINTER(c_p)] * 2 + [c_p, c_i, c_p, c_p] + [c_i] * 4 +
@@ -306,6 +309,15 @@ SIGNATURES = {
     "mmvae_tsne_joint_p": (c_i, [c_p, c_d, c_p, c_i, c_p, c_p, c_i, c_p]),
     "mmvae_tsne_forces": (c_i, [c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_l, c_l, c_p]),
     "mmvae_tsne_run": (c_i, [c_p, c_p, c_i, c_p, c_p, c_i, c_l, c_i, c_l, c_d, c_i, c_p]),
+    "mmvae_frechet_state_doubles": (c_sz, [c_i]),
+    "mmvae_sym_eig_ws_doubles": (c_sz, [c_i]),
+    "mmvae_frechet_ws_doubles": (c_sz, [c_i]),
+    "mmvae_sym_eig_waves_per_pair": (c_i, [c_i]),
+    "mmvae_frechet_update": (c_i, [c_p, c_p, c_p, c_l, c_i, c_p]),
+    "mmvae_frechet_finish": (c_i, [c_p, c_p, c_p, c_l, c_i, c_p]),
+    "mmvae_f64_gemm": (c_i, [c_p, c_p, c_p, c_i, c_i, c_p]),
+    "mmvae_sym_eig": (c_i, [c_p, c_p, c_p, c_p, ctypes.POINTER(c_i), ctypes.POINTER(c_i), c_i, c_i, c_p]),
+    "mmvae_frechet_distance": (c_i, [c_p] * 6 + [ctypes.POINTER(c_i), c_i, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

@@ -1,5 +1,5 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7e) as a mixin: held-out log-likelihood, latent
-classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis.  What they share is here once: the guard (`_need_eval`),
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7f) as a mixin: held-out log-likelihood, latent
+classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance of generated images.  What they share is here once: the guard (`_need_eval`),
 the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality lookup
 (`_find_modalities`).  The mixers override the hooks `_proposal_size`, `_proposal` and `_sample`."""
 import contextlib
@@ -514,3 +514,91 @@ class EvaluationMixin:
             tsne["modality"] = torch.arange(len(names), dtype=torch.int32, device=tsne["embedding"].device) \
                 .repeat_interleave(N)
         return {"latents": z, "kl": kl, "j": j, "tsne": tsne}
+
+    # ---- Frechet distance of generated images ------------------------------------------------------
+    def frechet_distances(self, batches, features, n_joint=0, eps=None, joint_eps=None):
+        """Frechet distance d^2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2 between the features of real and of
+        generated images: the arithmetic of the reference's calculate_frechet_distance (eval/fid_score.py:203-257), in
+        float64 on the device (ops.frechet_*; csrc/frechet.hip).  `batches`: an iterable of batch dicts; `features`:
+        {modality: callable}, each mapping a tensor to (rows, F) float features on the device -- coherence.
+        attribute_features(classifier), DigitClassifier.features, or a module of the caller's (with InceptionV3's pooled
+        features this is FID proper).  A callable receives batch[m]["data"] for the real rows and decoder_dist.loc for
+        generated ones; of the rows it returns for a generation, the first B (the batch's rows) are folded, as the digit
+        coherence reads them.  Per modality m in `features`, streaming moment states (memory does not grow with the rows):
+          real       every batch's data, folded first;
+          recon      forward() of the full batch;
+          cross[g]   forward() with only modality g given, for every other modality g;
+          joint      n_joint > 0: the decoder output of n_joint latents z ~ p(z) (`joint_eps` (n_joint, D) replaces the draw).
+        Per batch forward() runs on the full batch, then once per modality g in modality order.
+        -> {m: {"recon": d^2, "cross": {g: d^2}, "joint": d^2 | None, "n": real rows, "F": F,
+                "sweeps": {"recon": (s1, s2), "cross": {g: (s1, s2)}, "joint": (s1, s2) | None}}}, distances as floats, the
+        sweeps those of the two Jacobi eigendecompositions of a distance.
+        Deviations from the reference: the square root is taken through two symmetric eigendecompositions (S1 = V L V^T,
+        then R S2 R^T with R = L^1/2 V^T) instead of a Schur sqrtm of the non-symmetric product S1 S2; its fallback of
+        adding 1e-6 to both diagonals applies only when sqrtm returns non-finite values, which this route never does, and
+        is not restated, nor is its check of the imaginary part; the feature extractor is the caller's (InceptionV3's
+        weights cannot be shipped).
+        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
+        tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
+        dropout counters, gradients and the optimiser stay as they are."""
+        n_joint = int(n_joint)
+        self._need_eval("frechet_distances", _GENERATIONS, shared_latents=n_joint > 0)
+        names, batches = list(self.vaes.keys()), list(batches)
+        if not batches:
+            raise ValueError("frechet_distances: `batches` is empty")
+        if not features or any(m not in names or not callable(f) for m, f in features.items()):
+            raise ValueError(f"frechet_distances: `features` maps modalities of this model ({names}) to callables")
+        mods = [m for m in names if m in features]
+        for batch in batches:
+            if any(m not in batch or batch[m]["data"] is None for m in names):
+                raise ValueError("frechet_distances: every batch must hold every modality (a modality without data)")
+        rows = sum(len(b[mods[0]]["data"]) for b in batches)
+        if rows < 2 or n_joint == 1:
+            raise ValueError(f"frechet_distances: {rows} real rows, n_joint = {n_joint} (a covariance needs two rows)")
+        states, dims = {}, {}
+
+        def fold(m, key, x, keep=None):
+            f = features[m](x)
+            if not torch.is_tensor(f) or f.dim() != 2 or not f.is_floating_point():
+                raise ValueError(f"frechet_distances: the extractor of {m!r} must return float (rows, F) features")
+            if dims.setdefault(m, f.shape[1]) != f.shape[1]:
+                raise ValueError(f"frechet_distances: the extractor of {m!r} returned F = {f.shape[1]} after F = {dims[m]}")
+            if (m, key) not in states:
+                states[(m, key)] = ops.frechet_state(dims[m], f.device)
+            ops.frechet_update(states[(m, key)], f if keep is None else f[:keep])
+
+        with self._eval_noise(eps):
+            for batch in batches:
+                for m in mods:
+                    fold(m, "real", batch[m]["data"])
+            for batch in batches:
+                B = len(batch[mods[0]]["data"])
+                out = self.forward(batch)
+                for m in mods:
+                    fold(m, "recon", out.mods[m].decoder_dist.loc, B)
+                for g in names:
+                    if any(m != g for m in mods):
+                        out = self.forward(self._given_only(batch, [g]))
+                        for m in mods:
+                            if m != g:
+                                fold(m, ("cross", g), out.mods[m].decoder_dist.loc, B)
+            if n_joint > 0:
+                z = self._prior_sample(n_joint, joint_eps, "frechet_distances")
+                for m in mods:
+                    fold(m, "joint", self.vaes[m].dec({"latents": z, "masks": None})[0])
+            res = {}
+            for m in mods:
+                n, mu, sigma = ops.frechet_moments(states[(m, "real")])
+                r = {"recon": None, "cross": {}, "joint": None, "n": n, "F": dims[m],
+                     "sweeps": {"recon": None, "cross": {}, "joint": None}}
+                for (mm, key), st in states.items():
+                    if mm != m or key == "real":
+                        continue
+                    _, mu_g, sigma_g = ops.frechet_moments(st)
+                    d = ops.frechet_distance(mu, sigma, mu_g, sigma_g)
+                    if isinstance(key, tuple):
+                        r["cross"][key[1]], r["sweeps"]["cross"][key[1]] = float(d["distance"]), d["sweeps"]
+                    else:
+                        r[key], r["sweeps"][key] = float(d["distance"]), d["sweeps"]
+                res[m] = r
+        return res

@@ -189,6 +189,16 @@ class MultimodalVAE(nn.Module):
                           [("val_tsne_kl", out["tsne"]["kl_divergence"])])
         return out
 
+    def frechet_distances(self, batches, features, **kwargs):
+        """Frechet distance between the features of real and of generated images (TorchMMVAE.frechet_distances; the model
+        must be in eval mode), logged as test_frechet_<m>_recon, test_frechet_<m>_from_<g> and test_frechet_<m>_joint"""
+        out = self.model.frechet_distances(batches, features, **kwargs)
+        for m, r in out.items():
+            self._log_metrics([("test_frechet_{}_recon".format(m), r["recon"])] +
+                              [("test_frechet_{}_from_{}".format(m, g), d) for g, d in r["cross"].items()] +
+                              ([] if r["joint"] is None else [("test_frechet_{}_joint".format(m), r["joint"])]))
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;

@@ -11,6 +11,7 @@ Conventions used by every layer op
 """
 import bisect
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -3655,3 +3656,129 @@ def tsne_embed(X, perplexity=30.0, max_iter=1000, seed=123, init=None, lr="auto"
     _, kl, _ = tsne_forces(state, P, max(it, switch_it), switch_it=switch_it)
     return {"embedding": state[0].clone(), "kl_divergence": float(kl), "n_iter": it, "log": torch.cat(logs),
             "beta": beta}
+
+
+# ---- Frechet distance of feature sets (csrc/frechet.hip): float64, forward only, no autograd --------------------------------
+def _frechet_f(who, F):
+    F = int(F)
+    if not 1 <= F <= H.FRECHET_MAX_F:
+        raise ValueError(f"{who}: F = {F} features (1 .. {H.FRECHET_MAX_F} are on the MI355X path)")
+    return F
+
+
+def _frechet_state_f(who, state):
+    """F of a moment state, or ValueError: the contiguous float64 vector (1 + F + F F,) that frechet_state returns"""
+    ok = torch.is_tensor(state) and state.dim() == 1 and state.dtype == torch.float64 and state.is_contiguous()
+    F = (math.isqrt(max(4 * state.numel() - 3, 0)) - 1) // 2 if ok else 0
+    if not ok or 1 + F + F * F != state.numel() or not 1 <= F <= H.FRECHET_MAX_F:
+        what = f"{tuple(state.shape)}, {state.dtype}" if torch.is_tensor(state) else type(state).__name__
+        raise ValueError(f"{who}: the state is {what}; frechet_state gives a contiguous float64 vector (1 + F + F F,), "
+                         f"1 <= F <= {H.FRECHET_MAX_F} on the MI355X path")
+    return F
+
+
+def frechet_state(F, device):
+    """empty streaming moment state, float64 (1 + F + F F,): n | mean (F) | M2 (F,F), all 0"""
+    F = _frechet_f("frechet_state", F)
+    return torch.zeros(1 + F + F * F, dtype=torch.float64, device=device)
+
+
+def frechet_update(state, feats):
+    """fold the rows of feats (n_b, F) into the state: batch mean and centred scatter in double (one tiled SYRK on the
+    fp64 MFMA), merged by Chan's rule.  Memory does not grow with the number of rows folded."""
+    F = _frechet_state_f("frechet_update", state)
+    if feats.dim() != 2 or feats.shape[1] != F or not feats.is_floating_point():
+        raise ValueError(f"frechet_update: features of shape {tuple(feats.shape)}, {feats.dtype}; the state holds floating "
+                         f"(rows, {F}) (1 .. {H.FRECHET_MAX_F} features are on the MI355X path)")
+    if feats.shape[0] == 0:
+        return state
+    feats = H.f32c(feats.detach())
+    if not bool(torch.isfinite(feats).all()):
+        raise ValueError("frechet_update: the features hold values that are not finite")
+    ws = torch.empty(F, dtype=torch.float64, device=state.device)
+    _call("mmvae_frechet_update", H.ptr(state), H.ptr(feats), H.ptr(ws), feats.shape[0], F, H.stream())
+    return state
+
+
+def frechet_moments(state):
+    """-> (n, mu (F,) float64, sigma (F,F) float64 = M2 / (n - 1): np.cov's normalisation, n >= 2)"""
+    F = _frechet_state_f("frechet_moments", state)
+    n = int(state[0])
+    if n < 2:
+        raise ValueError(f"frechet_moments: n = {n} rows folded (a covariance needs n >= 2)")
+    mu = torch.empty(F, dtype=torch.float64, device=state.device)
+    sigma = torch.empty(F, F, dtype=torch.float64, device=state.device)
+    _call("mmvae_frechet_finish", H.ptr(state), H.ptr(mu), H.ptr(sigma), n, F, H.stream())
+    return n, mu, sigma
+
+
+def _f64_square(who, what, M):
+    if M.dim() != 2 or M.shape[0] != M.shape[1] or M.dtype != torch.float64:
+        raise ValueError(f"{who}: {what} of shape {tuple(M.shape)}, {M.dtype}; float64 (F,F), 1 <= F <= {H.FRECHET_MAX_F} on "
+                         f"the MI355X path")
+    _frechet_f(who, M.shape[0])
+    return M.contiguous()
+
+
+def f64_gemm(A, B, trans_b=False):
+    """C = A B (or A B^T) of row-major float64 (F,F) matrices on the fp64 MFMA tile routine"""
+    A, B = _f64_square("f64_gemm", "A", A), _f64_square("f64_gemm", "B", B)
+    if A.shape != B.shape:
+        raise ValueError(f"f64_gemm: A {tuple(A.shape)} and B {tuple(B.shape)} differ")
+    C = torch.empty_like(A)
+    _call("mmvae_f64_gemm", H.ptr(A), H.ptr(B), H.ptr(C), A.shape[0], int(bool(trans_b)), H.stream())
+    return C
+
+
+def sym_eig(S, vectors=True, max_sweeps=H.EIG_MAX_SWEEPS):
+    """One-sided Jacobi of the symmetric float64 S (F,F) in round-robin order, one launch per step (include/mmvae_hip.h:
+    mmvae_sym_eig) -> {"values": (F,) = |A_j|, the eigenvalues of a positive semi-definite S, unsorted, "vectors": (F,F)
+    with column j the eigenvector of values[j] (None for vectors=False: the same values bit for bit), "sweeps": int,
+    "rotations": [counted rotations per sweep]}.  The host reads one integer per sweep.  RuntimeError when the sweeps reach
+    `max_sweeps` (at most 30) without converging."""
+    S = _f64_square("sym_eig", "S", S)
+    F, max_sweeps = S.shape[0], int(max_sweeps)
+    if not 1 <= max_sweeps <= H.EIG_MAX_SWEEPS:
+        raise ValueError(f"sym_eig: max_sweeps = {max_sweeps} (1 .. {H.EIG_MAX_SWEEPS})")
+    if not bool(torch.isfinite(S).all()):
+        raise ValueError("sym_eig: S holds values that are not finite")
+    dev = S.device
+    ws = torch.empty(H.lib().mmvae_sym_eig_ws_doubles(F), dtype=torch.float64, device=dev)
+    Vc = torch.empty(F, F, dtype=torch.float64, device=dev) if vectors else None
+    values = torch.empty(F, dtype=torch.float64, device=dev)
+    sweeps, rot = ctypes.c_int(0), (ctypes.c_int * max_sweeps)()
+    _call("mmvae_sym_eig", H.ptr(S), H.ptr(ws), H.ptr(Vc), H.ptr(values), ctypes.byref(sweeps), rot, F, max_sweeps,
+          H.stream())
+    return {"values": values, "vectors": None if Vc is None else Vc.t(), "sweeps": sweeps.value,
+            "rotations": list(rot[:sweeps.value])}
+
+
+def frechet_distance(mu1, sigma1, mu2, sigma2):
+    """d^2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2 of float64 moments on the device, the square root through two
+    symmetric eigendecompositions: (lambda, V) of S1, R = diag(sqrt(lambda)) V^T, G = R S2 R^T, tr (S1 S2)^1/2 = sum_j
+    sqrt(sigma_j(G)).  -> {"distance": float64 0-d tensor, "tr_covmean": float64 0-d tensor, "sweeps": (s1, s2)}."""
+    sigma1, sigma2 = _f64_square("frechet_distance", "sigma1", sigma1), _f64_square("frechet_distance", "sigma2", sigma2)
+    F = sigma1.shape[0]
+    for what, t, shape in (("mu1", mu1, (F,)), ("mu2", mu2, (F,)), ("sigma2", sigma2, (F, F))):
+        if tuple(t.shape) != shape or t.dtype != torch.float64:
+            raise ValueError(f"frechet_distance: {what} of shape {tuple(t.shape)}, {t.dtype}; float64 {shape} beside sigma1 "
+                             f"(1 .. {H.FRECHET_MAX_F} features are on the MI355X path)")
+    mu1, mu2 = mu1.contiguous(), mu2.contiguous()
+    if not all(bool(torch.isfinite(t).all()) for t in (mu1, mu2, sigma1, sigma2)):
+        raise ValueError("frechet_distance: the moments hold values that are not finite")
+    dev = sigma1.device
+    ws = torch.empty(H.lib().mmvae_frechet_ws_doubles(F), dtype=torch.float64, device=dev)
+    out = torch.empty(5, dtype=torch.float64, device=dev)
+    sweeps = (ctypes.c_int * 2)()
+    _call("mmvae_frechet_distance", H.ptr(mu1), H.ptr(sigma1), H.ptr(mu2), H.ptr(sigma2), H.ptr(ws), H.ptr(out), sweeps, F,
+          H.stream())
+    return {"distance": out[0], "tr_covmean": out[1], "sweeps": (sweeps[0], sweeps[1])}
+
+
+def digit_hidden(state, kinds, images):
+    """-> (nets,N,50) fp32: relu(fc1) of the digit classifiers, dropout off (the features of DigitClassifier.features)"""
+    kinds, ktab, xtab, _, N = _digit_args(state, kinds, images)
+    hidden = torch.empty(len(kinds), N, 50, device=state.device)
+    if N > 0:
+        _call("mmvae_digit_hidden", H.ptr(state), ktab, xtab, H.ptr(hidden), len(kinds), state.shape[2], N, H.stream())
+    return hidden
