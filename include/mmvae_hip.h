@@ -1127,7 +1127,8 @@ int mmvae_input_pipe_commit(mmvae_input_pipe_t* pipe, const mmvae_input_mod_t* m
 int mmvae_add_pe_dropout_fwd(const float* x, const float* pe, float* y, int T, int B, int D,
                              const mmvae_dropout_t* drop, mmvae_stream_t stream);
 
-/* Scaled-dot-product attention with key padding mask for L,S <= 64 (nn.MultiheadAttention core).
+/* Scaled-dot-product attention with key padding mask for L, S <= 128 and head_dim hd <= 32 (nn.MultiheadAttention core;
+ * MMVAE_ERR_UNSUPPORTED past either limit, nothing written).
  *   q (L*N, ldq) rows r = l*N+n, head h at columns [h*hd,(h+1)*hd); k, v (S*N, ld) likewise.
  *   kpm (N,S) bytes, 1 = ignore key (may be NULL); with mask_is_valid != 0 the bytes are the batch's validity
  *   mask instead (1 = real token).  out (L*N, E=H*hd).  probs (N,H,L,S) saved for bwd: the normalised weights before
@@ -1142,6 +1143,31 @@ int mmvae_attn_bwd(const float* q, const float* k, const float* v, const float* 
  * 1 = the register form (csrc/text.hip: attn_t_bwd_kernel, needs 16-byte aligned head slices; measured level in the step);
  * returns the previous setting.  MMVAE_ATTN_T_BWD=1 in the environment starts with 1.  (nn.MultiheadAttention backward: reference models/encoders.py:706-716) */
 int mmvae_attn_t_bwd_set(int on);
+/* Which kernel instantiation of csrc/text.hip serves a call: one value per instantiation, returned by mmvae_attn_path and
+ * switched on by mmvae_attn_fwd / mmvae_attn_bwd themselves (the query IS the dispatch).  ROW = thread per query row / key
+ * column, <threads, padded head_dim>; MFMA = the LDS-tile MFMA kernels; T = the transposed forward / register-form backward.
+ *   hd <= 16 and (L > 32 or S > 32):  T_FWD if hd % 4 == 0, ldq, ldk, ldv % 4 == 0 and aligned16, else MFMA_FWD;
+ *                                     T_BWD under the same condition AND mmvae_attn_t_bwd_set(1), else MFMA_BWD;
+ *   otherwise ROW: 64 threads up to L, S <= 64, else 128; padded head_dim 16 up to hd <= 16, else 32.
+ * (so ROW_*_128_16 is built but no supported shape reaches it.) */
+enum {
+  MMVAE_ATTN_ROW_FWD_64_16 = 16,
+  MMVAE_ATTN_ROW_FWD_64_32,
+  MMVAE_ATTN_ROW_FWD_128_16,
+  MMVAE_ATTN_ROW_FWD_128_32,
+  MMVAE_ATTN_MFMA_FWD,
+  MMVAE_ATTN_T_FWD,
+  MMVAE_ATTN_ROW_BWD_64_16,
+  MMVAE_ATTN_ROW_BWD_64_32,
+  MMVAE_ATTN_ROW_BWD_128_16,
+  MMVAE_ATTN_ROW_BWD_128_32,
+  MMVAE_ATTN_MFMA_BWD,
+  MMVAE_ATTN_T_BWD
+};
+/* Pure query (launches nothing, needs no GPU).  bwd: 0 = mmvae_attn_fwd, 1 = mmvae_attn_bwd.  aligned16 != 0: every pointer
+ * the float4 paths touch is 16-byte aligned (forward: q, k, v; backward: q, k, v, dout, dq, dk, dv).  Returns one of the
+ * values above, MMVAE_ERR_UNSUPPORTED past L, S <= 128 / hd <= 32, MMVAE_ERR_ARG for a non-positive size. */
+int mmvae_attn_path(int bwd, int L, int S, int hd, long ldq, long ldk, long ldv, int aligned16);
 
 /* y = LayerNorm(x + r) * gamma + beta (eps 1e-5); r may be NULL, same-shape (r_rows = 0) or broadcast over time
  * (r_rows = N: row index = row % N).  xhat (rows,d) and rstd (rows) are saved for the backward.

@@ -968,9 +968,13 @@ __global__ __launch_bounds__(256) void attn_t_bwd_kernel(const float* __restrict
     }
   }
 }
-static inline bool attn_t_ok(const float* q, const float* k, const float* v, int hd, long ldq, long ldk, long ldv) {
-  return hd <= AT_HD && (hd & 3) == 0 && ((ldq | ldk | ldv) & 3) == 0 &&
-         ((((uintptr_t)q) | ((uintptr_t)k) | ((uintptr_t)v)) & 15) == 0;
+// what the float4 paths of the transposed forward and the register-form backward need of the layout ...
+static inline bool attn_t_shape_ok(int hd, long ldq, long ldk, long ldv) {
+  return hd <= AT_HD && (hd & 3) == 0 && ((ldq | ldk | ldv) & 3) == 0;
+}
+// ... and of the pointers
+static inline bool attn_aligned16(const void* a, const void* b, const void* c) {
+  return ((((uintptr_t)a) | ((uintptr_t)b) | ((uintptr_t)c)) & 15) == 0;
 }
 // the MFMA kernels take over from the thread-per-row ones past 32 rows (round 5: it was 64 -- the text decoder of a PoE
 // subset WITHOUT the text modality decodes all 45 positions of its modality: 20 / 33 us per call at 32 x 2 x 45 x 45)
@@ -994,27 +998,46 @@ extern "C" int mmvae_attn_t_bwd_set(int on) {
 static inline bool attn_use_mfma(int L, int S, int hd) {
   return hd <= AT_HD && (L > 32 || S > 32) && L <= 128 && S <= 128;
 }
+// THE dispatch rule: both launch functions switch on it and nothing else, so this query cannot drift from what runs.
+// (MMVAE_ATTN_ROW_*_128_16 is instantiated but not reachable: head_dim <= 16 past 32 rows or keys is an MFMA shape, and up
+// to 32 x 32 the 64-thread form serves.)
+extern "C" int mmvae_attn_path(int bwd, int L, int S, int hd, long ldq, long ldk, long ldv, int aligned16) {
+  if (L <= 0 || S <= 0 || hd <= 0) return MMVAE_ERR_ARG;
+  if (L > ATT_MAX || S > ATT_MAX || hd > ATT_HD_MAX) return MMVAE_ERR_UNSUPPORTED;
+  if (attn_use_mfma(L, S, hd)) {
+    const bool t_ok = attn_t_shape_ok(hd, ldq, ldk, ldv) && aligned16 != 0;
+    if (!bwd) return t_ok ? MMVAE_ATTN_T_FWD : MMVAE_ATTN_MFMA_FWD;
+    return (t_ok && attn_t_bwd_enabled()) ? MMVAE_ATTN_T_BWD : MMVAE_ATTN_MFMA_BWD;
+  }
+  const bool small = L <= 64 && S <= 64;
+  if (!bwd) return small ? (hd <= 16 ? MMVAE_ATTN_ROW_FWD_64_16 : MMVAE_ATTN_ROW_FWD_64_32)
+                         : (hd <= 16 ? MMVAE_ATTN_ROW_FWD_128_16 : MMVAE_ATTN_ROW_FWD_128_32);
+  return small ? (hd <= 16 ? MMVAE_ATTN_ROW_BWD_64_16 : MMVAE_ATTN_ROW_BWD_64_32)
+               : (hd <= 16 ? MMVAE_ATTN_ROW_BWD_128_16 : MMVAE_ATTN_ROW_BWD_128_32);
+}
 
 extern "C" int mmvae_attn_fwd(const float* q, const float* k, const float* v, const uint8_t* kpm, float* out,
                               float* probs, int L, int S, int N, int H, int hd, long ldq, long ldk, long ldv,
                               int mask_is_valid, const mmvae_dropout_t* drop, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(q && k && v && out && probs && L > 0 && S > 0 && N > 0 && H > 0 && hd > 0);
-  if (L > ATT_MAX || S > ATT_MAX || hd > ATT_HD_MAX) return MMVAE_ERR_UNSUPPORTED;
-  if (attn_use_mfma(L, S, hd) && attn_t_ok(q, k, v, hd, ldq, ldk, ldv)) {
-    hipLaunchKernelGGL(attn_t_fwd_kernel, dim3(N, H, (L + 31) / 32), dim3(64), 0, (hipStream_t)stream, q, k, v, kpm, out, probs,
-                       L, S, N, H, hd, ldq, ldk, ldv, mask_is_valid, drop_arg(drop));
-    return mmvae_launch_status();
-  }
-  if (attn_use_mfma(L, S, hd)) {
-    hipLaunchKernelGGL(attn_mfma_fwd_kernel, dim3(N, H), dim3(256), 0, (hipStream_t)stream, q, k, v, kpm, out, probs, L, S,
-                       N, H, hd, ldq, ldk, ldv, mask_is_valid, drop_arg(drop));
-    return mmvae_launch_status();
-  }
 #define ATT_FWD(AM, HD)                                                                                              \
   hipLaunchKernelGGL((attn_fwd_kernel<AM, HD>), dim3(N, H), dim3(AM), 0, (hipStream_t)stream, q, k, v, kpm, out, probs, \
                      L, S, N, H, hd, ldq, ldk, ldv, mask_is_valid, drop_arg(drop))
-  if (L <= 64 && S <= 64) { if (hd <= 16) ATT_FWD(64, 16); else ATT_FWD(64, 32); }
-  else { if (hd <= 16) ATT_FWD(128, 16); else ATT_FWD(128, 32); }
+  switch (mmvae_attn_path(0, L, S, hd, ldq, ldk, ldv, attn_aligned16(q, k, v))) {
+    case MMVAE_ATTN_T_FWD:
+      hipLaunchKernelGGL(attn_t_fwd_kernel, dim3(N, H, (L + 31) / 32), dim3(64), 0, (hipStream_t)stream, q, k, v, kpm, out,
+                         probs, L, S, N, H, hd, ldq, ldk, ldv, mask_is_valid, drop_arg(drop));
+      break;
+    case MMVAE_ATTN_MFMA_FWD:
+      hipLaunchKernelGGL(attn_mfma_fwd_kernel, dim3(N, H), dim3(256), 0, (hipStream_t)stream, q, k, v, kpm, out, probs, L, S,
+                         N, H, hd, ldq, ldk, ldv, mask_is_valid, drop_arg(drop));
+      break;
+    case MMVAE_ATTN_ROW_FWD_64_16: ATT_FWD(64, 16); break;
+    case MMVAE_ATTN_ROW_FWD_64_32: ATT_FWD(64, 32); break;
+    case MMVAE_ATTN_ROW_FWD_128_16: ATT_FWD(128, 16); break;
+    case MMVAE_ATTN_ROW_FWD_128_32: ATT_FWD(128, 32); break;
+    default: return MMVAE_ERR_UNSUPPORTED;
+  }
 #undef ATT_FWD
   return mmvae_launch_status();
 }
@@ -1022,24 +1045,26 @@ extern "C" int mmvae_attn_bwd(const float* q, const float* k, const float* v, co
                               float* dq, float* dk, float* dv, int L, int S, int N, int H, int hd, long ldq, long ldk,
                               long ldv, const mmvae_dropout_t* drop, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(q && k && v && probs && dout && dq && dk && dv && L > 0 && S > 0 && N > 0 && H > 0 && hd > 0);
-  if (L > ATT_MAX || S > ATT_MAX || hd > ATT_HD_MAX) return MMVAE_ERR_UNSUPPORTED;
-  if (attn_use_mfma(L, S, hd)) {
-    // the register form needs 16-byte aligned head slices (its dq / dk / dv stores are float4), as the transposed forward does
-    const bool t_ok = attn_t_bwd_enabled() && attn_t_ok(q, k, v, hd, ldq, ldk, ldv) && attn_t_ok(dq, dk, dv, hd, ldq, ldk, ldv) &&
-                      (((uintptr_t)dout) & 15) == 0;
-    if (t_ok)
-      hipLaunchKernelGGL(attn_t_bwd_kernel, dim3(N, H), dim3(256), 0, (hipStream_t)stream, q, k, v, probs, dout, dq, dk, dv, L,
-                         S, N, H, hd, ldq, ldk, ldv, drop_arg(drop));
-    else
-      hipLaunchKernelGGL(attn_mfma_bwd_kernel, dim3(N, H), dim3(256), 0, (hipStream_t)stream, q, k, v, probs, dout, dq, dk,
-                         dv, L, S, N, H, hd, ldq, ldk, ldv, drop_arg(drop));
-    return mmvae_launch_status();
-  }
+  // the register form needs 16-byte aligned head slices (its dq / dk / dv stores are float4), as the transposed forward does
+  const int aligned16 = attn_aligned16(q, k, v) && attn_aligned16(dq, dk, dv) && attn_aligned16(dout, dout, dout);
 #define ATT_BWD(AM, HD)                                                                                              \
   hipLaunchKernelGGL((attn_bwd_kernel<AM, HD>), dim3(N, H), dim3(AM), 0, (hipStream_t)stream, q, k, v, probs, dout, dq, \
                      dk, dv, L, S, N, H, hd, ldq, ldk, ldv, drop_arg(drop))
-  if (L <= 64 && S <= 64) { if (hd <= 16) ATT_BWD(64, 16); else ATT_BWD(64, 32); }
-  else { if (hd <= 16) ATT_BWD(128, 16); else ATT_BWD(128, 32); }
+  switch (mmvae_attn_path(1, L, S, hd, ldq, ldk, ldv, aligned16)) {
+    case MMVAE_ATTN_T_BWD:
+      hipLaunchKernelGGL(attn_t_bwd_kernel, dim3(N, H), dim3(256), 0, (hipStream_t)stream, q, k, v, probs, dout, dq, dk, dv, L,
+                         S, N, H, hd, ldq, ldk, ldv, drop_arg(drop));
+      break;
+    case MMVAE_ATTN_MFMA_BWD:
+      hipLaunchKernelGGL(attn_mfma_bwd_kernel, dim3(N, H), dim3(256), 0, (hipStream_t)stream, q, k, v, probs, dout, dq, dk,
+                         dv, L, S, N, H, hd, ldq, ldk, ldv, drop_arg(drop));
+      break;
+    case MMVAE_ATTN_ROW_BWD_64_16: ATT_BWD(64, 16); break;
+    case MMVAE_ATTN_ROW_BWD_64_32: ATT_BWD(64, 32); break;
+    case MMVAE_ATTN_ROW_BWD_128_16: ATT_BWD(128, 16); break;
+    case MMVAE_ATTN_ROW_BWD_128_32: ATT_BWD(128, 32); break;
+    default: return MMVAE_ERR_UNSUPPORTED;
+  }
 #undef ATT_BWD
   return mmvae_launch_status();
 }

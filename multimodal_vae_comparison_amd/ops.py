@@ -2223,7 +2223,7 @@ class EmbedPE(Function):
 
 
 class Attention(Function):
-    """softmax(q k^T / sqrt(hd) + key-padding mask) v for packed qkv (L, N, 3E), L <= 64"""
+    """softmax(q k^T / sqrt(hd) + key-padding mask) v for packed qkv (L, N, 3E), L <= 128, head_dim <= 32"""
 
     @staticmethod
     def forward(ctx, qkv, kpm, nhead, mask_is_valid, drop):

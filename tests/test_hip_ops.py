@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import attention_reference as AR
 import poe_reference as PR
 
 pytestmark = pytest.mark.gpu
@@ -782,6 +783,16 @@ def test_embed_pe(ops, B, T):
         check(eg2.grad, 2.5 * er.grad, 2e-5, "demb (3 passes)")
 
 
+def check_attention_parts(what, out, dqkv, ref, dref, E):
+    """out at 2e-5 and dq, dk, dv EACH at 5e-5 of its own maximum (a dk off by a few percent hides below a larger dv when
+    the packed gradient is judged on one maximum), all failing parts named at once"""
+    parts = AR.Parts(what)
+    parts.check("out", out, ref, 2e-5)
+    for i, part in enumerate(AR.GRADS):
+        parts.check(part, dqkv[..., i * E:(i + 1) * E], dref[..., i * E:(i + 1) * E], 5e-5)
+    parts.done()
+
+
 @pytest.mark.parametrize("L,N,E,H_", [(5, 6, 54, 2), (32, 128, 54, 2), (9, 7, 32, 2), (64, 3, 16, 2),
                                       (100, 5, 32, 2), (128, 3, 64, 2), (65, 130, 32, 2), (45, 32, 16, 2), (33, 4, 24, 2)])
 def test_attention(ops, L, N, E, H_):
@@ -807,12 +818,14 @@ def test_attention(ops, L, N, E, H_):
     out.backward(do.to(DEV))
     check(out, ref, 2e-5, "attn out")
     check(qg.grad, qr.grad, 5e-5, "attn dqkv")
+    check_attention_parts("attn", out, qg.grad, ref, qr.grad, E)
     from multimodal_vae_comparison_amd import hipops as H
     was = H.lib().mmvae_attn_t_bwd_set(1)      # ... and the register-form backward
     try:
         qg2 = qkv.to(DEV).requires_grad_(True)
         ops.attention(qg2, kpm.to(torch.uint8).to(DEV), H_).backward(do.to(DEV))
         check(qg2.grad, qr.grad, 5e-5, "attn dqkv (register-form backward)")
+        check_attention_parts("attn (register-form backward)", out, qg2.grad, ref, qr.grad, E)
     finally:
         H.lib().mmvae_attn_t_bwd_set(was)
 
@@ -854,6 +867,7 @@ def test_attention_weight_dropout(ops, L, N, E, H_, p):
             out.backward(do.to(DEV))
             check(out, ref, 2e-5, "attn out")
             check(qg.grad, qr.grad, 5e-5, f"attn dqkv (backward form {form})")
+            check_attention_parts(f"attn with dropout (backward form {form})", out, qg.grad, ref, qr.grad, E)
     finally:
         H.lib().mmvae_attn_t_bwd_set(was)
 
