@@ -1006,6 +1006,43 @@ int mmvae_frechet_distance(const double* mu1, const double* sigma1, const double
                            double* out, int* sweeps, int F, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * k-nearest-neighbour manifold estimates of generated images (TorchMMVAE.manifold_metrics; csrc/manifold.hip): improved
+ * precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020).  Feature rows are fp32,
+ * squared distances are taken in double through the Gram product:
+ *   n2[i] = sum_f x_if^2 (f in order, one thread per row), g_ij = sum_f b_if a_jf, d^2_ij = max(0, (n2_i + n2_j) - 2 g_ij).
+ *   g is one tiled product on v_mfma_f64_16x16x4_f64 (rows converted to double on load; 64 x 64 tile per workgroup; f
+ *   walked in order in steps of 4, no split over F: one summation order per g_ij, the same for (i,j) and (j,i)).  The
+ *   rows x cols matrix is never written: a workgroup owns 64 rows and a chunk of column tiles and reduces every tile in
+ *   its epilogue; the chunks' partials of a row go to ws and a second launch merges them in chunk order.  No atomics;
+ *   integer sums, minima and "the k smallest" do not depend on the split: two runs and any two plans give the same bits.
+ *   mmvae_manifold_sqnorms: n2 (rows) doubles.
+ *   mmvae_manifold_radii: rad2[i] = the k-th smallest d^2(X_i, X_j) over j != i, the row itself left out by INDEX (a
+ *     duplicate row is an ordinary neighbour at distance 0); rows >= k + 1.
+ *   mmvae_manifold_cross: query rows B against manifold rows A with their rad2_a: count[j] (int32) = #{i : d^2(B_j, A_i)
+ *     <= rad2_a[i]} (a point on a sphere is inside), mind2[j] = min_i d^2(B_j, A_i).  (B, A) = (generated, real) gives the
+ *     hits behind precision and density, (real, generated) those behind recall and the distances behind coverage.
+ *   chunks: 0 = the default plan, mmvae_manifold_chunks(rows, cols) = min(ceil(512 / row tiles), ceil(column tiles / 4))
+ *     chunks (two workgroups per CU of 256 at 10 000 rows, at least four column tiles per chunk); a positive value asks
+ *     for that many (at most one per column tile).  Chunk c holds the column tiles [c t, (c + 1) t), t = ceil(column
+ *     tiles / chunks); chunks that would be empty are not launched.
+ *   ws: mmvae_manifold_ws_doubles(rows, cols, k, chunks) = launched chunks x rows x max(k, 2) doubles; radii: (chunk, row,
+ *     k) the chunk's k smallest ascending, +inf where it met fewer; cross (k = 1): (chunk, row, 2) = (count, smallest d^2).
+ *   1 <= rows <= MMVAE_MANIFOLD_MAX_ROWS, 1 <= k <= MMVAE_MANIFOLD_MAX_K, 1 <= F <= MMVAE_FRECHET_MAX_F, chunks >= 0;
+ *   anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.  The size helpers are host functions (0 outside the
+ *   limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_MANIFOLD_MAX_ROWS 16384
+#define MMVAE_MANIFOLD_MAX_K 16
+int mmvae_manifold_chunks(long rows, long cols);
+size_t mmvae_manifold_ws_doubles(long rows, long cols, int k, int chunks);
+int mmvae_manifold_sqnorms(const float* X, double* n2, long rows, int F, mmvae_stream_t stream);
+int mmvae_manifold_radii(const float* X, const double* n2, double* ws, double* rad2, long rows, int F, int k, int chunks,
+                         mmvae_stream_t stream);
+int mmvae_manifold_cross(const float* B, const double* nb, const float* A, const double* na, const double* rad2_a,
+                         double* ws, int* count, double* mind2, long rows_b, long rows_a, int F, int chunks,
+                         mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -1,7 +1,8 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7f) as a mixin: held-out log-likelihood, latent
-classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance of generated images.  What they share is here once: the guard (`_need_eval`),
-the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality lookup
-(`_find_modalities`).  The mixers override the hooks `_proposal_size`, `_proposal` and `_sample`."""
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7g) as a mixin: held-out log-likelihood, latent
+classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance and precision / recall /
+density / coverage of generated images.  What they share is here once: the guard (`_need_eval`), the noise context
+(`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality lookup (`_find_modalities`), the walk over
+real and generated feature sets (`_walk_generations`).  The mixers override the hooks `_proposal_size`, `_proposal` and `_sample`."""
 import contextlib
 import itertools
 
@@ -78,6 +79,60 @@ class EvaluationMixin:
         """the batch with the `data` of every modality outside `given` set to None (masks kept), as the cross-generation
         calls of forward() take it"""
         return {m: (mods[m] if m in given else dict(mods[m], data=None)) for m in self.vaes}
+
+    def _walk_generations(self, who, batches, features, n_joint, eps, joint_eps, rows_ok, sink):
+        """The walk of the metrics that compare the features of real and of generated rows (`who`: frechet_distances,
+        manifold_metrics).  After the guard and the argument checks (`rows_ok(real rows, n_joint)` raises the metric's own
+        refusal; all of it before the first forward()), per modality m of `features` every set goes to `sink(m, key, f)`,
+        f (rows, F) the extractor's float features, inside the evaluation noise context:
+          "real"        every batch's data, all batches first;
+          "recon"       forward() of the full batch;
+          ("cross", g)  forward() with only modality g given, for every other modality g;
+          "joint"       n_joint > 0: the decoder output of n_joint latents z ~ p(z) (`joint_eps` replaces the draw).
+        Per batch forward() runs on the full batch, then once per modality g in modality order; of a generation's rows
+        the first B (the batch's) are kept.  -> (the modalities walked, in model order; {m: F})."""
+        n_joint = int(n_joint)
+        self._need_eval(who, _GENERATIONS, shared_latents=n_joint > 0)
+        names, batches = list(self.vaes.keys()), list(batches)
+        if not batches:
+            raise ValueError(f"{who}: `batches` is empty")
+        if not features or any(m not in names or not callable(f) for m, f in features.items()):
+            raise ValueError(f"{who}: `features` maps modalities of this model ({names}) to callables")
+        mods = [m for m in names if m in features]
+        for batch in batches:
+            if any(m not in batch or batch[m]["data"] is None for m in names):
+                raise ValueError(f"{who}: every batch must hold every modality (a modality without data)")
+        rows_ok(sum(len(b[mods[0]]["data"]) for b in batches), n_joint)
+        dims = {}
+
+        def hand(m, key, x, keep=None):
+            f = features[m](x)
+            if not torch.is_tensor(f) or f.dim() != 2 or not f.is_floating_point():
+                raise ValueError(f"{who}: the extractor of {m!r} must return float (rows, F) features")
+            if dims.setdefault(m, f.shape[1]) != f.shape[1]:
+                raise ValueError(f"{who}: the extractor of {m!r} returned F = {f.shape[1]} after F = {dims[m]}")
+            sink(m, key, f if keep is None else f[:keep])
+
+        with self._eval_noise(eps):
+            for batch in batches:
+                for m in mods:
+                    hand(m, "real", batch[m]["data"])
+            for batch in batches:
+                B = len(batch[mods[0]]["data"])
+                out = self.forward(batch)
+                for m in mods:
+                    hand(m, "recon", out.mods[m].decoder_dist.loc, B)
+                for g in names:
+                    if any(m != g for m in mods):
+                        out = self.forward(self._given_only(batch, [g]))
+                        for m in mods:
+                            if m != g:
+                                hand(m, ("cross", g), out.mods[m].decoder_dist.loc, B)
+            if n_joint > 0:
+                z = self._prior_sample(n_joint, joint_eps, who)
+                for m in mods:
+                    hand(m, "joint", self.vaes[m].dec({"latents": z, "masks": None})[0])
+        return mods, dims
 
     # ---- held-out log-likelihood (DESIGN.md section 7a) ---------------------------------------------------------------
     def _proposal_size(self, n_given):
@@ -541,51 +596,19 @@ class EvaluationMixin:
         Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
         tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
         dropout counters, gradients and the optimiser stay as they are."""
-        n_joint = int(n_joint)
-        self._need_eval("frechet_distances", _GENERATIONS, shared_latents=n_joint > 0)
-        names, batches = list(self.vaes.keys()), list(batches)
-        if not batches:
-            raise ValueError("frechet_distances: `batches` is empty")
-        if not features or any(m not in names or not callable(f) for m, f in features.items()):
-            raise ValueError(f"frechet_distances: `features` maps modalities of this model ({names}) to callables")
-        mods = [m for m in names if m in features]
-        for batch in batches:
-            if any(m not in batch or batch[m]["data"] is None for m in names):
-                raise ValueError("frechet_distances: every batch must hold every modality (a modality without data)")
-        rows = sum(len(b[mods[0]]["data"]) for b in batches)
-        if rows < 2 or n_joint == 1:
-            raise ValueError(f"frechet_distances: {rows} real rows, n_joint = {n_joint} (a covariance needs two rows)")
-        states, dims = {}, {}
+        states = {}
 
-        def fold(m, key, x, keep=None):
-            f = features[m](x)
-            if not torch.is_tensor(f) or f.dim() != 2 or not f.is_floating_point():
-                raise ValueError(f"frechet_distances: the extractor of {m!r} must return float (rows, F) features")
-            if dims.setdefault(m, f.shape[1]) != f.shape[1]:
-                raise ValueError(f"frechet_distances: the extractor of {m!r} returned F = {f.shape[1]} after F = {dims[m]}")
+        def fold(m, key, f):
             if (m, key) not in states:
-                states[(m, key)] = ops.frechet_state(dims[m], f.device)
-            ops.frechet_update(states[(m, key)], f if keep is None else f[:keep])
+                states[(m, key)] = ops.frechet_state(f.shape[1], f.device)
+            ops.frechet_update(states[(m, key)], f)
 
-        with self._eval_noise(eps):
-            for batch in batches:
-                for m in mods:
-                    fold(m, "real", batch[m]["data"])
-            for batch in batches:
-                B = len(batch[mods[0]]["data"])
-                out = self.forward(batch)
-                for m in mods:
-                    fold(m, "recon", out.mods[m].decoder_dist.loc, B)
-                for g in names:
-                    if any(m != g for m in mods):
-                        out = self.forward(self._given_only(batch, [g]))
-                        for m in mods:
-                            if m != g:
-                                fold(m, ("cross", g), out.mods[m].decoder_dist.loc, B)
-            if n_joint > 0:
-                z = self._prior_sample(n_joint, joint_eps, "frechet_distances")
-                for m in mods:
-                    fold(m, "joint", self.vaes[m].dec({"latents": z, "masks": None})[0])
+        def rows_ok(rows, n_joint):
+            if rows < 2 or n_joint == 1:
+                raise ValueError(f"frechet_distances: {rows} real rows, n_joint = {n_joint} (a covariance needs two rows)")
+
+        mods, dims = self._walk_generations("frechet_distances", batches, features, n_joint, eps, joint_eps, rows_ok, fold)
+        with torch.no_grad():
             res = {}
             for m in mods:
                 n, mu, sigma = ops.frechet_moments(states[(m, "real")])
@@ -600,5 +623,53 @@ class EvaluationMixin:
                         r["cross"][key[1]], r["sweeps"]["cross"][key[1]] = float(d["distance"]), d["sweeps"]
                     else:
                         r[key], r["sweeps"][key] = float(d["distance"]), d["sweeps"]
+                res[m] = r
+        return res
+
+    # ---- precision, recall, density and coverage of generated images -------------------------------
+    def manifold_metrics(self, batches, features, k=5, n_joint=0, eps=None, joint_eps=None):
+        """k-nearest-neighbour manifold estimates between the features of real and of generated images: improved precision
+        and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020) -- what a Frechet distance cannot
+        tell apart: poor samples (low precision, density) from samples that cover part of the data (low recall, coverage).
+        Squared distances in float64 on the device (ops.manifold_prdc; csrc/manifold.hip); with R the real rows, G a
+        generated set of M rows and rad^2_X[i] the k-th smallest d^2 from row i of X to the other rows of X:
+          precision = mean_j [some i: d^2(G_j, R_i) <= rad^2_R[i]]      recall = mean_i [some j: d^2(R_i, G_j) <= rad^2_G[j]]
+          density   = #{(i, j): d^2(G_j, R_i) <= rad^2_R[i]} / (k M)    coverage = mean_i [min_j d^2(R_i, G_j) <= rad^2_R[i]]
+        `batches`, `features`, `n_joint`, `eps`, `joint_eps`, the sets (real, recon, cross[g], joint) and the order of the
+        forward() calls are those of frechet_distances; the fp32 feature rows of every set are kept until the walk ends.
+        -> {m: {"recon": {"precision", "recall", "density", "coverage"}, "cross": {g: {...}}, "joint": {...} | None,
+                "n": real rows, "F": F, "k": k}}, floats.
+        Needs eval mode, k + 1 .. 16384 real rows, n_joint = 0 or >= k + 1, 1 <= k <= 16; runs without gradients; the
+        training noise state, the dropout counters, gradients and the optimiser stay as they are."""
+        k, top_k, top_rows = int(k), ops.H.MANIFOLD_MAX_K, ops.H.MANIFOLD_MAX_ROWS
+        sets = {}
+
+        def rows_ok(rows, n_joint):
+            if not 1 <= k <= top_k:
+                raise ValueError(f"manifold_metrics: k = {k} neighbours (1 .. {top_k} are on the MI355X path)")
+            if not k + 1 <= rows <= top_rows or 0 < n_joint < k + 1 or n_joint > top_rows:
+                raise ValueError(f"manifold_metrics: {rows} real rows, n_joint = {n_joint} (the k-th neighbour needs k + 1 = "
+                                 f"{k + 1} rows in a set; up to {top_rows} are on the MI355X path)")
+
+        def keep_rows(f):      # a copy: a kept view would hold the extractor's whole output (rows beyond B) until the end
+            return f.detach().to(torch.float32, copy=True)
+
+        mods, dims = self._walk_generations("manifold_metrics", batches, features, n_joint, eps, joint_eps, rows_ok,
+                                            lambda m, key, f: sets.setdefault((m, key), []).append(keep_rows(f)))
+        names = ("precision", "recall", "density", "coverage")
+        res = {}
+        with torch.no_grad():
+            for m in mods:
+                real = torch.cat(sets[(m, "real")])
+                r = {"recon": None, "cross": {}, "joint": None, "n": real.shape[0], "F": dims[m], "k": k}
+                for (mm, key), rows in sets.items():
+                    if mm != m or key == "real":
+                        continue
+                    out = ops.manifold_prdc(real, torch.cat(rows), k=k)
+                    out = {name: out[name] for name in names}
+                    if isinstance(key, tuple):
+                        r["cross"][key[1]] = out
+                    else:
+                        r[key] = out
                 res[m] = r
         return res

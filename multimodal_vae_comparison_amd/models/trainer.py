@@ -199,6 +199,17 @@ class MultimodalVAE(nn.Module):
                               ([] if r["joint"] is None else [("test_frechet_{}_joint".format(m), r["joint"])]))
         return out
 
+    def manifold_metrics(self, batches, features, **kwargs):
+        """precision, recall, density and coverage of generated images against real ones (TorchMMVAE.manifold_metrics; the
+        model must be in eval mode), logged as test_{precision,recall,density,coverage}_<m>_recon, ..._<m>_from_<g> and
+        ..._<m>_joint"""
+        out = self.model.manifold_metrics(batches, features, **kwargs)
+        for m, r in out.items():
+            sets = [("{}_recon".format(m), r["recon"])] + [("{}_from_{}".format(m, g), d) for g, d in r["cross"].items()] + \
+                ([] if r["joint"] is None else [("{}_joint".format(m), r["joint"])])
+            self._log_metrics(("test_{}_{}".format(name, tag), v) for tag, d in sets for name, v in d.items())
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;
