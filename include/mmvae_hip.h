@@ -1043,6 +1043,43 @@ int mmvae_manifold_cross(const float* B, const double* nb, const float* A, const
                          mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Aggregate posterior of the latent code (TorchMMVAE.disentanglement; csrc/aggpost.hip): what the ELBO decomposition
+ * (index-code mutual information, total correlation, dimension-wise KL; Chen et al. 2018) and the mutual information gap
+ * read.  z, loc, scale (N,D) fp32, row n of z a draw from posterior n; labels (K,N) int32 >= 0 or NULL with K = 0.  Pair
+ * term in double from the fp32 inputs converted on load, t = (z_nd - loc_md) / s_md (as a product with 1 / s_md):
+ *   Normal (laplace 0)  l[n,m,d] = -t^2 / 2 - log s_md - log(2 pi) / 2        Laplace  l[n,m,d] = -|t| - log(2 s_md)
+ *   joint[n]           = logsumexp_m sum_d l[n,m,d] - log N                                      (N)     doubles
+ *   marginal[n,d]      = logsumexp_m l[n,m,d] - log N                                            (N,D)   doubles
+ *   conditional[k,n,d] = logsumexp_{m : labels[k,m] == labels[k,n]} l[n,m,d] - log N_c           (K,N,D) doubles,
+ *     N_c the size of that class, counted inside the launch.
+ *   A fixed shift, no running maximum: row n is one of the m (of its own class too), so that sum_m exp(l[n,m,d] -
+ *   l[n,n,d]) holds the term 1; its argument is at most the row's own standardised residual plus log(s_n / s_m), hundreds
+ *   of nats below the overflow at 709 for a z drawn from its posterior, and terms below -745 vanish.  Every accumulator
+ *   is a plain fp64 sum of exp(l - shift), chunks merge by addition, the result is shift + log(sum) - log(count).  (A z
+ *   thousands of deviations from its own posterior overflows the sum: the outputs are +inf there, never a wrong number.)
+ *   Four launches: the shifts l[n,n,d] and sum_d l[n,n,d] (d in order); the (n,d) sums -- a workgroup owns 64 sample rows
+ *   (one per lane), 16 dimensions (4 per wave) and a chunk of posterior rows staged 32 at a time in LDS as (loc, 1 / s,
+ *   -log s - const) beside their labels: one exp per (n,m,d), the K class sums reuse it through a select --; the joint
+ *   sums -- the same rows and chunk, a thread adds l over d in order in a register per pair and takes one exp per (n,m),
+ *   and counts the classes --; the merge of the chunks' partials in chunk order.  The N x N x D terms are never written;
+ *   no atomics; two runs with one plan give the same bits, two plans regroup fp64 sums.
+ *   chunks: 0 = the default plan, mmvae_aggpost_chunks(N, D) = min(ceil(2048 / (ceil(N / 64) ceil(D / 16))), ceil(tiles
+ *     / 2)) chunks, tiles = ceil(N / 32) staged tiles; a positive value asks for that many (at most one per tile).  Chunk
+ *     c holds the tiles [c t, (c + 1) t), t = ceil(tiles / chunks); chunks that would be empty are not launched.
+ *   ws: mmvae_aggpost_ws_doubles(N, D, K, chunks) doubles = shift (N,D) | joint shift (N) | (chunk, n, d, 1 + K) sums,
+ *     all rows first, then per factor | (chunk, n, 1 + K) joint sum, then the class members met per factor.
+ *   1 <= N <= MMVAE_AGGPOST_MAX_ROWS, 1 <= D <= 256, 0 <= K <= MMVAE_AGGPOST_MAX_FACTORS, chunks >= 0; anything else
+ *   returns MMVAE_ERR_UNSUPPORTED and writes nothing.  The two helpers are host functions (0 outside the limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_AGGPOST_MAX_ROWS 16384
+#define MMVAE_AGGPOST_MAX_FACTORS 8
+int mmvae_aggpost_chunks(long N, int D);
+size_t mmvae_aggpost_ws_doubles(long N, int D, int K, int chunks);
+int mmvae_aggpost_lse(const float* z, const float* loc, const float* scale, int laplace, const int* labels, double* ws,
+                      double* joint, double* marginal, double* conditional, long N, int D, int K, int chunks,
+                      mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -80,6 +80,7 @@ DIGIT_MNIST, DIGIT_SVHN, DIGIT_MAX_NETS = 0, 1, 2      # csrc/digits.hip
 TSNE_MAX_POINTS, TSNE_MAX_DIM, TSNE_MIN_POINTS = 16384, 256, 4      # csrc/tsne.hip
 FRECHET_MAX_F, EIG_MAX_SWEEPS = 2048, 30      # csrc/frechet.hip
 MANIFOLD_MAX_ROWS, MANIFOLD_MAX_K = 16384, 16      # csrc/manifold.hip
+AGGPOST_MAX_ROWS, AGGPOST_MAX_FACTORS, AGGPOST_MAX_DIM = 16384, 8, 256      # csrc/aggpost.hip
 
 
 class LmeRows(ctypes.Structure):
@@ -325,6 +326,9 @@ SIGNATURES = {
     "mmvae_manifold_sqnorms": (c_i, [c_p, c_p, c_l, c_i, c_p]),
     "mmvae_manifold_radii": (c_i, [c_p] * 4 + [c_l, c_i, c_i, c_i, c_p]),
     "mmvae_manifold_cross": (c_i, [c_p] * 8 + [c_l, c_l, c_i, c_i, c_p]),
+    "mmvae_aggpost_chunks": (c_i, [c_l, c_i]),
+    "mmvae_aggpost_ws_doubles": (c_sz, [c_l, c_i, c_i, c_i]),
+    "mmvae_aggpost_lse": (c_i, [c_p, c_p, c_p, c_i] + [c_p] * 5 + [c_l, c_i, c_i, c_i, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

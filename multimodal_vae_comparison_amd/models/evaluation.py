@@ -1,8 +1,9 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7g) as a mixin: held-out log-likelihood, latent
-classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance and precision / recall /
-density / coverage of generated images.  What they share is here once: the guard (`_need_eval`), the noise context
-(`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality lookup (`_find_modalities`), the walk over
-real and generated feature sets (`_walk_generations`).  The mixers override the hooks `_proposal_size`, `_proposal` and `_sample`."""
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7h) as a mixin: held-out log-likelihood, latent
+classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
+density / coverage of generated images and the disentanglement of the latent code.  What they share is here once: the
+guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
+lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
+hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
 import contextlib
 import itertools
 
@@ -672,4 +673,103 @@ class EvaluationMixin:
                     else:
                         r[key] = out
                 res[m] = r
+        return res
+
+    # ---- disentanglement of the latent code ----------------------------------------------------------
+    def _joint_posterior(self, head):
+        """(loc, scale) of the joint posterior forward() builds when it is ONE Gaussian (the product of experts of poe and
+        dmvae), from what `_sample` returns first; None where the joint is a mixture (moe, mopoe): out of scope"""
+        return None
+
+    def disentanglement(self, batches, labels=None, eps=None, chunks=0):
+        """Disentanglement of the latent code, per posterior: the decomposition of the ELBO's KL term into index-code mutual
+        information, total correlation and dimension-wise KL, and the mutual information gap against labelled generative
+        factors (both Chen et al. 2018), from the aggregate posterior q(z) = (1/N) sum_m q(z | x_m) evaluated at one draw
+        per sample in float64 on the device (ops.aggregate_posterior; csrc/aggpost.hip).
+        `batches`: an iterable of batch dicts with every modality given.  Per batch the encoders, the mixing and the draws
+        of forward() run (the decoders are skipped, as in analyse_latents); collected are the (loc, scale, family) of every
+        modality's unimodal posterior (the first n_latents columns: DMVAE's shared code) and, for poe and dmvae, of the
+        product of experts (key "joint"; the mixture joints of moe and mopoe are not covered).  Per key, over the N rows
+        of all batches: e (N,D) of the key's family from the evaluation generator, or `eps[key]`; z = loc + scale e;
+        lpz = sum_d log p(z_d) under pz(*pz_params); then ops.aggregate_posterior, ops.elbo_decomposition and, with
+        labels, ops.mutual_information_gap.
+        `labels`: (N, K) integers >= 0, ROW n the K generative factors of sample n in batch order (a (N,) vector is one
+        factor), K <= 8; without labels the entries mig, per_factor and mi_table are absent.
+        -> {key: {"mi", "tc", "dwkl", "kl" (0-d float64), "mig" (0-d), "per_factor" (K,), "mi_table" (K,D), "h_z" (D,),
+                  "z", "loc", "scale" (N,D) fp32}}, keys in modality order, then "joint".
+        Needs eval mode, N <= 16384 rows, D <= 256; with labels D >= 2 and every factor taking two values at least.  Runs
+        without gradients; the draws of the walk come from the evaluation generator: the training noise state, the dropout
+        counters, `eps_override`, gradients and the optimiser stay as they are."""
+        who = "disentanglement"
+        self._need_eval(who, _LATENTS)
+        names, batches, D = list(self.vaes.keys()), list(batches), self.n_latents
+        if not batches:
+            raise ValueError(f"{who}: `batches` is empty")
+        for batch in batches:
+            if any(m not in batch or batch[m]["data"] is None for m in names):
+                raise ValueError(f"{who}: every batch must hold every modality")
+        N = sum(len(b[names[0]]["data"]) for b in batches)
+        if not 1 <= N <= ops.H.AGGPOST_MAX_ROWS or not 1 <= D <= ops.H.AGGPOST_MAX_DIM:
+            raise ValueError(f"{who}: {N} rows of {D} latent dimensions (1 .. {ops.H.AGGPOST_MAX_ROWS} rows of 1 .. "
+                             f"{ops.H.AGGPOST_MAX_DIM} dimensions are on the MI355X path)")
+        if int(chunks) < 0:
+            raise ValueError(f"{who}: chunks = {chunks} (0: the default plan, or a positive number of chunks)")
+        if labels is not None:
+            labels = torch.as_tensor(labels).detach()
+            if labels.is_floating_point() or labels.dtype == torch.bool or labels.dim() not in (1, 2):
+                raise ValueError(f"{who}: labels must be an integer (N, K) array, one row per sample")
+            labels = labels.reshape(labels.shape[0], -1)
+            if labels.shape[0] != N or not 1 <= labels.shape[1] <= ops.H.AGGPOST_MAX_FACTORS:
+                raise ValueError(f"{who}: labels is {tuple(labels.shape)}, the batches hold {N} rows (one ROW of 1 .. "
+                                 f"{ops.H.AGGPOST_MAX_FACTORS} factors per sample, in batch order)")
+            if int(labels.min()) < 0:
+                raise ValueError(f"{who}: labels holds negative values (classes are numbered from 0)")
+            if D < 2:
+                raise ValueError(f"{who}: the mutual information gap needs D >= 2 latent dimensions (D = {D})")
+            for k in range(labels.shape[1]):
+                if len(torch.unique(labels[:, k])) < 2:
+                    raise ValueError(f"{who}: factor {k} of labels takes a single value (H(v) = 0: the gap is not defined)")
+            labels = labels.t().contiguous()
+        eps = dict(eps or {})
+        for key, e in eps.items():
+            if key not in names + ["joint"] or not torch.is_tensor(e) or tuple(e.shape) != (N, D):
+                raise ValueError(f"{who}: eps maps {names + ['joint']} to ({N}, {D}) tensors (entry {key!r})")
+        locs, scales, family = ({m: [] for m in names + ["joint"]} for _ in range(3))
+        with self._eval_noise():
+            for batch in batches:
+                head, drawn = self._sample(batch)
+                for _ in drawn:      # (read to its end: the draws forward() takes)
+                    pass
+                for m, (loc, scale, fam) in self._unimodal(head).items():
+                    locs[m].append(loc)
+                    scales[m].append(scale)
+                    family[m] = fam
+                joint = self._joint_posterior(head)
+                if joint is not None:
+                    locs["joint"].append(joint[0])
+                    scales["joint"].append(joint[1])
+                    family["joint"] = dist.Normal
+            if "joint" in eps and not locs["joint"]:
+                raise ValueError(f"{who}: eps['joint'] given, but the joint posterior of {self.modelName} is not one Gaussian")
+            pz_loc, pz_scale = (p.detach().double() for p in self.pz_params)
+            res = {}
+            for key in names + (["joint"] if locs["joint"] else []):
+                loc = torch.cat([t.reshape(-1, t.shape[-1])[:, :D] for t in locs[key]]).float().contiguous()
+                scale = torch.cat([t.reshape(-1, t.shape[-1])[:, :D] for t in scales[key]]).float().contiguous()
+                laplace = family[key] is dist.Laplace
+                if key in eps:
+                    e = eps[key].to(device=loc.device, dtype=torch.float32)
+                else:
+                    e = (ops.rand_laplace if laplace else ops.randn)((N, D), self._noise_state())
+                z = (loc + scale * e).contiguous()
+                lpz = self.pz(pz_loc, pz_scale, validate_args=False).log_prob(z.double()).sum(1)
+                lab = None if labels is None else labels.to(z.device)
+                agg = ops.aggregate_posterior(z, loc, scale, laplace=laplace, labels=lab, chunks=chunks)
+                r = dict(ops.elbo_decomposition(agg, lpz))
+                r["h_z"] = -agg["marginal"].mean(0)
+                if lab is not None:
+                    gap = ops.mutual_information_gap(agg, lab)
+                    r.update(mig=gap["mig"], per_factor=gap["per_factor"], mi_table=gap["mi"], h_z=gap["h_z"])
+                r.update(z=z, loc=loc, scale=scale)
+                res[key] = r
         return res

@@ -532,6 +532,9 @@ class POE(TorchMMVAE):
     def _unimodal(self, head):
         return {m: (q.loc, q.scale, dist.Normal) for m, q in head[1].items()}
 
+    def _joint_posterior(self, head):
+        return head[0].loc, head[0].scale
+
     def forward(self, inputs, K=1):
         """mmvae_models.py:189-208"""
         (qz_x, single), zs = self._sample(inputs, K)
@@ -943,6 +946,10 @@ class DMVAE(TorchMMVAE):
 
     def _unimodal(self, head):
         return {m: (*q["shared"], dist.Normal) for m, q in head[0].items() if q["shared"] is not None}
+
+    def _joint_posterior(self, head):
+        """the product of the shared experts (mu, variance used as scale): the shared code's joint"""
+        return None if head[1] is None else (head[1][0], head[1][1])
 
     def forward(self, x, K=1):
         """mmvae_models.py:467-503: the container the evaluation code reads (shared / private posteriors, joint
