@@ -1080,6 +1080,43 @@ int mmvae_aggpost_lse(const float* z, const float* loc, const float* scale, int 
                       mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Kernel inception distance of generated images (TorchMMVAE.kernel_distances; csrc/kid.hip): the sums behind the unbiased
+ * MMD^2 (Binkowski et al. 2018) under the polynomial kernel k(x, y) = (gamma x . y + coef0)^degree, over `subsets` random
+ * subsets of m rows.  X (rows_x, F) and Y (rows_y, F) are fp32 feature rows; idx_x, idx_y (subsets, m) int32 list, per
+ * subset, the rows taken from X and from Y: x_i = X[idx_x[s, i]], y_j = Y[idx_y[s, j]].  sums (subsets, 3) doubles:
+ *   sums[s, 0] = sxx = sum_{i != j} k(x_i, x_j)      sums[s, 1] = syy = sum_{i != j} k(y_i, y_j)
+ *   sums[s, 2] = sxy = sum_{i, j} k(x_i, y_j)
+ *   The diagonal of sxx and syy is left out by POSITION i == j in the list (a row number that a list repeats is an
+ *   ordinary pair); sxy holds all m^2 terms.  MMD^2[s] = (sxx + syy) / (m (m - 1)) - 2 sxy / m^2 is the caller's.
+ *   g_ij = x_i . y_j is the tiled product of csrc/manifold.hip on v_mfma_f64_16x16x4_f64 (64 x 64 tile per workgroup; f
+ *   walked in order in steps of 4, no split over F), its rows converted to double on load and addressed through the
+ *   index list in the fetch: no gathered copy of the rows exists.  Epilogue per element: t = gamma g + coef0, t^degree by
+ *   degree - 1 successive products by t; four threads per row add the tile's values of their row.  The m x m block is
+ *   never written.  One launch, grid (chunks, row tiles, 3 subsets), covers every (subset, pair) slice; sxx and syy walk
+ *   only the column tiles on or above the diagonal tile and count the tiles strictly above it twice (a product by 2 is
+ *   exact).  A second launch adds the row partials of a slice in a fixed order.  No atomics: for a given (m, chunks) two
+ *   runs give the same bits; two chunk plans regroup fp64 sums and agree to rounding only.
+ *   THE DEVICE DOES NOT CHECK THE INDICES: every idx_x[s, i] must lie in [0, rows_x), every idx_y[s, j] in [0, rows_y)
+ *   (ops.kid_sums checks before every call).
+ *   chunks: 0 = the default plan, mmvae_kid_chunks(subsets, m) = min(ceil(512 / (3 subsets tiles)), ceil(tiles / 4))
+ *     chunks, tiles = ceil(m / 64) (two workgroups per CU of 256, at least four column tiles per chunk: 1 chunk from 3
+ *     subsets of 1000 rows on); a positive value asks for that many (at most one per column tile).  Chunk c holds the
+ *     column tiles [c t, (c + 1) t), t = ceil(tiles / chunks); chunks that would be empty are not launched.
+ *   ws: mmvae_kid_ws_doubles(subsets, m, chunks) = 3 subsets x launched chunks x m doubles, (slice, chunk, position).
+ *   2 <= m <= MMVAE_KID_MAX_SUBSET, 1 <= subsets <= MMVAE_KID_MAX_SUBSETS, 1 <= F <= MMVAE_FRECHET_MAX_F, 1 <= degree <=
+ *   MMVAE_KID_MAX_DEGREE, rows_x, rows_y >= 1, chunks >= 0; anything else returns MMVAE_ERR_UNSUPPORTED and writes
+ *   nothing.  The two helpers are host functions (0 outside the limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_KID_MAX_SUBSET 16384
+#define MMVAE_KID_MAX_SUBSETS 1024
+#define MMVAE_KID_MAX_DEGREE 8
+int mmvae_kid_chunks(int subsets, long m);
+size_t mmvae_kid_ws_doubles(int subsets, long m, int chunks);
+int mmvae_kid_sums(const float* X, const float* Y, const int* idx_x, const int* idx_y, double* ws, double* sums,
+                   long rows_x, long rows_y, int F, int subsets, long m, int degree, double gamma, double coef0, int chunks,
+                   mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

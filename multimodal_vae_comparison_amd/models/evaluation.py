@@ -1,6 +1,6 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7h) as a mixin: held-out log-likelihood, latent
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7i) as a mixin: held-out log-likelihood, latent
 classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
-density / coverage of generated images and the disentanglement of the latent code.  What they share is here once: the
+density / coverage and kernel inception distance of generated images and the disentanglement of the latent code.  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -83,7 +83,7 @@ class EvaluationMixin:
 
     def _walk_generations(self, who, batches, features, n_joint, eps, joint_eps, rows_ok, sink):
         """The walk of the metrics that compare the features of real and of generated rows (`who`: frechet_distances,
-        manifold_metrics).  After the guard and the argument checks (`rows_ok(real rows, n_joint)` raises the metric's own
+        manifold_metrics, kernel_distances).  After the guard and the argument checks (`rows_ok(real rows, n_joint)` raises the metric's own
         refusal; all of it before the first forward()), per modality m of `features` every set goes to `sink(m, key, f)`,
         f (rows, F) the extractor's float features, inside the evaluation noise context:
           "real"        every batch's data, all batches first;
@@ -672,6 +672,61 @@ class EvaluationMixin:
                         r["cross"][key[1]] = out
                     else:
                         r[key] = out
+                res[m] = r
+        return res
+
+    # ---- kernel inception distance of generated images ------------------------------------------------
+    def kernel_distances(self, batches, features, subsets=100, subset_size=1000, seed=0, n_joint=0, eps=None, joint_eps=None):
+        """Kernel inception distance (Binkowski et al. 2018) between the features of real and of generated images: the
+        unbiased estimate of the squared maximum mean discrepancy under the polynomial kernel k(x, y) = (x . y / F + 1)^3,
+        in float64 on the device (ops.kernel_inception_distance; csrc/kid.hip).  With R the real rows and G a generated set,
+        per subset s of m = min(subset_size, |R|, |G|) rows of each, drawn without replacement:
+          mmd2[s] = sum_{i != j} k(r_i, r_j) / (m (m - 1)) + sum_{i != j} k(g_i, g_j) / (m (m - 1)) - 2 sum_{i, j} k(r_i, g_j) / m^2
+          kid = mean_s mmd2[s]      std = the standard deviation of mmd2 over the subsets (divisor `subsets`)
+        Unlike the Frechet distance the estimate is unbiased at any set size -- models evaluated on different numbers of
+        rows can be compared -- and `std` is its error bar; a negative value is a legitimate estimate and is kept.
+        `batches`, `features`, `n_joint`, `eps`, `joint_eps`, the sets (real, recon, cross[g], joint) and the order of the
+        forward() calls are those of frechet_distances; the fp32 feature rows of every set are kept until the walk ends.
+        Every generated set is compared with the real rows on subsets drawn from a fresh numpy.random.RandomState(seed)
+        (ops.kid_draw).
+        -> {m: {"recon": {"kid", "std"}, "cross": {g: {"kid", "std"}}, "joint": {"kid", "std"} | None, "n": real rows,
+                "F": F, "subsets": subsets, "m": {"recon" | "from_<g>" | "joint": the rows per subset of that set}}}, floats.
+        Deviations from the usual KID: no Inception network -- the feature extractor is the caller's, as in
+        frechet_distances (with InceptionV3's pooled features this is KID proper); the subsets come from numpy's legacy
+        generator in the order stated in ops.kid_draw, not from any other implementation's stream.
+        Needs eval mode, 2 real rows at least, n_joint = 0 or >= 2, 1 <= subsets <= 1024; runs without gradients; the
+        training noise state, the dropout counters, gradients and the optimiser stay as they are."""
+        subsets, subset_size, top = int(subsets), int(subset_size), ops.H.KID_MAX_SUBSETS
+        sets = {}
+
+        def rows_ok(rows, n_joint):
+            if not 1 <= subsets <= top or subset_size < 2:
+                raise ValueError(f"kernel_distances: {subsets} subsets of {subset_size} rows (1 .. {top} subsets of two rows "
+                                 f"at least are on the MI355X path)")
+            if rows < 2 or n_joint == 1:
+                raise ValueError(f"kernel_distances: {rows} real rows, n_joint = {n_joint} (the unbiased estimate needs two "
+                                 f"rows of each set)")
+
+        def keep_rows(f):      # a copy: a kept view would hold the extractor's whole output (rows beyond B) until the end
+            return f.detach().to(torch.float32, copy=True)
+
+        mods, dims = self._walk_generations("kernel_distances", batches, features, n_joint, eps, joint_eps, rows_ok,
+                                            lambda m, key, f: sets.setdefault((m, key), []).append(keep_rows(f)))
+        res = {}
+        with torch.no_grad():
+            for m in mods:
+                real = torch.cat(sets[(m, "real")])
+                r = {"recon": None, "cross": {}, "joint": None, "n": real.shape[0], "F": dims[m], "subsets": subsets, "m": {}}
+                for (mm, key), rows in sets.items():
+                    if mm != m or key == "real":
+                        continue
+                    out = ops.kernel_inception_distance(real, torch.cat(rows), subsets=subsets, subset_size=subset_size,
+                                                        seed=seed)
+                    pair = {"kid": float(out["kid"]), "std": float(out["std"])}
+                    if isinstance(key, tuple):
+                        r["cross"][key[1]], r["m"]["from_{}".format(key[1])] = pair, out["m"]
+                    else:
+                        r[key], r["m"][key] = pair, out["m"]
                 res[m] = r
         return res
 

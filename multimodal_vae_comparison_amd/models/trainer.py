@@ -210,6 +210,27 @@ class MultimodalVAE(nn.Module):
             self._log_metrics(("test_{}_{}".format(name, tag), v) for tag, d in sets for name, v in d.items())
         return out
 
+    def kernel_distances(self, batches, features, **kwargs):
+        """kernel inception distance of generated images against real ones and its standard deviation over the subsets
+        (TorchMMVAE.kernel_distances; the model must be in eval mode), logged as test_kid_<m>_recon, test_kid_<m>_from_<g>,
+        test_kid_<m>_joint and the same names with kid_std"""
+        out = self.model.kernel_distances(batches, features, **kwargs)
+        for m, r in out.items():
+            sets = [("{}_recon".format(m), r["recon"])] + [("{}_from_{}".format(m, g), d) for g, d in r["cross"].items()] + \
+                ([] if r["joint"] is None else [("{}_joint".format(m), r["joint"])])
+            self._log_metrics(("test_{}_{}".format(name, tag), d[key]) for tag, d in sets
+                              for name, key in (("kid", "kid"), ("kid_std", "std")))
+        return out
+
+    def disentanglement(self, batches, **kwargs):
+        """ELBO decomposition and mutual information gap of the latent code (TorchMMVAE.disentanglement; the model must be
+        in eval mode), logged per posterior key as test_{mi,tc,dwkl,kl}_<key> and, where labels were given, test_mig_<key>"""
+        out = self.model.disentanglement(batches, **kwargs)
+        for key, r in out.items():
+            self._log_metrics([("test_{}_{}".format(name, key), r[name]) for name in ("mi", "tc", "dwkl", "kl")] +
+                              ([("test_mig_{}".format(key), r["mig"])] if "mig" in r else []))
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;
