@@ -1117,6 +1117,43 @@ int mmvae_kid_sums(const float* X, const float* Y, const int* idx_x, const int* 
                    mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cross-modal correlation of generations (TorchMMVAE.cross_modal_correlation; csrc/cca.hip): the canonical-correlation
+ * score of image-caption models (Shi et al. 2019), the arithmetic of the reference's cca / apply_weights / apply_pc
+ * (eval/mnistsvhn_helper.py:26-78, 149-177), in double, no atomics, every sum in a fixed order: two runs give the same bits.
+ *   mmvae_f64_gemm_ld: C (M,N) = A' B (trans_b = 0, B (K,N)) or A' B^T (B (N,K)), A' = A (M,K) with column k multiplied by
+ *     scale[k] (scale NULL: A itself, the bits of the plain product), row-major doubles with leading dimensions lda >= K,
+ *     ldb >= the width of B, ldc >= N: sub-blocks of larger matrices, read and written in place.  The MFMA tile routine of
+ *     mmvae_f64_gemm (64 x 64 per workgroup, k in steps of 4 in order, no K-split); only the (M,N) block of C is written.
+ *     C must not overlap A or B.  1 <= M, N, K <= MMVAE_FRECHET_MAX_F.
+ *   The fit (ops.cca_fit) is composed from mmvae_sym_eig and this product; see DESIGN.md section 7j.
+ *   mmvae_cca_score: a (rows,oa), b (rows,ob) fp32 feature rows; mean_a (oa), mean_b (ob), proj_a (oa,k), proj_b (ob,k)
+ *     doubles.  Per row r: p = (a_r - mean_a) proj_a, q = (b_r - mean_b) proj_b, rows converted and centred in double on
+ *     load, both products on v_mfma_f64_16x16x4_f64 (64 rows and all k columns per workgroup, the features walked in order
+ *     in steps of 4); cos[r] = p . q / (max(|p|, 1e-8) max(|q|, 1e-8)) (F.cosine_similarity's clamp), the three sums of a
+ *     row over its columns in a fixed order.  p and q are never written.  sum[0] = sum_r cos[r]: thread t of 256 sums the
+ *     rows t, t + 256, ... in order, the partials are added in thread order.  1 <= rows <= MMVAE_CCA_MAX_ROWS,
+ *     1 <= oa, ob <= MMVAE_FRECHET_MAX_F, 1 <= k <= MMVAE_CCA_MAX_K.
+ *   mmvae_sentence_features: ids (B,T) int32, emb (V,E) fp32, weights (V) fp32, pc (E) doubles or NULL, out (B,E) fp32.
+ *     One wave per sentence: L = index of the first `eos` + 1, or T without one; f = (sum_{t < L} weights[id_t] emb[id_t])
+ *     / L, the products and the sum in double in token order; with pc, f -= pc (pc . f) (per-lane partials in element
+ *     order, a shuffle butterfly); one rounding to fp32.  Every id must lie in [0, V) (ops.sentence_features checks before
+ *     the call); a token outside adds nothing and nothing outside the tables is read.  1 <= B <= MMVAE_CCA_MAX_ROWS,
+ *     1 <= T <= MMVAE_SENTENCE_MAX_T, 1 <= E <= MMVAE_SENTENCE_MAX_E, V >= 1.
+ *   Anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_CCA_MAX_K 64
+#define MMVAE_CCA_MAX_VIEWS 8
+#define MMVAE_CCA_MAX_ROWS 2147483647L
+#define MMVAE_SENTENCE_MAX_E 1024
+#define MMVAE_SENTENCE_MAX_T 512
+int mmvae_f64_gemm_ld(const double* A, int lda, const double* B, int ldb, double* C, int ldc, const double* scale, int M,
+                      int N, int K, int trans_b, mmvae_stream_t stream);
+int mmvae_cca_score(const float* a, const float* b, const double* mean_a, const double* mean_b, const double* proj_a,
+                    const double* proj_b, double* cos, double* sum, long rows, int oa, int ob, int k, mmvae_stream_t stream);
+int mmvae_sentence_features(const int* ids, const float* emb, const float* weights, const double* pc, float* out, long B,
+                            int T, int E, int V, int eos, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -8,7 +8,9 @@ Three parts:
   * the scoring helpers TorchMMVAE.cross_coherence / joint_coherence (models/evaluation.py) are built from.
 For the MNIST-SVHN benchmark (reference: eval/eval_mnistsvhn.py) DigitClassifier / DigitClassifiers at the end of the file:
 the two LeNet-style digit classifiers, trained and scored on csrc/digits.hip (TorchMMVAE.digit_cross_coherence /
-digit_joint_coherence).  Nothing here imports the models: they import this module.
+digit_joint_coherence).  For the cross-modal correlation (reference: eval/mnistsvhn_helper.py) sif_weights and
+SentenceFeatures after them: the frequency-weighted caption feature (TorchMMVAE.cross_modal_correlation).  Nothing here
+imports the models: they import this module.
 """
 import torch
 import torch.nn as nn
@@ -430,3 +432,58 @@ class DigitClassifiers(nn.Module):
         xm, xs, y = self._split(test, "test", mnist, svhn)
         pred = self.predict(xm, xs)
         return {k: float((pred[k] == y).sum()) / y.shape[0] for k in self.KINDS}
+
+
+# ---- sentence features for the cross-modal correlation (reference: eval/mnistsvhn_helper.py:116-177) ------------------------
+def sif_weights(counts, a=1e-3):
+    """the tokens' smooth-inverse-frequency weights a / (a + count / total) from their occurrence counts (V,), float32"""
+    counts = torch.as_tensor(counts, dtype=torch.float64)
+    if counts.dim() != 1 or counts.numel() < 1 or bool((counts < 0).any()) or float(counts.sum()) <= 0 or not a > 0:
+        raise ValueError("sif_weights: counts are non-negative occurrence counts (V,) with a positive total; a > 0")
+    return (a / (a + counts / counts.sum())).float()
+
+
+class SentenceFeatures:
+    """The caption feature of the cross-modal correlation: the frequency-weighted mean of a caption's word embeddings up to
+    its first `eos` token, with the captions' common component removed once `fit_pc` has found it (ops.sentence_features).
+    `emb` (V, E) is the caller's embedding table (the reference trains FastText on the captions; it cannot be shipped),
+    `weights` (V,) the tokens' weights (sif_weights).  Callable on (B, T, V) one-hot rows or probabilities (the argmax over V
+    is the token) or on (B, T) integer ids -> (B, E) fp32 features on the table's device."""
+
+    def __init__(self, emb, weights, eos=2):
+        if not torch.is_tensor(emb) or emb.dim() != 2 or not torch.is_tensor(weights) or tuple(weights.shape) != emb.shape[:1]:
+            raise ValueError("SentenceFeatures: emb is the (V, E) embedding table, weights (V,) one weight per token")
+        self.emb, self.weights, self.eos, self.pc = emb, weights, int(eos), None
+
+    def ids(self, text):
+        if not torch.is_tensor(text) or text.dim() not in (2, 3):
+            raise ValueError("SentenceFeatures: captions are (B, T, V) one-hot rows or probabilities, or (B, T) ids")
+        if text.dim() == 3:
+            if text.shape[2] != self.emb.shape[0]:
+                raise ValueError(f"SentenceFeatures: captions over {text.shape[2]} tokens, the table holds {self.emb.shape[0]}")
+            text = text.argmax(dim=2)
+        return text
+
+    def __call__(self, text):
+        return ops.sentence_features(self.ids(text), self.emb, self.weights, self.eos, self.pc)
+
+    def unprojected(self, text):
+        """the features with the common component left in (what fit_pc works on)"""
+        return ops.sentence_features(self.ids(text), self.emb, self.weights, self.eos, None)
+
+    def fit_pc(self, texts):
+        """`texts`: an iterable of caption batches.  Sets and returns `pc` (E,) float64: the top eigenvector of the
+        covariance of their features without the projection (streamed moments, ops.sym_eig) -- the reference's top right
+        singular vector of the centred feature matrix up to sign, which the projection f - pc (pc . f) does not see."""
+        state = None
+        for text in texts:
+            f = self.unprojected(text)
+            state = ops.frechet_state(f.shape[1], f.device) if state is None else state
+            ops.frechet_update(state, f)
+        if state is None:
+            raise ValueError("SentenceFeatures.fit_pc: `texts` is empty")
+        _, _, sigma = ops.frechet_moments(state)
+        e = ops.sym_eig(sigma)
+        v = e["vectors"][:, int(e["values"].argmax())]
+        self.pc = (v / torch.linalg.vector_norm(v)).contiguous()
+        return self.pc

@@ -1,7 +1,8 @@
 // Frechet distance of generated images (TorchMMVAE.frechet_distances): the arithmetic of the reference's
 // calculate_frechet_distance (eval/fid_score.py), d^2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2, all in double.
 //   fr_colmean_kernel    batch mean of X (n_b, F) fp32, rows summed in double in a fixed order
-//   f64_tile_kernel      ONE fp64 MFMA tile routine (v_mfma_f64_16x16x4_f64; 64 x 64 tile per workgroup, 32 x 32 per wave)
+//   f64_tile_kernel      ONE fp64 MFMA tile routine (f64_tile.hpp, shared with cca.hip; v_mfma_f64_16x16x4_f64; 64 x 64 tile
+//                        per workgroup, 32 x 32 per wave)
 //                        behind three products: the centred scatter of a batch merged into M2 by Chan's rule (SYRK, upper
 //                        tiles computed, mirrored on the store), C = A B and C = A B^T
 //   fr_merge_mean_kernel mean += delta n_b / (n + n_b), n += n_b
@@ -10,13 +11,8 @@
 //                        communication between workgroups
 //   fr_distance_kernel   the traces and the final sum, one workgroup, fixed order
 // No atomics; every sum has one owner and one order: two runs give the same bits.
-#include "common.hpp"
+#include "f64_tile.hpp"
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-#define FR_TILE 64            // C tile of a workgroup
-#define FR_KT 16              // k-depth of a staged tile
-#define FR_LD (FR_TILE + 2)   // LDS row stride in doubles
 #define EIG_TAU2 1e-30        // tau^2, tau = 1e-15: rotate when c^2 > tau^2 a b
 #define EIG_WIDE_F 256        // above: four waves per pair
 
@@ -44,11 +40,7 @@ __global__ __launch_bounds__(256) void fr_colmean_kernel(const float* __restrict
   if (wave == 0 && j < F) mean_b[j] = ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane])) / (double)nb;
 }
 
-// ---- the fp64 MFMA tile routine --------------------------------------------------------------------------------------------
-// C(i, j) = sum_k a(i, k) b(k, j) over a 64 x 64 tile.  Operand functors return 0 outside the matrix; KFAST says whether k
-// is the contiguous index of the operand's memory (which index the staging threads walk first).
-// v_mfma_f64_16x16x4_f64: lane l feeds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15], one double each; it holds
-// D[row = (l >> 4) + 4 r][col = l & 15] in register r (NOT the f32 forms' row = 4 (l >> 4) + r).
+// ---- the fp64 MFMA tile routine (f64_tile.hpp): the operands and stores of this file --------------------------------------
 struct FrSyrkOp {      // the centred batch: element (i, k) = (double)X[k][i] - mean_b[i]
   const float* X;
   const double* mean_b;
@@ -94,58 +86,8 @@ struct FrChanStore {   // M2[i][j] += v + delta_i delta_j n n_b / (n + n_b), the
 };
 
 template <class OpA, class OpB, class Store>
-__global__ __launch_bounds__(256) void f64_tile_kernel(OpA a, OpB b, Store st, int M, long K) {
-  __shared__ double As[FR_KT][FR_LD], Bs[FR_KT][FR_LD];
-  if (Store::UPPER && blockIdx.x < blockIdx.y) return;      // (workgroup-uniform, before any barrier)
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int i0 = blockIdx.y * FR_TILE, j0 = blockIdx.x * FR_TILE;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, lr = lane & 15, lk = lane >> 4;
-  f64x4 acc[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = f64x4{0.0, 0.0, 0.0, 0.0};
-  for (long k0 = 0; k0 < K; k0 += FR_KT) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < FR_TILE * FR_KT / 256; ++e) {
-      const int idx = tid + 256 * e;
-      const int ia = OpA::KFAST ? idx >> 4 : idx & 63, ka = OpA::KFAST ? idx & 15 : idx >> 6;
-      As[ka][ia] = a(i0 + ia, k0 + ka);
-      const int ib = OpB::KFAST ? idx >> 4 : idx & 63, kb = OpB::KFAST ? idx & 15 : idx >> 6;
-      Bs[kb][ib] = b(j0 + ib, k0 + kb);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k4 = 0; k4 < FR_KT; k4 += 4) {
-      double av[2], bv[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        av[t] = As[k4 + lk][wm + 16 * t + lr];
-        bv[t] = Bs[k4 + lk][wn + 16 * t + lr];
-      }
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mi], bv[ni], acc[mi][ni], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int i = i0 + wm + 16 * mi + lk + 4 * r, j = j0 + wn + 16 * ni + lr;
-        if (i < M && j < M) st(i, j, acc[mi][ni][r]);
-      }
-}
-
-template <class OpA, class OpB, class Store>
 static void fr_launch_tiles(OpA a, OpB b, Store st, int M, long K, hipStream_t s) {
-  const int t = (M + FR_TILE - 1) / FR_TILE;
-  hipLaunchKernelGGL((f64_tile_kernel<OpA, OpB, Store>), dim3(t, t), dim3(256), 0, s, a, b, st, M, K);
+  f64_launch_tiles(a, b, st, M, M, K, s);
 }
 
 // ---- moments ---------------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7i) as a mixin: held-out log-likelihood, latent
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7j) as a mixin: held-out log-likelihood, latent
 classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
-density / coverage and kernel inception distance of generated images and the disentanglement of the latent code.  What they share is here once: the
+density / coverage and kernel inception distance of generated images, the disentanglement of the latent code and the
+cross-modal (canonical) correlation of generations.  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -728,6 +729,115 @@ class EvaluationMixin:
                     else:
                         r[key], r["m"][key] = pair, out["m"]
                 res[m] = r
+        return res
+
+    # ---- cross-modal correlation of generations -------------------------------------------------------
+    def cross_modal_correlation(self, fit_batches, batches, features, k, ridge=1e-12, n_joint=0, eps=None, joint_eps=None):
+        """Canonical-correlation score of generations (Shi et al. 2019, the coherence measure of image-caption models such
+        as CUB): the one coherence metric that needs neither labels nor a classifier.  The arithmetic of the reference's
+        cca (eval/mnistsvhn_helper.py:26-78) in float64 on the device (ops.cca_fit, ops.cca_score; csrc/cca.hip).
+        `features`: {modality: callable -> (rows, o_m) float features}, two modalities at least (for captions
+        coherence.SentenceFeatures); a callable receives batch[m]["data"] for real rows and decoder_dist.loc for generated
+        ones, of whose rows the first B (the batch's) are read.
+          Fit    the real rows of `fit_batches`: every modality's features side by side in model order, streamed into one
+                 moment state (memory does not grow with the rows), then multi-view CCA with `k` joint dimensions.
+          Score  over `batches`, per row the cosine of the two projected, centred features; a (sum, rows) pair per key in
+                 double:
+                   real[(a, b)]    real a against real b: the ceiling the data itself reaches
+                   recon[(a, b)]   both from forward() of the full batch
+                   cross[(g, m)]   real g against m generated from g alone, every ordered pair
+                   joint[(a, b)]   n_joint > 0 only: both decoded from the same n_joint latents z ~ p(z) (`joint_eps`
+                                   (n_joint, D) replaces the draw)
+                 (a, b) run over the pairs of `features` in model order, a before b.  With more than two views a pair
+                 uses its two blocks of the joint projections, as the reference's torch.split does.
+        Per batch forward() runs on the full batch, then once per modality g of `features` in model order.
+        -> {"real", "recon", "cross"[, "joint"]: {pair: mean cosine, a float}, "correlations": [k floats], "k", "n_fit",
+            "widths": {m: o_m}, "condition": {m: lambda_min / lambda_max of m's covariance + ridge I},
+            "sweeps": {"views": {m: sweeps}, "joint": sweeps of the whitened matrix}}.
+        The widths together may not exceed 2048, the eigensolver's limit (a 2048-wide ResNet feature beside a 300-wide
+        sentence feature is outside it: reduce the image feature first).  Deviations from the reference: `k` is required
+        (its Otsu threshold for k=None is not restated); the covariances are float64 from the float32 features.
+        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps` (as frechet_distances).
+        The training noise state, the dropout counters, gradients and the optimiser stay as they are."""
+        who = "cross_modal_correlation"
+        n_joint = int(n_joint)
+        self._need_eval(who, _GENERATIONS, shared_latents=n_joint > 0)
+        names, fit_batches, batches = list(self.vaes.keys()), list(fit_batches), list(batches)
+        if not fit_batches or not batches:
+            raise ValueError(f"{who}: `fit_batches` and `batches` must not be empty")
+        if not isinstance(features, dict) or any(m not in names or not callable(f) for m, f in features.items()):
+            raise ValueError(f"{who}: `features` maps modalities of this model ({names}) to callables")
+        mods = [m for m in names if m in features]
+        if not 2 <= len(mods) <= ops.H.CCA_MAX_VIEWS:
+            raise ValueError(f"{who}: `features` names {len(mods)} modalities (a correlation needs 2 .. "
+                             f"{ops.H.CCA_MAX_VIEWS} views)")
+        for batch in fit_batches + batches:
+            if any(m not in batch or batch[m]["data"] is None for m in names):
+                raise ValueError(f"{who}: every batch must hold every modality (a modality without data)")
+        k, ridge = int(k), float(ridge)
+        if not 1 <= k <= ops.H.CCA_MAX_K or not ridge > 0.0 or n_joint < 0:
+            raise ValueError(f"{who}: k = {k} (1 .. {ops.H.CCA_MAX_K}), ridge = {ridge} (positive), n_joint = {n_joint}")
+        n_fit = sum(len(b[mods[0]]["data"]) for b in fit_batches)
+        if n_fit < 2:
+            raise ValueError(f"{who}: {n_fit} rows to fit (a covariance needs two rows)")
+        dims = {}
+
+        def feat(m, x, keep=None):
+            f = features[m](x)
+            if not torch.is_tensor(f) or f.dim() != 2 or not f.is_floating_point():
+                raise ValueError(f"{who}: the extractor of {m!r} must return float (rows, o) features")
+            if dims.setdefault(m, f.shape[1]) != f.shape[1]:
+                raise ValueError(f"{who}: the extractor of {m!r} returned o = {f.shape[1]} after o = {dims[m]}")
+            return f.float() if keep is None else f[:keep].float()
+
+        pairs = list(itertools.combinations(mods, 2))
+        sums = {}
+
+        def score(table, key, fa, fb):
+            a, b = key
+            _, s = ops.cca_score(fa, fb, fit["means"][at[a]], fit["means"][at[b]], fit["projections"][at[a]],
+                                 fit["projections"][at[b]])
+            old = sums.get((table, key))
+            sums[(table, key)] = (s if old is None else old[0] + s, fa.shape[0] + (0 if old is None else old[1]))
+
+        with self._eval_noise(eps):
+            state = None
+            for batch in fit_batches:
+                rows = torch.cat([feat(m, batch[m]["data"]) for m in mods], dim=1)
+                if state is None:
+                    widths = ops._cca_widths(who, [dims[m] for m in mods], rows.shape[1])
+                    if k > min(widths):
+                        raise ValueError(f"{who}: k = {k} joint dimensions, the narrowest view has {min(widths)} features")
+                    state = ops.frechet_state(rows.shape[1], rows.device)
+                ops.frechet_update(state, rows)
+            n_fit, mu, sigma = ops.frechet_moments(state)
+            fit = ops.cca_fit(mu, sigma, widths, k, ridge)
+            at = {m: i for i, m in enumerate(mods)}
+            for batch in batches:
+                B = len(batch[mods[0]]["data"])
+                real = {m: feat(m, batch[m]["data"]) for m in mods}
+                for a, b in pairs:
+                    score("real", (a, b), real[a], real[b])
+                out = self.forward(batch)
+                recon = {m: feat(m, out.mods[m].decoder_dist.loc, B) for m in mods}
+                for a, b in pairs:
+                    score("recon", (a, b), recon[a], recon[b])
+                for g in mods:
+                    out = self.forward(self._given_only(batch, [g]))
+                    for m in mods:
+                        if m != g:
+                            score("cross", (g, m), real[g], feat(m, out.mods[m].decoder_dist.loc, B))
+            if n_joint > 0:
+                z = self._prior_sample(n_joint, joint_eps, who)
+                joint = {m: feat(m, self.vaes[m].dec({"latents": z, "masks": None})[0]) for m in mods}
+                for a, b in pairs:
+                    score("joint", (a, b), joint[a], joint[b])
+            res = {t: {} for t in ("real", "recon", "cross") + (("joint",) if n_joint > 0 else ())}
+            for (table, key), (s, rows) in sums.items():
+                res[table][key] = float(s) / rows
+        res.update({"correlations": fit["correlations"].tolist(), "k": k, "n_fit": n_fit, "widths": dict(zip(mods, widths)),
+                    "condition": dict(zip(mods, fit["condition"])),
+                    "sweeps": {"views": dict(zip(mods, fit["sweeps"]["views"])), "joint": fit["sweeps"]["joint"]}})
         return res
 
     # ---- disentanglement of the latent code (DESIGN.md section 7h) ----------------------------------------------------------

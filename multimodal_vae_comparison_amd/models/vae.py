@@ -34,7 +34,8 @@ class DencoderFactory(object):
 # the evaluation metrics of TorchMMVAE (models/evaluation.py) -> whom each is built for: a unimodal VAE refuses them by name
 MIXER_METRICS = dict.fromkeys(("latents_for", "classify_latents", "cross_coherence", "joint_coherence",
                                "digit_cross_coherence", "digit_joint_coherence", "analyse_latents",
-                               "frechet_distances", "manifold_metrics", "kernel_distances", "disentanglement"),
+                               "frechet_distances", "manifold_metrics", "kernel_distances", "disentanglement",
+                               "cross_modal_correlation"),
                               "the multimodal mixers")
 MIXER_METRICS["estimate_log_likelihood"] = "the multimodal mixers poe, moe and mopoe"
 
