@@ -97,20 +97,7 @@ __device__ __forceinline__ void cca_project(const float* __restrict__ X, const d
     }
     __syncthreads();
     if (k0 + FR_KT < o) cca_fetch(st, X, mean, P, rows, r0, o, k, k0 + FR_KT);      // (workgroup-uniform)
-#pragma unroll
-    for (int k4 = 0; k4 < FR_KT; k4 += 4) {
-      double av[2], bv[2];
-#pragma unroll
-      for (int t = 0; t < 2; ++t) {
-        av[t] = As[k4 + lk][wm + 16 * t + lr];
-        bv[t] = Bs[k4 + lk][wn + 16 * t + lr];
-      }
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[mi], bv[ni], acc[mi][ni], 0, 0, 0);
-    }
+    f64_mfma_slab<FR_KT, FR_LD, FR_KT / 4>(As, Bs, wm, wn, lr, lk, acc);
   }
 }
 

@@ -2,9 +2,9 @@
 // (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020), from three kinds of pair-distance pass over two
 // feature sets, squared distances in double: d^2(x, y) = max(0, (|x|^2 + |y|^2) - 2 x . y).
 //   mf_sqnorms_kernel   |x_i|^2 summed in double in feature order, one thread per row
-//   mf_tile_kernel      ONE rectangular fp64 MFMA tile routine (v_mfma_f64_16x16x4_f64; 64 x 64 tile per workgroup, 32 x 32
-//                       per wave) for the Gram product B A^T of fp32 rows converted on load; a workgroup owns 64 rows of B
-//                       and walks a chunk of column tiles of A; every tile's d^2 goes through LDS to the epilogue:
+//   mf_tile_kernel      the fp64 pair-tile walker of pair_tile.hpp (lane layout, staging and LDS documented there) for the
+//                       Gram product B A^T: a workgroup owns 64 rows of B and walks a chunk of column tiles of A; every
+//                       tile's d^2 goes through LDS to the epilogue:
 //                         radii  each row keeps its smallest values (the diagonal skipped by index)
 //                         cross  each row counts the columns whose sphere holds it and keeps its smallest d^2
 //                       the N x M matrix is never written to memory
@@ -13,35 +13,15 @@
 // smallest" do not depend on how the columns are split: two runs and any two split plans give the same bits.
 #include <math.h>
 
-#include "common.hpp"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-#define MF_TILE 64                 // tile of a workgroup: rows of B x rows of A
-#define MF_KT 32                   // feature depth of a staged tile
-#define MF_LDS (MF_TILE + 2)       // LDS row stride of a staged operand, in doubles
-#define MF_LDD (MF_TILE + 4)       // LDS row stride of the d^2 tile: the epilogue's 16 rows x 4 quarters of a wave spread
-                                   // over the banks
-#define MF_LOADS (MF_TILE * MF_KT / 256)      // elements of each operand a thread stages per step
-#define MF_SLOTS 512               // workgroups wanted in flight: 256 CUs x 2 (34.5 KB of LDS each)
-#define MF_MIN_TILES 4             // column tiles per chunk at least (a chunk ends in a merge of four lists per row)
+#include "pair_tile.hpp"
 
 static bool mf_rows_ok(long n) { return n >= 1 && n <= MMVAE_MANIFOLD_MAX_ROWS; }
 static bool mf_f_ok(int F) { return F >= 1 && F <= MMVAE_FRECHET_MAX_F; }
 static bool mf_k_ok(int k) { return k >= 1 && k <= MMVAE_MANIFOLD_MAX_K; }
-static int mf_tiles(long n) { return (int)((n + MF_TILE - 1) / MF_TILE); }
 
 // -> column tiles per chunk and the chunks that hold at least one tile; `chunks` 0: the default plan
 static void mf_plan(long rows, long cols, int chunks, int* tiles_per_chunk, int* n_chunks) {
-  const int rt = mf_tiles(rows), ct = mf_tiles(cols);
-  if (chunks <= 0) {
-    chunks = (MF_SLOTS + rt - 1) / rt;
-    const int most = (ct + MF_MIN_TILES - 1) / MF_MIN_TILES;
-    if (chunks > most) chunks = most;
-  }
-  if (chunks > ct) chunks = ct;
-  *tiles_per_chunk = (ct + chunks - 1) / chunks;
-  *n_chunks = (ct + *tiles_per_chunk - 1) / *tiles_per_chunk;
+  pair_plan(pt_tiles(rows), pt_tiles(cols), chunks, PT_SLOTS, PT_MIN_TILES, tiles_per_chunk, n_chunks);
 }
 
 // ---- squared norms -------------------------------------------------------------------------------------------------------
@@ -92,144 +72,115 @@ struct MfKeep {
   }
 };
 
-// ---- the tile routine ---------------------------------------------------------------------------------------------------------
-// v_mfma_f64_16x16x4_f64: lane l feeds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15], one double each; it holds
-// D[row = (l >> 4) + 4 r][col = l & 15] in register r.
-// grid (chunks, row tiles), 256 threads.  Workgroup (c, t) owns the rows [64 t, 64 t + 64) of B against the column tiles
-// [c tpc, (c + 1) tpc) of A.  The fp32 elements of the next step (of the next tile after a tile's last) are fetched into
-// registers while the MFMAs of this one run.  Epilogue thread e = 4 row + quarter reads the columns quarter, quarter + 4,
-// ... of its row.
+// ---- the tile kernel: the policies of pair_tile_walk ---------------------------------------------------------------------------
+// rows i0 + r of B and j0 + r of A, addressed directly
+struct MfRows {
+  const float *Bm, *Am;
+  long i0, rows_b, rows_a;
+  int F;
+  __device__ __forceinline__ void columns(long) {}
+  __device__ __forceinline__ float b(int e, int k0) const {
+    const int r = threadIdx.x / PT_KT + (256 / PT_KT) * e, kk = threadIdx.x % PT_KT;
+    return (k0 + kk < F && i0 + r < rows_b) ? Bm[(size_t)(i0 + r) * F + k0 + kk] : 0.0f;
+  }
+  __device__ __forceinline__ float a(int e, long j0, int k0) const {
+    const int r = threadIdx.x / PT_KT + (256 / PT_KT) * e, kk = threadIdx.x % PT_KT;
+    return (k0 + kk < F && j0 + r < rows_a) ? Am[(size_t)(j0 + r) * F + k0 + kk] : 0.0f;
+  }
+};
+
+// d^2 from the norms and the dot product, and what a row keeps of it:
 // KEEP > 0, the radii (B == A, k <= KEEP): part (chunks, rows_b, k) = the k smallest d^2 of the chunk per row, ascending,
 //   +inf where fewer were met.
 // KEEP == 0, the cross pass: part (chunks, rows_b, 2) = (number of columns i with d^2 <= rad2_a[i], smallest d^2) of the
-//   chunk per row.
+//   chunk per row; rad2_a of the tile's columns is staged in LDS with the d^2 tile (this instantiation's 512 bytes).
+template <int KEEP>
+struct MfEpilogue {
+  static constexpr bool RADII = KEEP > 0;
+  const double *nb, *na, *rad2_a;
+  long i0, rows_b, rows_a;
+  MfKeep<RADII ? KEEP : 1> keep;
+  int count;
+  double nearest;
+  __device__ __forceinline__ static double* rad_s() {
+    __shared__ double s[PT_TILE];
+    return s;
+  }
+  __device__ __forceinline__ void stage(int t) {
+    const long j = (long)t * PT_TILE + threadIdx.x;
+    if constexpr (!RADII)
+      if (threadIdx.x < PT_TILE) rad_s()[threadIdx.x] = j < rows_a ? rad2_a[j] : 0.0;
+  }
+  __device__ __forceinline__ double column(int t, int cj) const {
+    const long j = (long)t * PT_TILE + cj;
+    return j < rows_a ? na[j] : 0.0;
+  }
+  __device__ __forceinline__ double element(double ncol, int ci, double g) const {
+    const double nrow = i0 + ci < rows_b ? nb[i0 + ci] : 0.0;
+    return fmax(0.0, (nrow + ncol) - 2.0 * g);
+  }
+  __device__ __forceinline__ void tile(const double* lds, int t) {
+    const int erow = threadIdx.x >> 2, equarter = threadIdx.x & 3;
+    const long j0 = (long)t * PT_TILE, ei = i0 + erow;
+    if (ei >= rows_b) return;
+#pragma unroll 4
+    for (int c = equarter; c < PT_TILE; c += 4) {
+      const long j = j0 + c;
+      if (j >= rows_a) break;
+      const double d2 = lds[erow * PT_LDD + c];
+      if constexpr (RADII) {
+        if (j != ei) keep.put(d2);
+      } else {
+        count += d2 <= rad_s()[c] ? 1 : 0;
+        nearest = fmin(nearest, d2);
+      }
+    }
+  }
+  // the four quarters of a row are four neighbouring lanes
+  __device__ __forceinline__ void write(double* __restrict__ part, int k) {
+    const int lane = threadIdx.x & 63, equarter = threadIdx.x & 3;
+    const long ei = i0 + (threadIdx.x >> 2);
+    double* out = part + ((size_t)blockIdx.x * rows_b + ei) * k;
+    if constexpr (RADII) {
+#pragma unroll
+      for (int q = 1; q < 4; ++q)
+#pragma unroll
+        for (int s = 0; s < KEEP; ++s) {
+          const double other = __shfl(keep.v[s], (lane & ~3) + q, 64);
+          if (equarter == 0) keep.put(other);
+        }
+      if (equarter == 0 && ei < rows_b) {
+#pragma unroll
+        for (int s = 0; s < KEEP; ++s)
+          if (s < k) out[s] = keep.v[s];
+      }
+    } else {
+#pragma unroll
+      for (int o = 1; o < 4; o <<= 1) {
+        count += __shfl_xor(count, o, 64);
+        nearest = fmin(nearest, __shfl_xor(nearest, o, 64));
+      }
+      if (equarter == 0 && ei < rows_b) {
+        out[0] = (double)count;
+        out[1] = nearest;
+      }
+    }
+  }
+};
+
+// grid (chunks, row tiles), 256 threads.  Workgroup (c, t) owns the rows [64 t, 64 t + 64) of B against the column tiles
+// [c tpc, (c + 1) tpc) of A; k = 2 for the cross pass.
 template <int KEEP>
 __global__ __launch_bounds__(256, 2) void mf_tile_kernel(const float* __restrict__ Bm, const double* __restrict__ nb,
                                                       const float* __restrict__ Am, const double* __restrict__ na,
                                                       const double* __restrict__ rad2_a, double* __restrict__ part,
                                                       long rows_b, long rows_a, int F, int k, int tpc) {
-  constexpr bool RADII = KEEP > 0;
-  __shared__ double lds[MF_TILE * MF_LDD];      // the d^2 tile; the staged operands live in its first 2 MF_KT MF_LDS doubles
-  __shared__ double rad_s[MF_TILE];             // cross pass: rad2_a of the tile's columns, staged with the d^2 tile
-  double(*Bs)[MF_LDS] = reinterpret_cast<double(*)[MF_LDS]>(lds);
-  double(*As)[MF_LDS] = reinterpret_cast<double(*)[MF_LDS]>(lds + MF_KT * MF_LDS);
-  static_assert(2 * MF_KT * MF_LDS <= MF_TILE * MF_LDD, "the staged operands fit inside the d^2 tile");
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long i0 = (long)blockIdx.y * MF_TILE;
-  const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, lr = lane & 15, lk = lane >> 4;
-  const int erow = tid >> 2, equarter = tid & 3;
-  const long ei = i0 + erow;
-  const int ct = (int)((rows_a + MF_TILE - 1) / MF_TILE);
-  const int t0 = blockIdx.x * tpc, t1 = min(ct, t0 + tpc);
-  MfKeep<RADII ? KEEP : 1> keep;
-  keep.clear();
-  int count = 0;
-  double nearest = INFINITY;
-  float pb[MF_LOADS], pa[MF_LOADS];
-  // element e of a thread: row (tid + 256 e) / MF_KT of the tile, feature (tid + 256 e) % MF_KT of the step
-  auto fetch = [&](long j0, int k0) {
-#pragma unroll
-    for (int e = 0; e < MF_LOADS; ++e) {
-      const int idx = tid + 256 * e, r = idx / MF_KT, kk = idx % MF_KT;
-      const bool kin = k0 + kk < F;
-      pb[e] = (kin && i0 + r < rows_b) ? Bm[(size_t)(i0 + r) * F + k0 + kk] : 0.0f;
-      pa[e] = (kin && j0 + r < rows_a) ? Am[(size_t)(j0 + r) * F + k0 + kk] : 0.0f;
-    }
-  };
-  if (t0 < t1) fetch((long)t0 * MF_TILE, 0);
-  for (int t = t0; t < t1; ++t) {
-    const long j0 = (long)t * MF_TILE;
-    f64x4 acc[2][2];
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) acc[mi][ni] = f64x4{0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < F; k0 += MF_KT) {
-      __syncthreads();      // (the previous tile's epilogue, or the previous step's MFMAs, have read the LDS)
-#pragma unroll
-      for (int e = 0; e < MF_LOADS; ++e) {
-        const int idx = tid + 256 * e, r = idx / MF_KT, kk = idx % MF_KT;
-        Bs[kk][r] = (double)pb[e];
-        As[kk][r] = (double)pa[e];
-      }
-      __syncthreads();
-      if (k0 + MF_KT < F)
-        fetch(j0, k0 + MF_KT);
-      else if (t + 1 < t1)
-        fetch(j0 + MF_TILE, 0);
-#pragma unroll 2
-      for (int k4 = 0; k4 < MF_KT; k4 += 4) {
-        double bv[2], av[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          bv[u] = Bs[k4 + lk][wm + 16 * u + lr];
-          av[u] = As[k4 + lk][wn + 16 * u + lr];
-        }
-#pragma unroll
-        for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(bv[mi], av[ni], acc[mi][ni], 0, 0, 0);
-      }
-    }
-    __syncthreads();        // (the last MFMAs have read the staged operands the tile overwrites)
-    if (!RADII && tid < MF_TILE) rad_s[tid] = j0 + tid < rows_a ? rad2_a[j0 + tid] : 0.0;
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      const int cj = wn + 16 * ni + lr;
-      const double ncol = j0 + cj < rows_a ? na[j0 + cj] : 0.0;
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int ci = wm + 16 * mi + lk + 4 * r;
-          const double nrow = i0 + ci < rows_b ? nb[i0 + ci] : 0.0;
-          lds[ci * MF_LDD + cj] = fmax(0.0, (nrow + ncol) - 2.0 * acc[mi][ni][r]);
-        }
-    }
-    __syncthreads();
-    if (ei < rows_b) {
-#pragma unroll 4
-      for (int c = equarter; c < MF_TILE; c += 4) {
-        const long j = j0 + c;
-        if (j >= rows_a) break;
-        const double d2 = lds[erow * MF_LDD + c];
-        if (RADII) {
-          if (j != ei) keep.put(d2);
-        } else {
-          count += d2 <= rad_s[c] ? 1 : 0;
-          nearest = fmin(nearest, d2);
-        }
-      }
-    }
-  }
-  // the four quarters of a row are four neighbouring lanes
-  if (RADII) {
-#pragma unroll
-    for (int q = 1; q < 4; ++q)
-#pragma unroll
-      for (int s = 0; s < KEEP; ++s) {
-        const double other = __shfl(keep.v[s], (lane & ~3) + q, 64);
-        if (equarter == 0) keep.put(other);
-      }
-    if (equarter == 0 && ei < rows_b) {
-      double* out = part + ((size_t)blockIdx.x * rows_b + ei) * k;
-#pragma unroll
-      for (int s = 0; s < KEEP; ++s)
-        if (s < k) out[s] = keep.v[s];
-    }
-  } else {
-#pragma unroll
-    for (int o = 1; o < 4; o <<= 1) {
-      count += __shfl_xor(count, o, 64);
-      nearest = fmin(nearest, __shfl_xor(nearest, o, 64));
-    }
-    if (equarter == 0 && ei < rows_b) {
-      double* out = part + ((size_t)blockIdx.x * rows_b + ei) * 2;
-      out[0] = (double)count;
-      out[1] = nearest;
-    }
-  }
+  const long i0 = (long)blockIdx.y * PT_TILE;
+  const int t0 = blockIdx.x * tpc, t1 = min(pt_tiles(rows_a), t0 + tpc);
+  MfEpilogue<KEEP> epi{nb, na, rad2_a, i0, rows_b, rows_a, {}, 0, INFINITY};
+  epi.keep.clear();
+  pair_tile_walk(MfRows{Bm, Am, i0, rows_b, rows_a, F}, epi, F, t0, t1);
+  epi.write(part, k);
 }
 
 // ---- merges: one thread per row, the chunks in order -----------------------------------------------------------------------
@@ -283,7 +234,7 @@ extern "C" size_t mmvae_manifold_ws_doubles(long rows, long cols, int k, int chu
 extern "C" int mmvae_manifold_sqnorms(const float* X, double* n2, long rows, int F, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(X && n2);
   if (!mf_rows_ok(rows) || !mf_f_ok(F)) return MMVAE_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(mf_sqnorms_kernel, dim3(mf_tiles(rows)), dim3(256), 0, (hipStream_t)stream, X, n2, rows, F);
+  hipLaunchKernelGGL(mf_sqnorms_kernel, dim3(pt_tiles(rows)), dim3(256), 0, (hipStream_t)stream, X, n2, rows, F);
   return mmvae_launch_status();
 }
 
@@ -294,7 +245,7 @@ extern "C" int mmvae_manifold_radii(const float* X, const double* n2, double* ws
   hipStream_t s = (hipStream_t)stream;
   int tpc, n;
   mf_plan(rows, rows, chunks, &tpc, &n);
-  const dim3 grid(n, mf_tiles(rows));
+  const dim3 grid(n, pt_tiles(rows));
   const double* none = nullptr;
   // the registers of a row's lists follow k: 4, 8 or MMVAE_MANIFOLD_MAX_K slots per epilogue thread
   if (k <= 4)
@@ -316,7 +267,7 @@ extern "C" int mmvae_manifold_cross(const float* B, const double* nb, const floa
   hipStream_t s = (hipStream_t)stream;
   int tpc, n;
   mf_plan(rows_b, rows_a, chunks, &tpc, &n);
-  hipLaunchKernelGGL((mf_tile_kernel<0>), dim3(n, mf_tiles(rows_b)), dim3(256), 0, s, B, nb, A, na, rad2_a, ws, rows_b,
+  hipLaunchKernelGGL((mf_tile_kernel<0>), dim3(n, pt_tiles(rows_b)), dim3(256), 0, s, B, nb, A, na, rad2_a, ws, rows_b,
                      rows_a, F, 2, tpc);
   hipLaunchKernelGGL(mf_merge_cross_kernel, dim3((unsigned)((rows_b + 255) / 256)), dim3(256), 0, s, ws, count, mind2, rows_b,
                      n);

@@ -3659,6 +3659,36 @@ def tsne_embed(X, perplexity=30.0, max_iter=1000, seed=123, init=None, lr="auto"
             "beta": beta}
 
 
+# ---- checks shared by the feature-set metrics (Frechet, manifold, KID) and the chunked kernels --------------------------------
+def _feature_rows(who, what, X, least=1, most=None, why="", finite=True):
+    """contiguous fp32 (rows, F) or ValueError: shape, dtype, the limit on F, `least` .. `most` rows (`why`: the caller's
+    clause on that limit), finite values (`finite` False: the caller checks them after its own comparisons)"""
+    if not torch.is_tensor(X) or X.dim() != 2 or not X.is_floating_point():
+        said = f"{tuple(X.shape)}, {X.dtype}" if torch.is_tensor(X) else type(X).__name__
+        raise ValueError(f"{who}: {what} is {said}; floating (rows, F) features")
+    rows, F = X.shape
+    if not 1 <= F <= H.FRECHET_MAX_F:
+        raise ValueError(f"{who}: {what} has F = {F} features (1 .. {H.FRECHET_MAX_F} are on the MI355X path)")
+    if rows < least or (most is not None and rows > most):
+        raise ValueError(f"{who}: {what} has {rows} rows ({why})")
+    X = H.f32c(X.detach())
+    if finite:
+        _finite(who, what, X)
+    return X
+
+
+def _finite(who, what, X):
+    if not bool(torch.isfinite(X).all()):
+        raise ValueError(f"{who}: {what} holds values that are not finite")
+
+
+def _chunks(who, chunks, what="column chunks"):
+    chunks = int(chunks)
+    if chunks < 0:
+        raise ValueError(f"{who}: chunks = {chunks} (0: the default plan, or a positive number of {what})")
+    return chunks
+
+
 # ---- Frechet distance of feature sets (csrc/frechet.hip): float64, forward only, no autograd --------------------------------
 def _frechet_f(who, F):
     F = int(F)
@@ -3688,14 +3718,12 @@ def frechet_update(state, feats):
     """fold the rows of feats (n_b, F) into the state: batch mean and centred scatter in double (one tiled SYRK on the
     fp64 MFMA), merged by Chan's rule.  Memory does not grow with the number of rows folded."""
     F = _frechet_state_f("frechet_update", state)
-    if feats.dim() != 2 or feats.shape[1] != F or not feats.is_floating_point():
-        raise ValueError(f"frechet_update: features of shape {tuple(feats.shape)}, {feats.dtype}; the state holds floating "
-                         f"(rows, {F}) (1 .. {H.FRECHET_MAX_F} features are on the MI355X path)")
+    feats = _feature_rows("frechet_update", "feats", feats, least=0, finite=False)
+    if feats.shape[1] != F:
+        raise ValueError(f"frechet_update: feats has F = {feats.shape[1]} features; the state holds floating (rows, {F})")
     if feats.shape[0] == 0:
         return state
-    feats = H.f32c(feats.detach())
-    if not bool(torch.isfinite(feats).all()):
-        raise ValueError("frechet_update: the features hold values that are not finite")
+    _finite("frechet_update", "feats", feats)
     ws = torch.empty(F, dtype=torch.float64, device=state.device)
     _call("mmvae_frechet_update", H.ptr(state), H.ptr(feats), H.ptr(ws), feats.shape[0], F, H.stream())
     return state
@@ -3785,29 +3813,8 @@ def _manifold_k(who, k):
 
 
 def _manifold_rows(who, what, X, least=1):
-    """contiguous fp32 (rows, F) or ValueError: shape, dtype, the limits, at least `least` rows, finite values"""
-    if not torch.is_tensor(X) or X.dim() != 2 or not X.is_floating_point():
-        said = f"{tuple(X.shape)}, {X.dtype}" if torch.is_tensor(X) else type(X).__name__
-        raise ValueError(f"{who}: {what} is {said}; floating (rows, F) features")
-    rows, F = X.shape
-    if not 1 <= F <= H.FRECHET_MAX_F:
-        raise ValueError(f"{who}: {what} has F = {F} features (1 .. {H.FRECHET_MAX_F} are on the MI355X path)")
-    if not least <= rows <= H.MANIFOLD_MAX_ROWS:
-        raise ValueError(f"{who}: {what} has {rows} rows ({least} .. {H.MANIFOLD_MAX_ROWS} are on the MI355X path; "
-                         f"the k-th neighbour needs k + 1 rows)")
-    X = X.detach()
-    X = X.float() if X.dtype != torch.float32 else X
-    X = X.contiguous()
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError(f"{who}: {what} holds values that are not finite")
-    return X
-
-
-def _manifold_chunks(who, chunks):
-    chunks = int(chunks)
-    if chunks < 0:
-        raise ValueError(f"{who}: chunks = {chunks} (0: the default plan, or a positive number of column chunks)")
-    return chunks
+    return _feature_rows(who, what, X, least, H.MANIFOLD_MAX_ROWS, f"{least} .. {H.MANIFOLD_MAX_ROWS} are on the MI355X "
+                                                                     f"path; the k-th neighbour needs k + 1 rows")
 
 
 def _manifold_sqnorms(X):
@@ -3844,7 +3851,7 @@ def manifold_radii(X, k, chunks=0):
     left out by index (a duplicate row is a neighbour at distance 0).  d^2 = max(0, (|x|^2 + |y|^2) - 2 x . y) in double, the
     Gram product on the fp64 MFMA; the N x N matrix is never written.  `chunks`: how many workgroups share a row's columns
     (0: the default plan); the result does not depend on it, bit for bit."""
-    k, chunks = _manifold_k("manifold_radii", k), _manifold_chunks("manifold_radii", chunks)
+    k, chunks = _manifold_k("manifold_radii", k), _chunks("manifold_radii", chunks)
     X = _manifold_rows("manifold_radii", "X", X, least=k + 1)
     return _manifold_radii(X, _manifold_sqnorms(X), k, chunks)
 
@@ -3865,7 +3872,7 @@ def manifold_cross(queries, manifold, rad2, chunks=0):
     """query rows (Nq,F) against manifold rows (Na,F) with their squared radii rad2 (Na,) float64
     -> (count (Nq,) int32 = the number of manifold rows whose sphere holds the query, d^2 <= rad^2: a point on a sphere is
         inside; mind2 (Nq,) float64 = the query's smallest squared distance to the manifold rows)."""
-    chunks = _manifold_chunks("manifold_cross", chunks)
+    chunks = _chunks("manifold_cross", chunks)
     B = _manifold_rows("manifold_cross", "queries", queries)
     A = _manifold_rows("manifold_cross", "manifold", manifold)
     if A.shape[1] != B.shape[1]:
@@ -3885,7 +3892,7 @@ def manifold_prdc(real, fake, k=5, chunks=0):
       precision = mean_j [hit_real[j] > 0], recall = mean_i [hit_fake[i] > 0], density = sum_j hit_real[j] / (k M),
       coverage = mean_i [near_real[i] <= rad2_real[i]].
     -> the four as floats (quotients of integer sums: exact counts) and the five per-row tensors on the device."""
-    k, chunks = _manifold_k("manifold_prdc", k), _manifold_chunks("manifold_prdc", chunks)
+    k, chunks = _manifold_k("manifold_prdc", k), _chunks("manifold_prdc", chunks)
     R = _manifold_rows("manifold_prdc", "real", real, least=k + 1)
     G = _manifold_rows("manifold_prdc", "fake", fake, least=k + 1)
     if R.shape[1] != G.shape[1]:
@@ -3903,21 +3910,6 @@ def manifold_prdc(real, fake, k=5, chunks=0):
 
 
 # ---- kernel inception distance of feature sets (csrc/kid.hip): float64 sums of polynomial kernel values, forward only -------
-def _kid_rows(who, what, X):
-    """contiguous fp32 (rows, F) or ValueError: shape, dtype, the limit on F, at least one row"""
-    if not torch.is_tensor(X) or X.dim() != 2 or not X.is_floating_point():
-        said = f"{tuple(X.shape)}, {X.dtype}" if torch.is_tensor(X) else type(X).__name__
-        raise ValueError(f"{who}: {what} is {said}; floating (rows, F) features")
-    rows, F = X.shape
-    if not 1 <= F <= H.FRECHET_MAX_F:
-        raise ValueError(f"{who}: {what} has F = {F} features (1 .. {H.FRECHET_MAX_F} are on the MI355X path)")
-    if not 1 <= rows < 2 ** 31:
-        raise ValueError(f"{who}: {what} has {rows} rows (1 .. 2^31 - 1: the index lists are int32)")
-    X = X.detach()
-    X = X.float() if X.dtype != torch.float32 else X
-    return X.contiguous()
-
-
 def _kid_index(who, what, idx, rows, device):
     """contiguous int32 (S, m) on `device` or ValueError: an integer (S, m) tensor inside the limits, every entry in
     [0, rows) -- one min/max read on the device, before any C call: the kernel does not check"""
@@ -3938,11 +3930,10 @@ def _kid_index(who, what, idx, rows, device):
 
 
 def _kid_kernel(who, F, degree, gamma, coef0, chunks):
-    degree, chunks = int(degree), int(chunks)
+    degree = int(degree)
     if not 1 <= degree <= H.KID_MAX_DEGREE:
         raise ValueError(f"{who}: degree = {degree} (1 .. {H.KID_MAX_DEGREE} are on the MI355X path)")
-    if chunks < 0:
-        raise ValueError(f"{who}: chunks = {chunks} (0: the default plan, or a positive number of column chunks)")
+    chunks = _chunks(who, chunks)
     gamma, coef0 = 1.0 / F if gamma is None else float(gamma), float(coef0)
     if not math.isfinite(gamma) or not math.isfinite(coef0):
         raise ValueError(f"{who}: gamma = {gamma}, coef0 = {coef0} (finite numbers)")
@@ -3952,14 +3943,14 @@ def _kid_kernel(who, F, degree, gamma, coef0, chunks):
 def _kid_sums(who, names, X, Y, idx_x, idx_y, degree, gamma, coef0, chunks):
     """every check of kid_sums, then the C call -> (sums, the int32 index lists handed to it)"""
     (nx, ny), (nix, niy) = names
-    X, Y = _kid_rows(who, nx, X), _kid_rows(who, ny, Y)
+    X, Y = (_feature_rows(who, what, t, 1, 2 ** 31 - 1, "1 .. 2^31 - 1: the index lists are int32", finite=False)
+            for what, t in ((nx, X), (ny, Y)))      # (finite values: after the comparisons of the two sets)
     if X.shape[1] != Y.shape[1]:
         raise ValueError(f"{who}: {nx} has F = {X.shape[1]} features, {ny} F = {Y.shape[1]}")
     if X.device != Y.device:
         raise ValueError(f"{who}: {nx} is on {X.device}, {ny} on {Y.device}")
-    for what, t in ((nx, X), (ny, Y)):
-        if not bool(torch.isfinite(t).all()):
-            raise ValueError(f"{who}: {what} holds values that are not finite")
+    _finite(who, nx, X)
+    _finite(who, ny, Y)
     F = X.shape[1]
     degree, gamma, coef0, chunks = _kid_kernel(who, F, degree, gamma, coef0, chunks)
     if torch.is_tensor(idx_x) and torch.is_tensor(idx_y) and idx_x.shape != idx_y.shape:
@@ -4284,9 +4275,7 @@ def aggregate_posterior(z, loc, scale, laplace=False, labels=None, chunks=0):
     default plan); two plans regroup fp64 sums (agreement to rounding, not bit for bit), two runs with one plan give the
     same bits.  A z that lies so far from its own posterior that exp overflows raises FloatingPointError."""
     who = "aggregate_posterior"
-    chunks = int(chunks)
-    if chunks < 0:
-        raise ValueError(f"{who}: chunks = {chunks} (0: the default plan, or a positive number of chunks)")
+    chunks = _chunks(who, chunks, "chunks")
     z = _aggpost_rows(who, "z", z)
     loc, scale = _aggpost_rows(who, "loc", loc, z), _aggpost_rows(who, "scale", scale, z)
     if not bool((scale > 0).all()):
