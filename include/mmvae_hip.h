@@ -1154,6 +1154,59 @@ int mmvae_sentence_features(const int* ids, const float* emb, const float* weigh
                             int T, int E, int V, int eos, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Latent cluster analysis (TorchMMVAE.cluster_latents; csrc/cluster.hip): k-means (Lloyd) with
+ * `restarts` independent fits side by side, the statistics of a partition and the silhouette sums.  X (rows, F) fp32 rows,
+ * read as double; centres / means (restarts, C, F) doubles; labels (restarts, rows) int32 in [0, C).
+ *   mmvae_cluster_assign: d^2[i, c] = sum_f (x_if - mu_cf)^2 by direct differences, f in order.  given = 0: labels[r, i] =
+ *     argmin_c d^2 (a tie goes to the lowest c) is WRITTEN and d2[r, i] = its d^2; given = 1: labels is READ and d2[r, i] =
+ *     d^2[i, labels[r, i]] (+inf for a label outside [0, C)).
+ *   mmvae_cluster_means: counts[r, c] = n_c; means[r, c, :] = (sum of the rows of cluster c, in index order) / n_c; the
+ *     entries of a cluster without rows are left as they are.
+ *   mmvae_cluster_spread: from labels and d2 (restarts, rows): counts, within[r, c] = sum_{i in c} d2[r, i], wdist[r, c] =
+ *     sum_{i in c} sqrt(d2[r, i]), rows in index order; inertia[r] = sum_c within[r, c], c in order.
+ *   mmvae_cluster_lloyd: enqueues the iterations it0 .. it0 + n_iter - 1 (numbered from 1; it0 + n_iter - 1 <= max_iter <=
+ *     MMVAE_CLUSTER_MAX_ITER) for all restarts: two launches per iteration and no host synchronisation.  Iteration t:
+ *     assignment (labels in place); a restart whose labels all equal the previous iteration's (t > 1) has converged: its
+ *     state is written and its centres stay; otherwise the centres become the means (a cluster without rows keeps its
+ *     centre and counts the update).  Workgroups of finished restarts return at once.  ws: int32,
+ *     mmvae_cluster_lloyd_ws_ints(rows, restarts) = restarts x (4 + ceil(rows / 64) + MMVAE_CLUSTER_MAX_K), ZEROED by the
+ *     caller before iteration 1 and carried between calls: (restarts, 4) = (finished, n_iter, converged, unused), then the
+ *     blocks' change records (restarts, ceil(rows / 64)), then (restarts, MMVAE_CLUSTER_MAX_K): per cluster the number of
+ *     updates it had no rows at (their sum is the restart's `empty`).  labels needs no initial value.  A restart not
+ *     finished after max_iter iterations has n_iter = max_iter, converged = 0 (the caller's to write) and needs one more
+ *     mmvae_cluster_assign for its labels.
+ *   mmvae_cluster_sil_sums: S (rows, C) doubles, S[i, c] = sum_{j in c, j != i} sqrt(max(0, (n2_i + n2_j) - 2 x_i . x_j)),
+ *     n2 from mmvae_manifold_sqnorms, the product on the fp64 pair-tile walker of csrc/pair_tile.hpp.  list (padded) int32:
+ *     the row numbers sorted by cluster, every cluster's run padded with -1 to a multiple of 64 (padded = 64 x the tiles of
+ *     all runs; entries outside [0, rows) count as -1); table (chunks, 3) int32 = (cluster, first tile, tile past the last)
+ *     of each chunk, a cluster's chunks consecutive and in order; first (C + 1) int32: cluster c owns the chunks
+ *     [first[c], first[c + 1]) (none: its column of S is 0).  Tile numbers are clamped to the list.  One workgroup per
+ *     (chunk, row tile) writes one partial per row, ws (chunks, rows) doubles = mmvae_cluster_sil_ws_doubles(rows, chunks);
+ *     a merge adds a cluster's chunks in order.  mmvae_cluster_sil_tiles_per_chunk(rows, column tiles, chunks): the column
+ *     tiles a chunk holds at the most (chunks 0: the default plan of mmvae_manifold_chunks; a positive value asks for
+ *     that many chunks of the whole list).
+ *   1 <= rows <= MMVAE_MANIFOLD_MAX_ROWS, 1 <= F <= MMVAE_FRECHET_MAX_F, 1 <= C <= MMVAE_CLUSTER_MAX_K, 1 <= restarts <=
+ *   MMVAE_CLUSTER_MAX_INIT; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.  The size helpers are host
+ *   functions (0 outside the limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_CLUSTER_MAX_K 64
+#define MMVAE_CLUSTER_MAX_INIT 64
+#define MMVAE_CLUSTER_MAX_ITER 1000
+size_t mmvae_cluster_lloyd_ws_ints(long rows, int restarts);
+int mmvae_cluster_sil_tiles_per_chunk(long rows, int col_tiles, int chunks);
+size_t mmvae_cluster_sil_ws_doubles(long rows, int chunks);
+int mmvae_cluster_assign(const float* X, const double* centres, int* labels, double* d2, long rows, int F, int C,
+                         int restarts, int given, mmvae_stream_t stream);
+int mmvae_cluster_means(const float* X, const int* labels, double* means, int* counts, long rows, int F, int C, int restarts,
+                        mmvae_stream_t stream);
+int mmvae_cluster_spread(const int* labels, const double* d2, int* counts, double* within, double* wdist, double* inertia,
+                         long rows, int C, int restarts, mmvae_stream_t stream);
+int mmvae_cluster_lloyd(const float* X, double* centres, int* labels, int* ws, long rows, int F, int C, int restarts, int it0,
+                        int n_iter, int max_iter, mmvae_stream_t stream);
+int mmvae_cluster_sil_sums(const float* X, const double* n2, const int* list, const int* table, const int* first, double* ws,
+                           double* S, long rows, int F, int C, long padded, int chunks, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -83,6 +83,7 @@ MANIFOLD_MAX_ROWS, MANIFOLD_MAX_K = 16384, 16      # csrc/manifold.hip
 AGGPOST_MAX_ROWS, AGGPOST_MAX_FACTORS, AGGPOST_MAX_DIM = 16384, 8, 256      # csrc/aggpost.hip
 KID_MAX_SUBSET, KID_MAX_SUBSETS, KID_MAX_DEGREE = 16384, 1024, 8      # csrc/kid.hip
 CCA_MAX_K, CCA_MAX_VIEWS, CCA_MAX_ROWS, SENTENCE_MAX_E, SENTENCE_MAX_T = 64, 8, 2 ** 31 - 1, 1024, 512      # csrc/cca.hip
+CLUSTER_MAX_K, CLUSTER_MAX_INIT, CLUSTER_MAX_ITER = 64, 64, 1000      # csrc/cluster.hip
 
 
 class LmeRows(ctypes.Structure):
@@ -337,6 +338,14 @@ SIGNATURES = {
     "mmvae_f64_gemm_ld": (c_i, [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p]),
     "mmvae_cca_score": (c_i, [c_p] * 8 + [c_l, c_i, c_i, c_i, c_p]),
     "mmvae_sentence_features": (c_i, [c_p] * 5 + [c_l, c_i, c_i, c_i, c_i, c_p]),
+    "mmvae_cluster_lloyd_ws_ints": (c_sz, [c_l, c_i]),
+    "mmvae_cluster_sil_tiles_per_chunk": (c_i, [c_l, c_i, c_i]),
+    "mmvae_cluster_sil_ws_doubles": (c_sz, [c_l, c_i]),
+    "mmvae_cluster_assign": (c_i, [c_p] * 4 + [c_l, c_i, c_i, c_i, c_i, c_p]),
+    "mmvae_cluster_means": (c_i, [c_p] * 4 + [c_l, c_i, c_i, c_i, c_p]),
+    "mmvae_cluster_spread": (c_i, [c_p] * 6 + [c_l, c_i, c_i, c_p]),
+    "mmvae_cluster_lloyd": (c_i, [c_p] * 4 + [c_l] + [c_i] * 6 + [c_p]),
+    "mmvae_cluster_sil_sums": (c_i, [c_p] * 7 + [c_l, c_i, c_i, c_l, c_i, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

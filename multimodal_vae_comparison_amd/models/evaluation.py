@@ -1,7 +1,7 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7j) as a mixin: held-out log-likelihood, latent
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7k) as a mixin: held-out log-likelihood, latent
 classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
-density / coverage and kernel inception distance of generated images, the disentanglement of the latent code and the
-cross-modal (canonical) correlation of generations.  What they share is here once: the
+density / coverage and kernel inception distance of generated images, the disentanglement of the latent code, the
+cross-modal (canonical) correlation of generations and the cluster analysis of the latents.  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -335,6 +335,90 @@ class EvaluationMixin:
             out["loss"][k] = float(nll[p].mean())
             out["pred"][k] = pred[p]
         return out
+
+    # ---- latent cluster analysis ----------------------------------------------------------------
+    def cluster_latents(self, batches, n_clusters, labels=None, given=None, n_init=10, max_iter=300, seed=0, init=None):
+        """How the latent space clusters, per conditioning subset: k-means on the latents `latents_for` gives for every
+        batch (ops.kmeans_fit: `n_init` restarts side by side from ops.kmeans_draw(N, n_clusters, n_init, seed), or from
+        `init`: integer (R, C) row numbers or float64 (R, C, D) centres, for every subset), and of the restart with the
+        smallest inertia the silhouette (ops.silhouette), the Calinski-Harabasz and Davies-Bouldin indices
+        (ops.cluster_stats, ops.cluster_indices).  `batches`: an iterable of batch dicts; `given`: modality-name lists
+        (default_given()), keys "+".join(names).
+        `labels`: (N,) or (N, A) integers >= 0, ROW n the A label columns of sample n in batch order, every column with two
+        values at least and ids below 64.  Per column a: ops.cluster_agreement(labels[:, a], the k-means labels) and
+        label_silhouette[a] = the silhouette score of the ground-truth partition itself -- the per-label-column analysis
+        the reference's utils.cluster_analysis loop asks of its analyse_clusters.
+        -> {key: {"labels" (N,) int32, "centres" (C,D) float64, "inertia", "n_iter", "converged",
+                  "restarts": {"inertia", "n_iter", "converged", "empty"} (R,), "silhouette": float,
+                  "silhouette_samples" (N,) float64, "calinski_harabasz", "davies_bouldin": floats,
+                  "agreement": {a: {"ari", "nmi", "homogeneity", "completeness", "purity"}}, "label_silhouette": {a: float}}}.
+        Needs eval mode, 2 <= n_clusters <= min(64, N), N <= 16384 rows.  Runs without gradients; the draws come from the
+        evaluation generator or `eps_override`: the training noise state, the dropout counters, gradients and the
+        optimiser stay as they are."""
+        who = "cluster_latents"
+        self._need_eval(who, _LATENTS)
+        names, batches, D = list(self.vaes.keys()), list(batches), self.n_latents
+        if not batches:
+            raise ValueError(f"{who}: `batches` is empty")
+        given = self.default_given() if given is None else [list(g) for g in given]
+        for g in given:
+            if not g or any(m not in names for m in g):
+                raise ValueError(f"{who}: `given` entry {g} must name modalities of this model ({names})")
+        given = [[m for m in names if m in g] for g in given]
+        for batch in batches:
+            for g in given:
+                if any(m not in batch or batch[m]["data"] is None for m in g):
+                    raise ValueError(f"{who}: `given` entry {g} names a modality without data")
+        N = sum(len(b[given[0][0]]["data"]) for b in batches)
+        H = ops.H
+        if not 1 <= N <= H.MANIFOLD_MAX_ROWS or not 1 <= D <= H.FRECHET_MAX_F:
+            raise ValueError(f"{who}: {N} rows of {D} latent dimensions (1 .. {H.MANIFOLD_MAX_ROWS} rows of 1 .. "
+                             f"{H.FRECHET_MAX_F} dimensions are on the MI355X path)")
+        C, n_init, max_iter = int(n_clusters), int(n_init), int(max_iter)
+        if not 2 <= C <= H.CLUSTER_MAX_K or C > N:
+            raise ValueError(f"{who}: n_clusters = {C} for {N} rows (2 .. {H.CLUSTER_MAX_K} clusters, at most one per row, "
+                             f"are on the MI355X path)")
+        if not 1 <= n_init <= H.CLUSTER_MAX_INIT or not 1 <= max_iter <= H.CLUSTER_MAX_ITER:
+            raise ValueError(f"{who}: n_init = {n_init}, max_iter = {max_iter} (1 .. {H.CLUSTER_MAX_INIT} restarts of 1 .. "
+                             f"{H.CLUSTER_MAX_ITER} iterations are on the MI355X path)")
+        if init is not None:
+            init, _ = ops.kmeans_check_init(who, init, N, D, C)
+        if labels is not None:
+            labels = torch.as_tensor(labels).detach().cpu()
+            if labels.is_floating_point() or labels.dtype == torch.bool or labels.dim() not in (1, 2):
+                raise ValueError(f"{who}: labels must be an integer (N, A) array, one row per sample")
+            labels = labels.reshape(labels.shape[0], -1)
+            if labels.shape[0] != N or labels.shape[1] < 1:
+                raise ValueError(f"{who}: labels is {tuple(labels.shape)}, the batches hold {N} rows (one ROW of label "
+                                 f"columns per sample, in batch order)")
+            if int(labels.min()) < 0:
+                raise ValueError(f"{who}: labels holds negative values (classes are numbered from 0)")
+            for a in range(labels.shape[1]):
+                if len(torch.unique(labels[:, a])) < 2 or int(labels[:, a].max()) >= H.CLUSTER_MAX_K:
+                    raise ValueError(f"{who}: label column {a} takes {len(torch.unique(labels[:, a]))} value(s), the largest "
+                                     f"{int(labels[:, a].max())} (its silhouette needs two classes at least; ids below "
+                                     f"{H.CLUSTER_MAX_K} are on the MI355X path)")
+        res = {}
+        for g in given:
+            z = torch.cat([self.latents_for(b, g) for b in batches]).float().contiguous()
+            start = torch.from_numpy(ops.kmeans_draw(N, C, n_init, seed)) if init is None else init
+            fit = ops.kmeans_fit(z, start.to(z.device), max_iter=max_iter)
+            best = fit["best"]
+            found = fit["labels"][best].contiguous()
+            sil = ops.silhouette(z, found, C)
+            idx = ops.cluster_indices(ops.cluster_stats(z, found, C))
+            r = {"labels": found, "centres": fit["centres"][best], "inertia": float(fit["inertia"][best]),
+                 "n_iter": int(fit["n_iter"][best]), "converged": bool(fit["converged"][best]),
+                 "restarts": {k: fit[k] for k in ("inertia", "n_iter", "converged", "empty")},
+                 "silhouette": sil["score"], "silhouette_samples": sil["samples"],
+                 "calinski_harabasz": idx["calinski_harabasz"], "davies_bouldin": idx["davies_bouldin"],
+                 "agreement": {}, "label_silhouette": {}}
+            for a in range(0 if labels is None else labels.shape[1]):
+                column = labels[:, a].contiguous()
+                r["agreement"][a] = ops.cluster_agreement(column, found.cpu())
+                r["label_silhouette"][a] = ops.silhouette(z, column.to(z.device))["score"]
+            res["+".join(g)] = r
+        return res
 
     # ---- generation coherence (DESIGN.md section 7c) ------------------------------------------------------------------
     def _image_text(self, image, text):

@@ -231,6 +231,22 @@ class MultimodalVAE(nn.Module):
                               ([("test_mig_{}".format(key), r["mig"])] if "mig" in r else []))
         return out
 
+    def cluster_latents(self, batches, n_clusters, **kwargs):
+        """cluster analysis of the latents (TorchMMVAE.cluster_latents: k-means per conditioning subset, silhouette,
+        Calinski-Harabasz and Davies-Bouldin indices; the model must be in eval mode), logged as
+        test_cluster_{silhouette,ch,db}_<key> and, where labels were given, test_cluster_{ari,nmi,purity}_<key>_<a> and
+        test_cluster_label_silhouette_<key>_<a>"""
+        out = self.model.cluster_latents(batches, n_clusters, **kwargs)
+        for key, r in out.items():
+            self._log_metrics([("test_cluster_silhouette_{}".format(key), r["silhouette"]),
+                               ("test_cluster_ch_{}".format(key), r["calinski_harabasz"]),
+                               ("test_cluster_db_{}".format(key), r["davies_bouldin"])] +
+                              [("test_cluster_{}_{}_{}".format(name, key, a), agree[name])
+                               for a, agree in r["agreement"].items() for name in ("ari", "nmi", "purity")] +
+                              [("test_cluster_label_silhouette_{}_{}".format(key, a), v)
+                               for a, v in r["label_silhouette"].items()])
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;

@@ -1,0 +1,412 @@
+"""Host checks of the latent cluster analysis.  The float64 restatement the GPU tests of
+csrc/cluster.hip are held to (tests/cluster_reference.py: direct differences, no Gram product) against outputs recorded from
+scikit-learn (tests/golden/cluster, made by tests/golden/make_golden_cluster.py) and against a case worked by hand; the
+host-side arithmetic of the ops (agreement, indices, the chunk plan); cluster_latents keeps the metrics' contract on CPU
+models, where nothing reaches a kernel; the ops refuse what is outside the limits before any launch."""
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+import cluster_reference as R
+from conftest import ROOT
+
+GOLDEN = os.path.join(ROOT, "tests", "golden", "cluster")
+SYMBOLS = ("mmvae_cluster_lloyd_ws_ints", "mmvae_cluster_sil_tiles_per_chunk", "mmvae_cluster_sil_ws_doubles",
+           "mmvae_cluster_assign", "mmvae_cluster_means", "mmvae_cluster_spread", "mmvae_cluster_lloyd",
+           "mmvae_cluster_sil_sums")
+
+
+def close(got, want, what):
+    """1e-12 relative, to the largest magnitude of the recorded array (an element near 0 has no relative error to speak of)"""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    err, scale = float(np.abs(got - want).max()), float(np.abs(want).max())
+    assert err <= 1e-12 * scale, f"{what}: off by {err:.3e} at scale {scale:.3e}"
+
+
+# ---- 1. the restatement against scikit-learn's recorded outputs ---------------------------------------------------------------
+@pytest.mark.parametrize("i", range(len(R.SHAPES)))
+def test_restatement_against_scikit_learn(i):
+    N, F, C = R.SHAPES[i]
+    X, _ = R.case(i)
+    rec = np.load(os.path.join(GOLDEN, f"case{i}.npz"))
+    for m in (300, 3):
+        o = R.fit(i, m)
+        assert not o["ever_empty"]      # (scikit-learn moves an empty cluster; the contract keeps it)
+        assert np.array_equal(o["labels"], rec[f"labels_{m}"]) and o["n_iter"].tolist() == rec[f"n_iter_{m}"].tolist()
+        close(o["centres"], rec[f"centres_{m}" if f"centres_{m}" in rec else "centres_300"], f"centres, max_iter {m}")
+        close(o["inertia"], rec[f"inertia_{m}"], f"inertia, max_iter {m}")
+    o = R.fit(i)
+    assert int(rec["best"]) in o["tied"]      # (restarts with one and the same result: scikit-learn's pick is its rounding's)
+    labels = o["labels"][o["best"]]
+    sil = R.silhouette(X, labels, C)
+    close(sil["samples"], rec["silhouette"], "silhouette samples")
+    close(sil["score"], rec["silhouette"].mean(), "silhouette score")
+    ch, db = R.indices(R.stats(X, labels, C))
+    close(ch, rec["ch"], "Calinski-Harabasz")
+    close(db, rec["db"], "Davies-Bouldin")
+    agree = R.agreement(np.arange(N) % C, labels)
+    for n in ("ari", "nmi", "homogeneity", "completeness"):
+        close(agree[n], rec[n], n)
+
+
+def test_crafted_partition_against_scikit_learn():
+    """unused ids, singletons and a duplicated row.  scikit-learn's Euclidean distances go through the Gram product and put
+    the two equal rows sqrt(rounding) apart; the contract leaves a row out by index and has them at 0.  Those two samples
+    are held to scikit-learn's silhouette of directly taken distances, all others to its default."""
+    X, labels, other, (a, b) = R.crafted()
+    C = len(R.CRAFTED_SIZES)
+    rec = np.load(os.path.join(GOLDEN, "crafted.npz"))
+    sil = R.silhouette(X, labels, C)
+    rest = np.setdiff1d(np.arange(len(X)), (a, b))
+    close(sil["samples"][rest], rec["silhouette"][rest], "silhouette samples")
+    close(sil["samples"], rec["silhouette_direct"], "silhouette samples from direct distances")
+    off = np.abs(sil["samples"][[a, b]] - rec["silhouette"][[a, b]])
+    assert np.all(off > 1e-12) and np.all(off <= sil["tol_samples"][[a, b]])
+    assert np.all(sil["sums"][:, [1, 5]] == 0.0) and np.all(sil["samples"][np.isin(labels, (3, 6))] == 0.0)
+    ch, db = R.indices(R.stats(X, labels, C))
+    close(ch, rec["ch"], "Calinski-Harabasz")
+    close(db, rec["db"], "Davies-Bouldin")
+    agree = R.agreement(other, labels)
+    for n in ("ari", "nmi", "homogeneity", "completeness"):
+        close(agree[n], rec[n], n)
+
+
+LINE = np.array([[0], [2], [4], [10], [12], [30]], dtype=np.float32)
+
+
+def test_integer_case_by_hand():
+    """points on a line, start centres 0, 4, 30.  Iteration 1: 2 is as far from 0 as from 4 and goes to the lower index:
+    {0, 2} {4, 10, 12} {30} -> centres 1, 26/3, 30.  Iteration 2: 4 is 3 from 1 and 14/3 from 26/3: {0, 2, 4} {10, 12} {30}
+    -> 2, 11, 30.  Iteration 3: nothing moves: converged, n_iter = 3, inertia 4 + 0 + 4 + 1 + 1 + 0 = 10.
+    Silhouette: a = 3, 2, 3 | 2, 2 and b = 11, 9, 7 | 8, 10 -> 8/11, 7/9, 4/7, 3/4, 4/5, and 0 for the singleton.
+    CH = (1780/3 / 2) / (10 / 3) = 89; spreads 4/3, 1, 0, means 9, 28, 19 apart: DB = (7/27 + 7/27 + 1/19) / 3.
+    Against the classes 0 0 0 1 1 1: the pairs give tp 8, fp 0, fn 4, tn 18: ARI = 12/17; purity and homogeneity 1."""
+    o = R.kmeans(LINE, np.array([[0, 2, 5]]))
+    assert o["labels"].tolist() == [[0, 0, 0, 1, 1, 2]] and o["n_iter"].tolist() == [3] and o["converged"].tolist() == [True]
+    assert o["centres"][0, :, 0].tolist() == [2.0, 11.0, 30.0] and o["inertia"].tolist() == [10.0] and o["gap"] == 0.0
+    assert o["counts"].tolist() == [[3, 2, 1]] and o["empty"].tolist() == [0] and o["best"] == 0
+    two = R.kmeans(LINE, np.array([[0, 2, 5]]), max_iter=2)      # stopped after the second update: one more assignment
+    assert two["labels"].tolist() == [[0, 0, 0, 1, 1, 2]] and two["n_iter"].tolist() == [2] and not two["converged"][0]
+    assert two["centres"][0, :, 0].tolist() == [2.0, 11.0, 30.0]
+    one = R.kmeans(LINE, np.array([[0, 2, 5]]), max_iter=1)
+    assert one["labels"].tolist() == [[0, 0, 0, 1, 1, 2]] and one["centres"][0, :, 0].tolist() == [1.0, 26.0 / 3.0, 30.0]
+    labels = o["labels"][0]
+    sil = R.silhouette(LINE, labels, 3)
+    assert np.allclose(sil["samples"], [8 / 11, 7 / 9, 4 / 7, 3 / 4, 4 / 5, 0.0], rtol=0, atol=4 * R.U) and sil["samples"][5] == 0.0
+    st = R.stats(LINE, labels, 3)
+    assert st["means"][:, 0].tolist() == [2.0, 11.0, 30.0] and st["within"].tolist() == [8.0, 2.0, 0.0]
+    assert st["wdist"].tolist() == [4.0, 2.0, 0.0]
+    ch, db = R.indices(st)
+    assert abs(ch - 89.0) <= 1e-12 * 89 and abs(db - (7 / 27 + 7 / 27 + 1 / 19) / 3) <= 1e-15
+    agree = R.agreement([0, 0, 0, 1, 1, 1], labels)
+    assert abs(agree["ari"] - 12 / 17) <= 1e-15 and agree["purity"] == 1.0 and abs(agree["homogeneity"] - 1.0) <= 1e-15
+    assert 0.0 < agree["completeness"] < 1.0 and agree["completeness"] < agree["nmi"] < 1.0
+    # an unused id changes nothing but the width of the sums
+    wide = R.silhouette(LINE, labels * 2, 5)
+    assert np.array_equal(wide["samples"], sil["samples"]) and np.all(wide["sums"][:, [1, 3]] == 0.0)
+
+
+@pytest.mark.parametrize("i", range(len(R.SHAPES)))
+def test_margins_make_exact_labels_a_fair_demand(i):
+    """what the GPU tests assert again before they ask for exact labels"""
+    for m in (300, 3):
+        o = R.fit(i, m)
+        b = R.bar(R.SHAPES[i][1], o["scale"])
+        print(f"{R.SHAPES[i]}, max_iter {m}: gap {o['gap'] / b:.3g} bars, n_iter {o['n_iter'].tolist()}")
+        assert o["gap"] >= 1e3 * b and not o["ever_empty"] and o["best_margin"] >= 1e-9 and o["best"] == min(o["tied"])
+
+
+# ---- 2. the host-side arithmetic of the ops -------------------------------------------------------------------------------------
+def test_ops_agreement_and_indices_are_the_restatement():
+    from multimodal_vae_comparison_amd import ops
+    X, labels, other, _ = R.crafted()
+    got, want = ops.cluster_agreement(torch.from_numpy(np.array(other)), torch.from_numpy(np.array(labels))), R.agreement(other, labels)
+    assert set(got) == set(R.AGREEMENT) and all(isinstance(got[n], float) and abs(got[n] - want[n]) <= 1e-15 for n in R.AGREEMENT)
+    assert ops.cluster_agreement([0, 0, 1, 1], [5, 5, 2, 2]) == {n: 1.0 for n in R.AGREEMENT}
+    st = R.stats(X, labels, len(R.CRAFTED_SIZES))
+    idx = ops.cluster_indices({k: torch.from_numpy(np.asarray(st[k])) for k in ("counts", "means", "within", "wdist")})
+    ch, db = R.indices(st)
+    assert abs(idx["calinski_harabasz"] / ch - 1) <= 1e-14 and abs(idx["davies_bouldin"] / db - 1) <= 1e-14
+    assert np.array_equal(ops.kmeans_draw(70, 3, 4, 9), R.draw(70, 3, 4, 9)) and ops.kmeans_draw(70, 3, 4, 9).dtype == np.int32
+    rs = np.random.RandomState(9)
+    assert ops.kmeans_draw(70, 3, 2, 9).tolist() == [rs.permutation(70)[:3].tolist(), rs.permutation(70)[:3].tolist()]
+
+
+def test_chunk_plan():
+    """every cluster's run padded to whole tiles; a chunk holds tiles of one cluster; a cluster's chunks are consecutive"""
+    from multimodal_vae_comparison_amd import ops
+    counts = np.array(R.CRAFTED_SIZES)
+    offset, padded, table, first = ops._silhouette_plan(counts, 195, 0)
+    assert offset.tolist() == [0, 1, 1, 3, 4, 5, 5, 6] and padded == 384
+    assert table.tolist() == [[0, 0, 1], [2, 1, 3], [3, 3, 4], [4, 4, 5], [6, 5, 6]] and first.tolist() == [0, 1, 1, 2, 3, 4, 4, 5]
+    for chunks in (0, 1, 2, 3, 7, 1000):
+        offset, padded, table, first = ops._silhouette_plan(np.array([300, 200, 0, 600]), 1100, chunks)
+        assert padded == 64 * 19 and table.dtype == np.int32 and first.dtype == np.int32 and first[-1] == len(table)
+        tiles = []
+        for c in range(4):
+            mine = table[first[c]:first[c + 1]]
+            assert np.all(mine[:, 0] == c) and np.all(mine[:, 1] < mine[:, 2])
+            tiles += [t for _, t0, t1 in mine for t in range(t0, t1)]
+            assert [t for _, t0, t1 in mine for t in range(t0, t1)] == list(range(offset[c], offset[c + 1]))
+        assert tiles == list(range(19))
+    assert len(ops._silhouette_plan(np.array([300, 200, 0, 600]), 1100, 1)[2]) == 3
+    assert len(ops._silhouette_plan(np.array([300, 200, 0, 600]), 1100, 1000)[2]) == 19
+
+
+# ---- 3. the contract on CPU models ----------------------------------------------------------------------------------------------
+def _model(mixing="mopoe", mods=None, D=8):
+    from multimodal_vae_comparison_amd.models.trainer import MultimodalVAE
+    from multimodal_vae_comparison_amd.synthetic import CD_MODS, config_from_mods
+    cfg, dims = config_from_mods(mixing, CD_MODS if mods is None else mods, D, batch_size=4)
+    model = MultimodalVAE(cfg, feature_dims=dims, device="cpu").model
+    model.eval()
+    return model
+
+
+def test_unimodal_vae_refuses_cluster_latents_by_name():
+    from multimodal_vae_comparison_amd.models.vae import MIXER_METRICS, VAE
+    from multimodal_vae_comparison_amd.synthetic import CD_MODS
+    vae = _model(mods=CD_MODS[:1])
+    assert isinstance(vae, VAE) and "cluster_latents" in MIXER_METRICS
+    with pytest.raises(NotImplementedError) as e:
+        vae.cluster_latents()
+    assert "unimodal" in str(e.value) and "TorchMMVAE.cluster_latents" in str(e.value)
+
+
+def test_train_mode_raises():
+    from multimodal_vae_comparison_amd.synthetic import cdsprites_batch
+    model = _model()
+    model.train()
+    with pytest.raises(RuntimeError, match="cluster_latents needs eval mode"):
+        model.cluster_latents([cdsprites_batch(4, 6, seed=3)], 2)
+
+
+def test_argument_errors_come_before_the_first_encoder_call(monkeypatch):
+    from multimodal_vae_comparison_amd.synthetic import cdsprites_batch
+    model = _model()
+    batch = cdsprites_batch(4, 6, seed=3)
+    calls = []
+    monkeypatch.setattr(model, "_sample", lambda *a, **kw: calls.append(1))
+    monkeypatch.setattr(model, "latents_for", lambda *a, **kw: calls.append(1))
+    cases = [
+        ("`batches` is empty", ([], 2), {}),
+        ("without data", ([dict(batch, mod_2=dict(batch["mod_2"], data=None))], 2), {}),
+        ("must name modalities", ([batch], 2), {"given": [["mod_9"]]}),
+        ("must name modalities", ([batch], 2), {"given": [[]]}),
+        ("n_clusters = 1 .*MI355X path", ([batch], 1), {}),
+        ("n_clusters = 65 .*MI355X path", ([batch] * 20, 65), {}),
+        ("n_clusters = 5 for 4 rows", ([batch], 5), {}),
+        ("n_init = 0.*MI355X path", ([batch], 2), {"n_init": 0}),
+        ("n_init = 65.*MI355X path", ([batch], 2), {"n_init": 65}),
+        ("max_iter = 1001.*MI355X path", ([batch], 2), {"max_iter": 1001}),
+        ("max_iter = 0.*MI355X path", ([batch], 2), {"max_iter": 0}),
+        ("labels must be an integer", ([batch], 2), {"labels": torch.zeros(4)}),
+        ("labels must be an integer", ([batch], 2), {"labels": torch.zeros(4, 1, 1, dtype=torch.int64)}),
+        (r"labels is \(3, 1\), the batches hold 4 rows", ([batch], 2), {"labels": torch.tensor([0, 1, 0])}),
+        ("negative values", ([batch], 2), {"labels": torch.tensor([0, 1, -1, 0])}),
+        ("label column 1 takes 1 value", ([batch], 2), {"labels": torch.tensor([[0, 3], [1, 3], [0, 3], [1, 3]])}),
+        ("label column 0 takes 2 value.*largest 64", ([batch], 2), {"labels": torch.tensor([0, 64, 0, 0])}),
+        ("init is .*float32", ([batch], 2), {"init": torch.zeros(1, 2, 8)}),
+        ("init holds 3 centres per restart, n_clusters = 2", ([batch], 2), {"init": torch.tensor([[0, 1, 2]])}),
+        ("init holds row numbers from 0 to 4", ([batch], 2), {"init": torch.tensor([[0, 4]])}),
+        ("init names a row twice", ([batch], 2), {"init": torch.tensor([[0, 1], [3, 3]])}),
+        ("init has centres of 7 features", ([batch], 2), {"init": torch.zeros(1, 2, 7, dtype=torch.float64)}),
+        ("init holds values that are not finite", ([batch], 2), {"init": torch.full((1, 2, 8), float("inf"), dtype=torch.float64)}),
+        (".*65 restarts .*MI355X path", ([batch], 2), {"init": torch.tensor([[0, 1]]).repeat(65, 1)}),
+    ]
+    for match, args, kwargs in cases:
+        with pytest.raises(ValueError, match="cluster_latents: .*" + match):
+            model.cluster_latents(*args, **kwargs)
+    big = dict(batch, mod_1=dict(batch["mod_1"], data=torch.zeros(1, 3, 64, 64).expand(16385, 3, 64, 64)))
+    with pytest.raises(ValueError, match="cluster_latents: 16385 rows .*MI355X path"):
+        model.cluster_latents([big], 2)
+    assert not calls and model._eval_draws is False and model.eps_override is None
+
+
+def test_a_failing_call_leaves_the_noise_setup_as_it_found_it():
+    """on a CPU model the first encoder call fails inside the noise context of latents_for"""
+    from multimodal_vae_comparison_amd.synthetic import cdsprites_batch
+    model = _model()
+    batch = cdsprites_batch(4, 6, seed=3)
+    mine = model.eps_override = [torch.zeros(4, 8)]
+
+    def broken(*a, **kw):
+        assert model._eval_draws is True and not torch.is_grad_enabled()
+        raise KeyError("the encoders fail inside the noise context")
+
+    model._sample = broken
+    with pytest.raises(KeyError):
+        model.cluster_latents([batch], 2)
+    assert model._eval_draws is False and torch.is_grad_enabled()
+    assert model.eps_override is mine and len(mine) == 1
+
+
+def test_ops_refuse_before_a_launch():
+    from multimodal_vae_comparison_amd import ops
+    x = torch.ones(6, 4)
+    rows = torch.tensor([[0, 1]])
+    for match, X in ((r"X is \(6,\)", torch.ones(6)), ("X is .*int64", torch.ones(6, 4, dtype=torch.int64)),
+                     ("X has F = 2049 .*MI355X path", torch.ones(6, 2049)), ("X has 16385 rows .*MI355X path", torch.ones(16385, 2)),
+                     ("X holds values that are not finite", torch.full((6, 4), float("nan")))):
+        with pytest.raises(ValueError, match="kmeans_fit: " + match):
+            ops.kmeans_fit(X, rows)
+        with pytest.raises(ValueError, match="silhouette: " + match):
+            ops.silhouette(X, torch.arange(len(X)) % 2)
+        with pytest.raises(ValueError, match="cluster_stats: " + match):
+            ops.cluster_stats(X, torch.arange(len(X)) % 2, 2)
+    for match, init, kw in (("init is .*float32", torch.zeros(1, 2, 4), {}), (r"init is \(2,\)", torch.tensor([0, 1]), {}),
+                            ("init is list", [[0, 1]], {}), (".*65 restarts .*MI355X path", rows.repeat(65, 1), {}),
+                            (".*65 clusters .*MI355X path", torch.arange(65)[None, :], {}),
+                            (".*7 clusters for 6 rows .*MI355X path", torch.arange(7)[None, :], {}),
+                            (".*row numbers from 0 to 6", torch.tensor([[0, 6]]), {}),
+                            (".*row numbers from -1 to 1", torch.tensor([[-1, 1]]), {}),
+                            (".*names a row twice", torch.tensor([[0, 1, 2], [2, 5, 2]]), {}),
+                            (".*centres of 5 features", torch.zeros(1, 2, 5, dtype=torch.float64), {}),
+                            ("init holds values that are not finite", torch.full((1, 2, 4), float("nan"), dtype=torch.float64), {}),
+                            ("max_iter = 0 .*MI355X path", rows, {"max_iter": 0}),
+                            ("max_iter = 1001 .*MI355X path", rows, {"max_iter": 1001})):
+        with pytest.raises(ValueError, match="kmeans_fit: " + match):
+            ops.kmeans_fit(x, init, **kw)
+    lab = torch.tensor([0, 1, 0, 1, 2, 2])
+    for op, more in ((ops.silhouette, ()), (ops.cluster_stats, (3,))):
+        who = op.__name__
+        for match, labels in ((r"labels is \(6, 1\)", lab[:, None]), ("labels is .*float32", lab.float()), ("labels is .*bool", lab > 0),
+                              ("labels has 5 entries for 6 rows", lab[:5]), (".*negative ids", lab - 1),
+                              ("labels is on meta, the rows on cpu", lab.to("meta"))):
+            with pytest.raises(ValueError, match=f"{who}: " + match):
+                op(x, labels, *more)
+        with pytest.raises(ValueError, match=f"{who}: labels holds the id 2; n_clusters = 2"):
+            op(x, lab, 2)
+        with pytest.raises(ValueError, match=f"{who}: 65 clusters .*MI355X path"):
+            op(x, lab, 65)
+        with pytest.raises(ValueError, match=f"{who}: 0 clusters .*MI355X path"):
+            op(x, lab, 0)
+    with pytest.raises(ValueError, match="silhouette: 70 clusters .*MI355X path"):
+        ops.silhouette(torch.ones(70, 4), torch.arange(70))
+    with pytest.raises(ValueError, match="silhouette: .*two clusters with rows"):
+        ops.silhouette(x, torch.full((6,), 2), 4)
+    with pytest.raises(ValueError, match="silhouette: chunks = -1"):
+        ops.silhouette(x, lab, chunks=-1)
+    with pytest.raises(ValueError, match="cluster_stats: n_clusters is None"):
+        ops.cluster_stats(x, lab, None)
+    # on the host nothing runs: the last refusal names the missing device
+    for call in (lambda: ops.kmeans_fit(x, rows), lambda: ops.silhouette(x, lab), lambda: ops.cluster_stats(x, lab, 3)):
+        with pytest.raises(ValueError, match="there is no host path"):
+            call()
+    for match, a, b in ((r"a is \(2, 2\)", torch.zeros(2, 2, dtype=torch.int64), lab), ("b is .*float32", lab, lab.float()),
+                        ("a holds negative ids", lab - 1, lab), ("a has 6 entries, b 5", lab, lab[:5]),
+                        (r"b is \(0,\)", lab, lab[:0])):
+        with pytest.raises(ValueError, match="cluster_agreement: " + match):
+            ops.cluster_agreement(a, b)
+    with pytest.raises(ValueError, match="cluster_indices: stats is what cluster_stats returns"):
+        ops.cluster_indices({"counts": lab})
+    one = {"counts": torch.tensor([6, 0]), "means": torch.zeros(2, 4, dtype=torch.float64),
+           "within": torch.zeros(2, dtype=torch.float64), "wdist": torch.zeros(2, dtype=torch.float64)}
+    with pytest.raises(ValueError, match="cluster_indices: 1 clusters with rows for 6 rows"):
+        ops.cluster_indices(one)
+
+
+# ---- 4. ABI -----------------------------------------------------------------------------------------------------------------------
+def test_new_symbols_are_in_the_header_and_the_ctypes_table():
+    from multimodal_vae_comparison_amd import hipops
+    src = open(os.path.join(ROOT, "include", "mmvae_hip.h")).read()
+    for name in SYMBOLS:
+        assert re.search(r"\b%s\s*\(" % name, src), f"{name} is not declared in mmvae_hip.h"
+        assert name in hipops.SIGNATURES, f"{name} is not in the ctypes table"
+        assert hasattr(hipops.lib(), name)
+    for macro, value in (("MMVAE_CLUSTER_MAX_K", hipops.CLUSTER_MAX_K), ("MMVAE_CLUSTER_MAX_INIT", hipops.CLUSTER_MAX_INIT),
+                         ("MMVAE_CLUSTER_MAX_ITER", hipops.CLUSTER_MAX_ITER)):
+        assert int(re.search(r"#define %s (\d+)" % macro, src).group(1)) == value
+    assert (hipops.CLUSTER_MAX_K, hipops.CLUSTER_MAX_INIT, hipops.CLUSTER_MAX_ITER) == (64, 64, 1000)
+    L = hipops.lib()
+    # the Lloyd state: per restart four ints, one change record per block of 64 rows and one counter of empty updates per cluster
+    assert L.mmvae_cluster_lloyd_ws_ints(1100, 3) == 3 * (4 + 18 + 64) and L.mmvae_cluster_lloyd_ws_ints(64, 1) == 69
+    assert L.mmvae_cluster_lloyd_ws_ints(16384, 64) == 64 * (4 + 256 + 64)
+    for rows, restarts in ((0, 1), (16385, 1), (5, 0), (5, 65)):
+        assert L.mmvae_cluster_lloyd_ws_ints(rows, restarts) == 0
+    # the silhouette's plan is the manifold pass's: min(ceil(512 / row tiles), ceil(column tiles / 4)) chunks of the list
+    assert L.mmvae_cluster_sil_tiles_per_chunk(10000, 167, 0) == 42 and L.mmvae_cluster_sil_tiles_per_chunk(1100, 19, 0) == 4
+    assert L.mmvae_cluster_sil_tiles_per_chunk(1100, 19, 1) == 19 and L.mmvae_cluster_sil_tiles_per_chunk(1100, 19, 1000) == 1
+    assert L.mmvae_cluster_sil_tiles_per_chunk(9, 2, 0) == 2
+    for rows, tiles, chunks in ((0, 5, 0), (16385, 5, 0), (5, 0, 0), (5, 321, 0), (5, 5, -1)):
+        assert L.mmvae_cluster_sil_tiles_per_chunk(rows, tiles, chunks) == 0
+    assert L.mmvae_cluster_sil_ws_doubles(1100, 12) == 12 * 1100 and L.mmvae_cluster_sil_ws_doubles(16384, 320) == 320 * 16384
+    for rows, chunks in ((0, 5), (16385, 5), (5, 0), (5, 321)):
+        assert L.mmvae_cluster_sil_ws_doubles(rows, chunks) == 0
+
+
+# ---- 5. the routing of subsets and label columns, on a CPU model with scripted latents and ops -----------------------------
+def test_subsets_and_label_columns_are_routed_to_their_keys_and_log_tags(monkeypatch):
+    """latents_for is scripted to return rows that depend on the subset and the batch; the ops are the restatement.  Every
+    subset and every label column then has numbers of its own, so a result filed under another key or a permuted log tag
+    shows."""
+    from multimodal_vae_comparison_amd import ops
+    from multimodal_vae_comparison_amd.models.trainer import MultimodalVAE
+    from multimodal_vae_comparison_amd.synthetic import CD_MODS, cdsprites_batch, config_from_mods
+    B, C, D, n_init, seed = 6, 3, 8, 4, 7
+    cfg, dims = config_from_mods("mopoe", CD_MODS, D, batch_size=B)
+    tr = MultimodalVAE(cfg, feature_dims=dims, device="cpu")
+    model = tr.model
+    model.eval()
+    batches = [cdsprites_batch(B, 6, seed=3 + i) for i in range(2)]
+    rng = np.random.RandomState(5)
+    made, order = {}, []
+
+    def latents_for(batch, given, of=None):
+        i = next(n for n, b in enumerate(batches) if b is batch)
+        order.append((i, tuple(given)))
+        made[(i, tuple(given))] = torch.from_numpy(R.features(B, D, C, seed=rng.randint(1 << 20)))
+        return made[(i, tuple(given))]
+
+    def kmeans_fit(X, init, max_iter=300):
+        o = R.kmeans(X.numpy(), init.numpy(), max_iter)
+        return {**{k: torch.from_numpy(o[k]) for k in ("centres", "labels", "inertia", "n_iter", "converged", "empty", "counts")},
+                "best": o["best"]}
+
+    def silhouette(X, labels, n_clusters=None, chunks=0):
+        o = R.silhouette(X.numpy(), labels.numpy(), int(labels.max()) + 1 if n_clusters is None else n_clusters)
+        return {"samples": torch.from_numpy(o["samples"]), "score": o["score"], "sums": torch.from_numpy(o["sums"]),
+                "counts": torch.from_numpy(o["counts"])}
+
+    def cluster_stats(X, labels, n_clusters):
+        o = R.stats(X.numpy(), labels.numpy(), n_clusters)
+        return {k: torch.from_numpy(np.asarray(o[k])) for k in ("counts", "means", "within", "wdist")}
+
+    monkeypatch.setattr(model, "latents_for", latents_for)
+    for name, f in (("kmeans_fit", kmeans_fit), ("silhouette", silhouette), ("cluster_stats", cluster_stats)):
+        monkeypatch.setattr(ops, name, f)
+    truth = np.stack([np.arange(2 * B) % C, np.arange(2 * B) // B], 1)
+    given = [["mod_2"], ["mod_2", "mod_1"]]
+    res = tr.cluster_latents(batches, C, labels=truth, given=given, n_init=n_init, max_iter=50, seed=seed)
+    assert order == [(0, ("mod_2",)), (1, ("mod_2",)), (0, ("mod_1", "mod_2")), (1, ("mod_1", "mod_2"))]
+    assert list(res) == ["mod_2", "mod_1+mod_2"]
+    logged, seen = {}, []
+    for key, g in (("mod_2", ("mod_2",)), ("mod_1+mod_2", ("mod_1", "mod_2"))):
+        Z = np.concatenate([made[(i, g)].numpy() for i in range(2)])
+        o = R.kmeans(Z, R.draw(2 * B, C, n_init, seed), 50)
+        labels, r = o["labels"][o["best"]], res[key]
+        assert np.array_equal(r["labels"].numpy(), labels) and np.array_equal(r["centres"].numpy(), o["centres"][o["best"]])
+        assert (r["inertia"], r["n_iter"], r["converged"]) == (o["inertia"][o["best"]], o["n_iter"][o["best"]], o["converged"][o["best"]])
+        assert all(np.array_equal(r["restarts"][k].numpy(), o[k]) for k in ("inertia", "n_iter", "converged", "empty"))
+        sil = R.silhouette(Z, labels, C)
+        ch, db = R.indices(R.stats(Z, labels, C))
+        assert r["silhouette"] == sil["score"] and np.array_equal(r["silhouette_samples"].numpy(), sil["samples"])
+        assert abs(r["calinski_harabasz"] / ch - 1) <= 1e-14 and abs(r["davies_bouldin"] / db - 1) <= 1e-14
+        logged.update({f"test_cluster_silhouette_{key}": sil["score"], f"test_cluster_ch_{key}": r["calinski_harabasz"],
+                       f"test_cluster_db_{key}": r["davies_bouldin"]})
+        assert set(r["agreement"]) == set(r["label_silhouette"]) == {0, 1}
+        for a in (0, 1):
+            agree = R.agreement(truth[:, a], labels)
+            assert all(abs(r["agreement"][a][n] - agree[n]) <= 1e-15 for n in R.AGREEMENT)
+            own = R.silhouette(Z, truth[:, a], int(truth[:, a].max()) + 1)["score"]
+            assert r["label_silhouette"][a] == own
+            logged.update({f"test_cluster_ari_{key}_{a}": r["agreement"][a]["ari"], f"test_cluster_nmi_{key}_{a}": r["agreement"][a]["nmi"],
+                           f"test_cluster_purity_{key}_{a}": r["agreement"][a]["purity"],
+                           f"test_cluster_label_silhouette_{key}_{a}": own})
+            seen.append((agree["ari"], own))
+        seen.append((sil["score"], ch))
+    assert len(set(seen)) == len(seen), "two entries share their numbers: choose another seed"
+    assert {k: float(v) for k, v in tr.logged.items() if k.startswith("test_")} == logged
