@@ -180,6 +180,18 @@ int mmvae_conv2d_k4s2_bwd(const float* dy, const float* x, const float* w, float
                           int B, int Cin, int Cout, int Hout, int x_act, int accumulate, mmvae_stream_t stream);
 int mmvae_convT2d_k4s2_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, float* ws,
                            int B, int Cin, int Cout, int Hin, int x_act, int accumulate, mmvae_stream_t stream);
+/* The weight-gradient halves of several mmvae_convT2d_k4s2_bwd launches in ONE launch of their own (their data
+ * gradients: mmvae_convT2d_k4s2_dgrad): job j leaves in ws exactly the partial rows (mmvae_conv_wgrad_layout) that
+ * mmvae_convT2d_k4s2_bwd(.., accumulate = MMVAE_ACC_DEFER) leaves for the same layer, for the caller's fold.  Serves the
+ * two large layers of Dec_CNN (models/decoders.py:62-69): (Cin, Cout, Hin) = (32, 3, 32) and (32, 32, 16); any other
+ * geometry, jobs whose splits call for different loop forms, or n_jobs > MMVAE_CONV_WGRAD_BATCH_MAX:
+ * MMVAE_ERR_UNSUPPORTED. */
+#define MMVAE_CONV_WGRAD_BATCH_MAX 4
+typedef struct {
+  const float* x; const float* dy; float* ws;      /* x (B,Cin,Hin,Hin), dy (B,Cout,2Hin,2Hin) */
+  int B, Cin, Cout, Hin, x_act, has_bias;
+} mmvae_conv_wgrad_job_t;
+int mmvae_conv_wgrad_batch(const mmvae_conv_wgrad_job_t* jobs, int n_jobs, mmvae_stream_t stream);
 /* Dec_CNN's last layer and its reconstruction loss in ONE launch (round 5; csrc/conv_t3.inc):
  *   logits = convT2d(act(x), w, bias)  x (B,32,32,32) -> (B,3,64,64)       models/decoders.py:69,95
  *   x_hat  = clamp(sigmoid(logits), 1e-6, 1 - 1e-6)                         models/decoders.py:96-97   (never stored)

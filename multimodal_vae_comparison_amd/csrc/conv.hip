@@ -282,6 +282,78 @@ extern "C" int mmvae_convT2d_k4s2_wgrad(const float* x, const float* dy, float* 
   return conv_wgrad_dispatch(x, dy, dw, db, ws, B, Cin, Cout, Hin, x_act, MMVAE_ACT_NONE, 2, accumulate,
                              (hipStream_t)stream);
 }
+// ------------------------------------------------------------------------------------------------
+// Weight gradients of several ConvTranspose2d layers in ONE launch (as rgemm_batch_kernel for the Linear layers): the
+// weight-gradient parts of the fused backward launches above, taken off the chain their data gradients sit on.  blk0[]
+// maps a workgroup to its job, inside a job the workgroups are numbered as the fused launch numbers its first n_w ones,
+// and every job runs the conv_wgrad_body instantiation the fused launch of its layer picks: same partials in ws.
+// ------------------------------------------------------------------------------------------------
+struct ConvWgradBatch {
+  ConvWgradArgs a[MMVAE_CONV_WGRAD_BATCH_MAX];
+  int blk0[MMVAE_CONV_WGRAD_BATCH_MAX + 1];
+  int gx[MMVAE_CONV_WGRAD_BATCH_MAX];      // position splits of the job (the body's grid.x)
+  int q3[MMVAE_CONV_WGRAD_BATCH_MAX];      // 1: the 3-channel image layer, 0: a 32-channel layer on the 16 x 16 map
+  int n;
+};
+// W32: the 32-channel jobs' geometry (8- or 16-channel chunks: wgrad_qc8), one per launch
+template <typename W32, bool SPEC>
+__global__ __launch_bounds__(256) void conv_wgrad_batch_kernel(ConvWgradBatch bt) {
+  MMVAE_TRACE_STAMP(40);
+  using W3 = WgradGeom<3, 5>;
+  __shared__ __attribute__((aligned(16))) float smem[cmax(W3::SMEM, W32::SMEM)];
+  int p = 0;
+#pragma unroll
+  for (int q = 1; q < MMVAE_CONV_WGRAD_BATCH_MAX; ++q) p = (q < bt.n && (int)blockIdx.x >= bt.blk0[q]) ? q : p;
+  const int local = blockIdx.x - bt.blk0[p], gx = bt.gx[p];
+  if (bt.q3[p]) conv_wgrad_body<W3, SPEC>(bt.a[p], local % gx, local / gx, gx, smem);
+  else conv_wgrad_body<W32, SPEC>(bt.a[p], local % gx, local / gx, gx, smem);
+}
+
+extern "C" int mmvae_conv_wgrad_batch(const mmvae_conv_wgrad_job_t* jobs, int n_jobs, mmvae_stream_t stream) {
+  MMVAE_CHECK_ARG(jobs && n_jobs >= 1);
+  if (n_jobs > MMVAE_CONV_WGRAD_BATCH_MAX) return MMVAE_ERR_UNSUPPORTED;
+  ConvWgradBatch bt;
+  bt.n = n_jobs;
+  bt.blk0[0] = 0;
+  int spec = -1, qc8 = -1;
+  for (int p = 0; p < n_jobs; ++p) {
+    const mmvae_conv_wgrad_job_t& j = jobs[p];
+    MMVAE_CHECK_ARG(j.x && j.dy && j.ws && j.B > 0);
+    // the two layers of Dec_CNN whose fused backward launch this one relieves (mmvae_convT2d_k4s2_bwd)
+    const bool l3 = j.Cin == 32 && j.Cout == 3 && j.Hin == 32, l32 = j.Cin == 32 && j.Cout == 32 && j.Hin == 16;
+    if (!(l3 || l32) || j.x_act == MMVAE_ACT_GELU) return MMVAE_ERR_UNSUPPORTED;
+    const int n_macro = wgrad_n_macro(j.B, j.Hin), nsplit = wgrad_splits(n_macro, j.Cout);
+    const int s = wgrad_spec(n_macro, nsplit) ? 1 : 0;
+    if (spec >= 0 && s != spec) return MMVAE_ERR_UNSUPPORTED;      // (one loop form per launch)
+    spec = s;
+    int nch = 1;      // WgradGeom<3, 5>::NCH
+    if (l32) {
+      const int c8 = wgrad_qc8(nsplit, n_macro) ? 1 : 0;
+      if (qc8 >= 0 && c8 != qc8) return MMVAE_ERR_UNSUPPORTED;     // (one 32-channel geometry per launch)
+      qc8 = c8;
+      nch = c8 ? WgradGeom<32, 4, 8>::NCH : WgradGeom<32, 4>::NCH;
+    }
+    bt.a[p] = ConvWgradArgs{j.x, j.dy, j.ws, j.B, j.x_act, MMVAE_ACT_NONE, j.has_bias ? 2 : 0, n_macro, 32,
+                            (long)32 * j.Cout * 16 + 32};
+    bt.gx[p] = nsplit;
+    bt.q3[p] = l3 ? 1 : 0;
+    bt.blk0[p + 1] = bt.blk0[p] + nsplit * nch;
+  }
+  for (int p = n_jobs; p < MMVAE_CONV_WGRAD_BATCH_MAX; ++p) {
+    bt.a[p] = bt.a[0]; bt.gx[p] = 1; bt.q3[p] = 0; bt.blk0[p + 1] = bt.blk0[n_jobs];
+  }
+  const dim3 grid(bt.blk0[n_jobs]);
+  hipStream_t st = (hipStream_t)stream;
+  if (qc8 != 0) {
+    if (spec) hipLaunchKernelGGL((conv_wgrad_batch_kernel<WgradGeom<32, 4, 8>, true>), grid, dim3(256), 0, st, bt);
+    else hipLaunchKernelGGL((conv_wgrad_batch_kernel<WgradGeom<32, 4, 8>, false>), grid, dim3(256), 0, st, bt);
+  } else {
+    if (spec) hipLaunchKernelGGL((conv_wgrad_batch_kernel<WgradGeom<32, 4>, true>), grid, dim3(256), 0, st, bt);
+    else hipLaunchKernelGGL((conv_wgrad_batch_kernel<WgradGeom<32, 4>, false>), grid, dim3(256), 0, st, bt);
+  }
+  return mmvae_launch_status();
+}
+
 extern "C" size_t mmvae_conv_wgrad_ws_floats(int B, int Csmall, int Clarge, int Hsmall) {
   return conv_wgrad_ws_floats(B, Csmall, Clarge, Hsmall);
 }

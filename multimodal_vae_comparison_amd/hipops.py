@@ -147,6 +147,7 @@ SIGNATURES = {
     "mmvae_conv_wgrad_ws_floats": (c_sz, [c_i] * 4),
     "mmvae_conv2d_k4s2_bwd": (c_i, [c_p] * 7 + [c_i] * 6 + [c_p]),
     "mmvae_convT2d_k4s2_bwd": (c_i, [c_p] * 7 + [c_i] * 6 + [c_p]),
+    "mmvae_conv_wgrad_batch": (c_i, [c_p, c_i, c_p]),
     "mmvae_gemm_f32": (c_i, [c_p] * 7 + [c_i] * 3 + [c_l] * 5 + [c_i] * 5 + [c_p]),
     "mmvae_gemm_ws_floats": (c_sz, [c_i] * 3),
     "mmvae_gemm_splits": (c_i, [c_i] * 4),
@@ -410,6 +411,14 @@ DROPOUT_ADVANCE_MAX = 16
 class WgradJob(ctypes.Structure):
     _fields_ = [("dy", c_p), ("x", c_p), ("dw", c_p), ("db", c_p), ("ws", c_p), ("M", c_i), ("N", c_i), ("K", c_i),
                 ("ldx", c_l), ("x_act", c_i), ("accumulate", c_i)]
+
+
+CONV_WGRAD_BATCH_MAX = 4
+
+
+class ConvWgradJob(ctypes.Structure):     # mmvae_conv_wgrad_job_t
+    _fields_ = [("x", c_p), ("dy", c_p), ("ws", c_p), ("B", c_i), ("Cin", c_i), ("Cout", c_i), ("Hin", c_i),
+                ("x_act", c_i), ("has_bias", c_i)]
 
 
 class TxtWgradJob(ctypes.Structure):      # mmvae_txt_wgrad_job_t

@@ -132,6 +132,8 @@ class MoPOE(TorchMMVAE):
                 st.wait_stream(fuse)
         recs = [None] * M
         order = [(i, names[i], real[(i + M - 1) % M] if rotate else real[i]) for i in range(M)]
+        # (the stream of a decoder that does not share the fusion's: idle behind that decoder's backward pass)
+        self._idle_stream = next((st for _, _, st in reversed(order) if st != fuse0), None)
         for i, n, st in order:
             vae = self.vaes[n]
             _uses(z[i], st)
@@ -202,6 +204,10 @@ class MoPOE(TorchMMVAE):
             # fusion's stream has queued its last backward launch: ops.GradReducer.run_early_step
             ops.GradReducer.early_step = (early[0], self._fuse_stream, early[1], early[2])
             ops.GradReducer.dw_open = True
+        if not cut and ops.GradReducer.defer_next and self._idle_stream is not None and M == 2:
+            # (captured one-GPU step of two towers, the layout this was measured in) the image decoder's large conv weight
+            # gradients leave its backward chain
+            ops.GradReducer.cw_streams = (self._fuse_stream, self._idle_stream)
         if cut:
             # decoders + fusion only: the gradients of the towers' head outputs come back instead of flowing on
             self._cut = (list(self._fusion_inputs), torch.autograd.grad(recs + [kl], self._fusion_inputs, self._seeds),
@@ -210,6 +216,7 @@ class MoPOE(TorchMMVAE):
             torch.autograd.backward(recs + [kl], self._seeds)
         ops.GradReducer.tail = ops.GradReducer.early_step = None
         ops.GradReducer.dw_open = ops.GradReducer.early_ready = False
+        ops.GradReducer.cw_streams = None
         if tail is not None and tail["done"]:
             out = tail["args"][2].unbind(0)
         if out is None:

@@ -81,6 +81,7 @@ class GradReducer:
         _, st = cls._st(device)
         cls.early_step, cls.dw_jobs, cls.dw_open = None, [], False      # (per-step state: a backward pass that raised leaves them behind)
         cls.tw_jobs, cls.early_ready = {}, False
+        cls.cw_jobs, cls.cw_done, cls.cw_streams = [], None, None
         cls.last_writer.clear()
         cls.packed_grads.clear()
         cls.packed_uses.clear()
@@ -268,6 +269,64 @@ class GradReducer:
             j.M, j.N, j.K, j.ldx, j.x_act, j.accumulate = M, N, K, K, x_act, H.ACC_DEFER
         _call("mmvae_linear_bwd_weight_batch", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
 
+    # cw_jobs: weight gradients of Dec_CNN's two large ConvTranspose2d layers (32 -> 3 on the 32 x 32 map, 32 -> 32 on the
+    # 16 x 16 one) whose backward only launched the data gradient (_convT_k4s2_bwd): (x, dy, dw, db, ws, (B, Cin, Cout, Hin),
+    # x_act), tensors held until flush_cw has queued them as ONE launch.  Nothing on the chain image decoder -> fusion ->
+    # encoders reads dW / db -- their first reader is the optimiser launch that folds the decoders' range -- so the launch
+    # runs on the OTHER stream of the step, behind the text decoder's backward pass (cw_streams, set by
+    # MoPOE.objective_backward for a captured one-GPU step: (the fusion's stream, the other decoder's)).
+    cw_jobs = []
+    cw_enabled = os.environ.get("MMVAE_CONV_DW_LATER", "1") == "1"
+    # largest batch at which a layer is parked (same box, cfg2 step, parent -> parked, DESIGN.md 0 and
+    # profiles/r07_conv_dw_later.txt): beside the chain's latency-bound kernels the launch costs what it occupies of the chip
+    CW_MAX_BATCH = {(32, 3, 32): 128, (32, 32, 16): 64}
+    cw_streams = None
+    cw_done = None        # event behind the batch launch; EarlyStepPoint.backward (or the end-of-backward join) waits for it
+
+    @classmethod
+    def cw_later(cls, device, shape):
+        st = cls.cw_streams
+        return (cls.cw_enabled and st is not None and torch.cuda.current_stream(device) == st[0]
+                and shape[0] <= cls.CW_MAX_BATCH.get(tuple(shape[1:]), 0) and len(cls.cw_jobs) < H.CONV_WGRAD_BATCH_MAX)
+
+    @classmethod
+    def cw_park(cls, job):
+        """-> None, or (the last layer of this batch size is parked) the function that queues the batch launch; the caller
+        calls it BEHIND its own data-gradient launch: captured in the other order, the graph holds the chain's next kernel
+        back until the batch launch starts (profiles/r07_conv_dw_later.txt).  The launch waits for what the chain has
+        queued up to HERE: the data gradient that produced this job's dy."""
+        cls.cw_jobs.append(job)
+        B = job[5][0]
+        if len(cls.cw_jobs) < sum(B <= m for m in cls.CW_MAX_BATCH.values()):
+            return None
+        dev = job[0].device
+        ev = torch.cuda.current_stream(dev).record_event()
+        return lambda: cls._cw_launch(dev, ev)
+
+    @classmethod
+    def _cw_launch(cls, dev, ev):
+        side = cls.cw_streams[1]
+        side.wait_event(ev)
+        for j in cls.cw_jobs:
+            for t in j[:2]:      # x, dy: allocated on the chain's stream, read on the other one
+                (t._base if t._base is not None else t).record_stream(side)
+        with torch.cuda.stream(side):
+            cls.flush_cw()
+            cls.cw_done = side.record_event()
+        cls.note_stream(dev, side)      # (the end-of-backward join covers a step without EarlyStepPoint)
+
+    @classmethod
+    def flush_cw(cls):
+        """the parked conv weight gradients in one launch on the current stream (partials into their arena slices)"""
+        jobs, cls.cw_jobs = cls.cw_jobs, []
+        if not jobs:
+            return
+        arr = (H.ConvWgradJob * len(jobs))()
+        for j, (x, dy, dw, db, ws, (B, Cin, Cout, Hin), x_act) in zip(arr, jobs):
+            j.x, j.dy, j.ws = H.ptr(x), H.ptr(dy), H.ptr(ws)
+            j.B, j.Cin, j.Cout, j.Hin, j.x_act, j.has_bias = B, Cin, Cout, Hin, x_act, int(db is not None)
+        _call("mmvae_conv_wgrad_batch", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
+
     # tw_jobs: {stream: [(dy2, x2, w, b, gw, gb)]} -- weight gradients of TALL-SKINNY Linear layers (the action towers'
     # attention projections: 12 800 rows, 32 .. 96 columns) whose backward only launched the data gradient.  Eight of them
     # share one launch of the tall-skinny weight-gradient kernel (_txt_wgrad: csrc/twgrad.hip) on the stream they were
@@ -325,6 +384,7 @@ class GradReducer:
         if len(inside) > H.MAX_SEGMENTS or any(sg[1] + 4 * sg[3] > hi for sg in inside):
             return
         st["segs"] = [sg for sg in st["segs"] if not (lo <= sg[1] < hi)]
+        assert cls.cw_done is None      # (EarlyStepPoint.backward has ordered the parked conv weight gradients in front)
         # (no parked weight gradient is left here: EarlyStepPoint.backward, which sets `early_ready`, has queued them all
         # and closed `dw_open`)
         fn(cls._table(inside) if inside else None)
@@ -349,6 +409,7 @@ class GradReducer:
     @classmethod
     def flush(cls, device):
         cls.flush_dw()      # (no EarlyStepPoint ran behind them: here, behind the whole backward pass)
+        cls.flush_cw()      # (a batch whose last layer never came)
         cls.tw_flush()      # (each list on the stream it was parked from, in front of the join below)
         _, st = cls._st(device)
         cur = torch.cuda.current_stream(device)
@@ -625,7 +686,18 @@ def _convT_k4s2_bwd(x, w, dy, in_act, gw, gb, has_b, need_dx):
     ws = GradReducer.alloc(nws, x.device) if defer else H.workspace(nws, x.device)
     acc = H.ACC_DEFER if defer else acc_w
     dx = None
-    if need_dx:       # input- and weight-gradient workgroups in ONE launch
+    if need_dx and defer and GradReducer.cw_later(x.device, (B, Cin, Cout, Hin)):
+        # the captured one-GPU MoPoE step, one of the image decoder's two large layers: only the DATA gradient (the same
+        # kernel and tile order as the fused launch's data-gradient part) sits on the chain decoder -> fusion -> encoders;
+        # the parked weight gradients follow in ONE launch on the step's other stream (GradReducer.cw_park), same partials in `ws`
+        dx = torch.empty_like(x)
+        go = GradReducer.cw_park((x, dy, dw, db, ws, (B, Cin, Cout, Hin), in_act))
+        ep = _DACT[in_act]
+        _call("mmvae_convT2d_k4s2_dgrad", H.ptr(dy), H.ptr(w), H.ptr(x) if ep else None, H.ptr(dx), B, Cin, Cout, Hin, ep,
+              H.stream())
+        if go is not None:
+            go()
+    elif need_dx:       # input- and weight-gradient workgroups in ONE launch
         dx = torch.empty_like(x)
         _call("mmvae_convT2d_k4s2_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
               B, Cin, Cout, Hin, in_act, acc, H.stream())
@@ -1431,6 +1503,11 @@ class EarlyStepPoint(Function):
                                          # must not trigger the early optimiser launch: the fusion's backward has not run)
         GradReducer.dw_open = False      # (the encoders' Linear layers behind this point keep their grouped launches)
         GradReducer.flush_dw()
+        # the parked conv weight gradients' partials are written on the other stream: in front of the early optimiser launch
+        # (here, not in front of that launch: an edge into the middle of the encoders' backward serialises the graph)
+        done, GradReducer.cw_done = GradReducer.cw_done, None
+        if done is not None:
+            torch.cuda.current_stream(g.device).wait_event(done)
         return g
 
 

@@ -24,7 +24,7 @@ NAMES = {0: "img enc conv1", 1: "img enc conv2", 2: "img enc conv3", 3: "img enc
          24: "  gemm_grouped", 25: "  rgemm16", 26: "  rgemm", 27: "  rgemm_grouped", 28: "  bce_rowsum", 29: "  ce_time_fwd",
          30: "  embed_pe_fwd", 31: "  embed_pe_bwd", 32: "  permute_mask", 33: "  dropout_advance", 34: "  dropout_act",
          35: "  txt_wgrad", 36: "img dec convT3 col2im fwd", 37: "  gemm_b16", 38: "  gemm_b16 linear bwd",
-         39: "  rgemm_batch (parked dW)"}
+         39: "  rgemm_batch (parked dW)", 40: "  conv_wgrad_batch (parked conv dW)"}
 dev = torch.device("cuda", 0)
 B = int(os.environ.get("TRACE_BATCH", 128))
 torch.manual_seed(0)
@@ -58,12 +58,17 @@ v = table.cpu().tolist()
 n_ev = v[0]
 ev = [(v[9 + 2 * (k & 2047)], v[8 + 2 * (k & 2047)]) for k in range(max(0, n_ev - 2047), n_ev)]     # (time, id), launch order
 ev.sort()
-starts = [i for i, (t, k) in enumerate(ev) if k == 0]           # conv1 opens a step
+# conv1 opens a step, behind the closing adam launch of the one before (the gather kernel's ids 0 / 1 are also those of the
+# image decoder's two large data gradients when they run as launches of their own, MMVAE_CONV_DW_LATER: behind bce_rowsum)
+starts = [i for i, (t, k) in enumerate(ev) if k == 0 and i > 0 and ev[i - 1][1] == 20]
 assert len(starts) >= 3, "no complete step in the event log"
 step = ev[starts[-2]:starts[-1]]
 t0 = step[0][0]
 prev = t0
+ALONE = {0: "img dec bwd convT3, data gradient alone", 1: "img dec bwd convT(16), data gradient alone"}
+bwd = False
 for t, k in step:
-    print(f"{(t - t0) / 100.0:8.2f} us  (+{(t - prev) / 100.0:6.2f})  {NAMES.get(k, k)}")
+    bwd = bwd or k == 28
+    print(f"{(t - t0) / 100.0:8.2f} us  (+{(t - prev) / 100.0:6.2f})  {ALONE[k] if bwd and k in ALONE else NAMES.get(k, k)}")
     prev = t
 print(f"{(ev[starts[-1]][0] - t0) / 100.0:8.2f} us  next step's conv1   ({len(step)} instrumented launches per step)")
