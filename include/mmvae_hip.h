@@ -1219,6 +1219,39 @@ int mmvae_cluster_sil_sums(const float* X, const double* n2, const int* list, co
                            double* S, long rows, int F, int C, long padded, int chunks, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image reconstruction quality (EvaluationMixin.reconstruction_quality; csrc/image_quality.hip): per pair
+ * of images x, y (N, C, H, W) fp32, contiguous, read as double: the errors, PSNR, SSIM (Wang et al. 2004) and multi-scale values.
+ *   mmvae_image_quality: out (N, 5 + scales) doubles, row n = (mse, mae, psnr, ssim, ms_ssim, level_1 .. level_scales):
+ *     mse / mae = mean of (x - y)^2 / |x - y| over C H W; psnr = 10 log10(data_range^2 / mse), +inf at mse = 0.
+ *     Per plane and valid window position (no padding; (H - win + 1) (W - win + 1) of them), with the 2-D weights
+ *     window[i] window[j] (`window`: win HOST doubles that sum to 1): mu_x, mu_y the weighted means,
+ *     var_x = cov_scale (sum w x^2 - mu_x^2), var_y alike, cov = cov_scale (sum w x y - mu_x mu_y);
+ *     l = (2 mu_x mu_y + c1) / (mu_x^2 + mu_y^2 + c1), cs = (2 cov + c2) / (var_x + var_y + c2).  A plane's ssim / cs / l are the
+ *     means of l cs / cs / l over its positions, an image's the means of its C planes'.  ssim is level 1's.
+ *     Level s + 1 is the 2 x 2 average pooling of level s (in double, on chip, of both images).  level_s = the image's cs of
+ *     level s for s < scales and its l for s = scales; ms_ssim = prod_s max(level_s, 0)^ms_weights[s] (`ms_weights`: scales HOST
+ *     doubles; scales = 1: ms_ssim = max(ssim, 0), ms_weights is not read).
+ *     One launch, one workgroup per image; nothing but `out` is written, no atomics, every sum in a fixed order: a row's bits
+ *     do not depend on the other rows of the call.
+ *   mmvae_image_quality_max_scales(H, W, win): the deepest `scales` the plane allows (a level that is pooled needs even sides,
+ *     every level sides >= win; at most MMVAE_IQ_MAX_SCALES), 0 for a plane or window outside the limits.
+ *   mmvae_image_quality_lds_bytes(H, W, win): the LDS of one workgroup (0 outside the limits).  Both are host functions.
+ *   win odd in MMVAE_IQ_MIN_WIN .. MMVAE_IQ_MAX_WIN, win <= H, W <= MMVAE_IQ_MAX_SIDE, 1 <= C <= MMVAE_IQ_MAX_CHANNELS,
+ *   1 <= scales <= max_scales, 1 <= N <= MMVAE_IQ_MAX_ROWS; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_IQ_MIN_WIN 3
+#define MMVAE_IQ_MAX_WIN 11
+#define MMVAE_IQ_MAX_SIDE 64
+#define MMVAE_IQ_MAX_CHANNELS 4
+#define MMVAE_IQ_MAX_SCALES 4
+#define MMVAE_IQ_MAX_ROWS 2147483647L
+int mmvae_image_quality_max_scales(int H, int W, int win);
+size_t mmvae_image_quality_lds_bytes(int H, int W, int win);
+int mmvae_image_quality(const float* x, const float* y, double* out, long N, int C, int H, int W, int win, const double* window,
+                        double data_range, double c1, double c2, double cov_scale, int scales, const double* ms_weights,
+                        mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

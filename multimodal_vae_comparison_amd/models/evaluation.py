@@ -1,7 +1,8 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7k) as a mixin: held-out log-likelihood, latent
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7l) as a mixin: held-out log-likelihood, latent
 classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
 density / coverage and kernel inception distance of generated images, the disentanglement of the latent code, the
-cross-modal (canonical) correlation of generations and the cluster analysis of the latents.  What they share is here once: the
+cross-modal (canonical) correlation of generations, the cluster analysis of the latents and the reconstruction quality of
+generated images against the images they were generated for (PSNR, SSIM, MS-SSIM).  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -1021,4 +1022,96 @@ class EvaluationMixin:
                     r.update(mig=gap["mig"], per_factor=gap["per_factor"], mi_table=gap["mi"], h_z=gap["h_z"])
                 r.update(z=z, loc=loc, scale=scale)
                 res[key] = r
+        return res
+
+    # ---- reconstruction quality of generated images ---------------------------------------------------
+    @staticmethod
+    def _image_planes(data_dim):
+        """the callable that lays a tensor of an image modality with this data_dim out as (rows, C, H, W), as the project
+        reads that modality elsewhere, or None for a data_dim that is no known image form"""
+        d = tuple(data_dim)
+        if d in ((64, 64, 3), (3, 64, 64)):      # the CdSprites+ decoder labels its output by view and does not permute it
+            return lambda t: t.reshape(-1, 3, 64, 64)      # (coherence.quantise_images)
+        if d in ((28, 28, 1), (1, 28, 28)):
+            return lambda t: t.reshape(-1, 1, 28, 28)
+        if d in ((32, 32, 3), (3, 32, 32)):      # Dec_SVHN returns (.., 32, 32, 3): permuted back (DigitClassifier.images)
+            return lambda t: (t.reshape(-1, 32, 32, 3).permute(0, 3, 1, 2) if tuple(t.shape[-3:]) == (32, 32, 3)
+                              else t.reshape(-1, 3, 32, 32))
+        return None
+
+    def reconstruction_quality(self, batches, images=None, eps=None, **window):
+        """How close a generated image is to the image it was generated for: PSNR, SSIM (Wang et al. 2004) and MS-SSIM, the
+        mean squared and the mean absolute error, pair by pair in float64 on the device (ops.image_quality;
+        csrc/image_quality.hip).  Row i of a reconstruction and of a cross-generation belongs to row i of the batch's data;
+        joint samples have no partner and are not walked, so that the metric works for every mixer, private latents
+        included.  `batches`: an iterable of batch dicts holding every modality.
+        `images`: {modality: callable -> (rows, C, H, W)}, handed batch[m]["data"] for the real rows and decoder_dist.loc for
+        generated ones (the first B rows are read).  The default takes every modality whose data_dim is a known image
+        form, in the layout the project reads it in elsewhere: (64, 64, 3) -> reshape(-1, 3, 64, 64) (the CdSprites+ decoder's
+        output is labelled, not permuted: coherence.quantise_images), (28, 28, 1) -> (-1, 1, 28, 28), (32, 32, 3) -> permuted
+        back to (-1, 3, 32, 32) (DigitClassifier.images).
+        `window`: win, sigma, data_range, k1, k2, sample_covariance, scales, weights of ops.image_quality.
+        The sets and the order of the forward() calls are those of frechet_distances with n_joint = 0; each batch's real
+        rows are kept as fp32 copies until the walk ends, every generated batch is scored as it arrives.
+        -> {m: {"recon": {...}, "cross": {g: {...}}, "n": rows, "shape": (C, H, W),
+                "per_sample": {"recon": {name: (n,)}, "cross": {g: {name: (n,)}}}}}, each {...} the float means over the rows of
+        "psnr", "ssim", "ms_ssim", "mse", "mae" (psnr is +inf as soon as one row is reproduced exactly, as the per-image
+        convention gives), per_sample the float64 tensors they are the means of and "levels" (n, scales).
+        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
+        tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
+        dropout counters, gradients and the optimiser stay as they are."""
+        who = "reconstruction_quality"
+        self._need_eval(who, _GENERATIONS)
+        names = list(self.vaes.keys())
+        if images is None:
+            images = {m: f for m, f in ((m, self._image_planes(self.vaes[m].data_dim)) for m in names) if f is not None}
+            if not images:
+                raise ValueError(f"{who}: no modality of this model has a known image form "
+                                 f"({[tuple(self.vaes[m].data_dim) for m in names]}): name the layouts in `images`")
+        elif not images or any(m not in names or not callable(f) for m, f in images.items()):
+            raise ValueError(f"{who}: `images` maps modalities of this model ({names}) to callables")
+        shapes, real, done, scores = {}, {}, {}, {}
+
+        def flat(m):
+            def planes(t):
+                p = images[m](t)
+                if not torch.is_tensor(p) or p.dim() != 4 or not p.is_floating_point():
+                    raise ValueError(f"{who}: the callable of {m!r} must return float (rows, C, H, W) images")
+                if shapes.setdefault(m, tuple(p.shape[1:])) != tuple(p.shape[1:]):
+                    raise ValueError(f"{who}: the callable of {m!r} returned images of {tuple(p.shape[1:])} after "
+                                     f"{shapes[m]}")
+                return p.reshape(p.shape[0], -1)
+            return planes
+
+        def sink(m, key, f):
+            if key == "real":
+                ops.image_quality_plan((len(f),) + shapes[m], **window)      # (refusals before the first forward())
+                real.setdefault(m, []).append(f.detach().to(torch.float32, copy=True))
+                return
+            b = done.get((m, key), 0)
+            done[(m, key)] = b + 1
+            x = real[m][b]
+            if f.shape[0] != x.shape[0]:
+                raise ValueError(f"{who}: {f.shape[0]} generated rows of {m!r} for the {x.shape[0]} rows of batch {b}")
+            scores.setdefault((m, key), []).append(
+                ops.image_quality(x.reshape(-1, *shapes[m]), f.detach().reshape(-1, *shapes[m]), **window))
+
+        mods, _ = self._walk_generations(who, batches, {m: flat(m) for m in images}, 0, eps, None, lambda rows, n_joint: None,
+                                         sink)
+        stats = ("psnr", "ssim", "ms_ssim", "mse", "mae")
+        res = {}
+        with torch.no_grad():
+            for m in mods:
+                r = {"recon": None, "cross": {}, "n": sum(len(x) for x in real[m]), "shape": shapes[m],
+                     "per_sample": {"recon": None, "cross": {}}}
+                for (mm, key), parts in scores.items():
+                    if mm != m:
+                        continue
+                    per = {name: torch.cat([p[name] for p in parts]) for name in stats + ("levels",)}
+                    means = {name: float(per[name].mean()) for name in stats}
+                    if isinstance(key, tuple):
+                        r["cross"][key[1]], r["per_sample"]["cross"][key[1]] = means, per
+                    else:
+                        r[key], r["per_sample"][key] = means, per
+                res[m] = r
         return res

@@ -247,6 +247,17 @@ class MultimodalVAE(nn.Module):
                                for a, v in r["label_silhouette"].items()])
         return out
 
+    def reconstruction_quality(self, batches, **kwargs):
+        """PSNR, SSIM and MS-SSIM of reconstructions and cross-generations against the images they were generated for
+        (TorchMMVAE.reconstruction_quality; the model must be in eval mode), logged as test_{psnr,ssim,ms_ssim}_<m>_recon and
+        test_{psnr,ssim,ms_ssim}_<m>_from_<g>"""
+        out = self.model.reconstruction_quality(batches, **kwargs)
+        for m, r in out.items():
+            sets = [("{}_recon".format(m), r["recon"])] + [("{}_from_{}".format(m, g), d) for g, d in r["cross"].items()]
+            self._log_metrics(("test_{}_{}".format(name, tag), d[name]) for tag, d in sets
+                              for name in ("psnr", "ssim", "ms_ssim"))
+        return out
+
     # ---- checkpoints (SURVEY 8(f) rank 2) -----------------------------------------------------------
     def save_checkpoint(self, path, epoch=0, global_step=0):
         """Lightning-style `.ckpt` with the reference's key names (`model.vaes.mod_k.enc...`, `model._pz_params.1`;
