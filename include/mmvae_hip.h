@@ -1542,8 +1542,8 @@ int mmvae_adam_fold_flat(float* p, float* g, float* m, float* v, float* vmax, lo
                          const mmvae_reduce_segments_t* table, const mmvae_rowptrs_t* rows, const float* W_host,
                          float* out, int n_rows, int B, int n_out, mmvae_stream_t stream);
 /* One step's fold + update in SEVERAL launches: elements [lo, hi) of the flat buffers only (lo % 4 == 0), with those
- * segments of `table` whose destination lies inside the range (segments outside are skipped, one that straddles lo or hi
- * is MMVAE_ERR_ARG; table may be NULL).  Every launch of a step reads the same step number from step_dev; exactly one --
+ * segments of `table` whose destination lies inside the range (segments of another range of [0, n) are skipped; one that straddles lo
+ * or hi, or whose destination is not wholly inside the flat buffer, is MMVAE_ERR_ARG; table may be NULL).  Every launch of a step reads the same step number from step_dev; exactly one --
  * the LAST in stream order -- passes advance_step = 1 and closes the step.  Per element bit-identical to
  * mmvae_adam_fold_flat over the whole buffer.  (The captured training step updates the decoders' + prior's range beside the
  * encoders' backward pass, so that only the encoders' parameters are left for the serial launch at the end of the step.)

@@ -654,10 +654,9 @@ static int adam_fold_impl(float* p, float* g, float* m, float* v, float* vmax, l
   for (int s = 0; table && s < table->n; ++s) {
     if (!table->dst[s] || table->len[s] <= 0) return MMVAE_ERR_ARG;
     const float *d0 = table->dst[s], *d1 = table->dst[s] + table->len[s];
-    if (d1 <= g + lo || d0 >= g + hi) {
-      if (whole) return MMVAE_ERR_ARG;       // (outside the flat buffer)
-      continue;
-    }
+    // outside the flat buffer altogether: no launch of the step would fold it -- checked BEFORE "another launch's range"
+    if (d0 < g || d1 > g + n) return MMVAE_ERR_ARG;
+    if (d1 <= g + lo || d0 >= g + hi) continue;      // inside [0, n) but not in [lo, hi): it belongs to another launch
     if (d0 < g + lo || d1 > g + hi) return MMVAE_ERR_ARG;      // straddles a range boundary
     const int k = inside.n++;
     inside.src[k] = table->src[s]; inside.dst[k] = table->dst[s]; inside.rows[k] = table->rows[s];

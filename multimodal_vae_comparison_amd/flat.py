@@ -88,6 +88,21 @@ class FlatParams:
         ops.fill(self.grad, 0.0)
 
 
+def closing_table_strays(table, grad_base, lo, hi):
+    """Offsets (in floats from the flat gradient's base pointer `grad_base`) of the entries of a fold table
+    (hipops.ReduceSegments or None) whose destination reaches into elements [lo, hi) -- the range a step_early() launch has
+    already updated.  The closing launch over [0, lo) would skip such an entry as "another launch's segment" and its
+    partial gradient would be lost for the step.  Pure host arithmetic on the table: no GPU, no library call."""
+    if table is None:
+        return []
+    out = []
+    for s in range(int(table.n)):
+        d0 = (int(table.dst[s] or 0) - int(grad_base)) // 4
+        if d0 < hi and d0 + int(table.len[s]) > lo:
+            out.append(d0)
+    return out
+
+
 class FlatAdam(torch.optim.Optimizer):
     """torch.optim.Adam(lr, betas=(0.9, 0.999), eps=1e-8, amsgrad=True) (reference: models/trainer.py:79-81)
     as one kernel over the flat buffer.  The step count lives on the device so that a captured hipGraph
@@ -133,6 +148,13 @@ class FlatAdam(torch.optim.Optimizer):
             # launch covers [0, lo) with the segments that are left
             lo, hi = early
             assert hi == self.flat.data.numel() and 0 < lo < hi
+            stray = closing_table_strays(d["table"] if d is not None else None, self.flat.grad.data_ptr(), lo, hi)
+            if stray:
+                # (registered after GradReducer.run_early_step took its segments: the launch over [lo, hi) is done, the one
+                # over [0, lo) would skip them -- eager steps and capture only, never on replay)
+                raise RuntimeError(f"FlatAdam.step: the deferred fold table still holds {len(stray)} segment(s) for the "
+                                   f"range [{lo}, {hi}) that step_early() has already updated, at flat offset(s) "
+                                   f"{stray[:8]}: their partial gradients would be dropped")
             ops.adam_fold_range(self.flat.data, self.flat.grad, self.m, self.v, self.vmax, 0, lo, True, float(g["lr"]),
                                 g["betas"][0], g["betas"][1], g["eps"], self.step_dev, self.grad_scale, True,
                                 d["table"] if d is not None else None, tail=d["tail"] if d is not None else None)

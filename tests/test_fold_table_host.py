@@ -49,3 +49,56 @@ def test_merging_can_be_switched_off(monkeypatch):
     segs = [(0x1000, 0x9000, 4, 8, 16), (0x1020, 0x9020, 4, 8, 16)]
     monkeypatch.setattr(G, "merge_adjacent", False)
     assert G._merged(segs) == segs
+
+
+def _table(entries):
+    """a hand-filled fold table: (dst pointer, len) per entry; sources / rows / strides do not enter the decision"""
+    from multimodal_vae_comparison_amd import hipops as H
+    t = H.ReduceSegments()
+    for j, (dp, ln) in enumerate(entries):
+        t.src[j], t.dst[j], t.rows[j], t.len[j], t.stride[j] = 0x100000 + 0x1000 * j, dp, 4, ln, ln
+    t.n = len(entries)
+    return t
+
+
+def test_closing_table_strays_names_the_entries_of_the_range_already_updated():
+    from multimodal_vae_comparison_amd import flat
+    base, lo, hi = 0x7f0000000000, 1000, 4000
+    at = lambda off: base + 4 * off
+    assert flat.closing_table_strays(None, base, lo, hi) == []
+    assert flat.closing_table_strays(_table([]), base, lo, hi) == []
+    # wholly in front of lo, ending exactly at lo: the closing launch's own segments
+    assert flat.closing_table_strays(_table([(at(0), 16), (at(984), 16), (at(500), 1)]), base, lo, hi) == []
+    # first element of the early range, its last element, one in the middle, one that straddles lo
+    t = _table([(at(0), 16), (at(1000), 1), (at(3999), 1), (at(2000), 64), (at(996), 8)])
+    assert flat.closing_table_strays(t, base, lo, hi) == [1000, 3999, 2000, 996]
+    # entries behind t.n are not looked at
+    t.n = 1
+    assert flat.closing_table_strays(t, base, lo, hi) == []
+
+
+def test_flat_adam_step_refuses_a_stray_segment_after_step_early(monkeypatch):
+    """FlatAdam.step() closing a step whose second range step_early() has updated: a deferred entry for that range raises
+    and names its offset; without one the closing launch gets [0, lo) and the table (no GPU: the launch is recorded)"""
+    import torch
+    from multimodal_vae_comparison_amd import flat
+    mod = torch.nn.Module()
+    mod.a, mod.b = torch.nn.Parameter(torch.zeros(24)), torch.nn.Parameter(torch.zeros(40))
+    fp = flat.FlatParams(mod)
+    opt = flat.FlatAdam(fp, lr=1e-3)
+    n = fp.data.numel()
+    lo = 32
+    calls = []
+    monkeypatch.setattr(ops, "adam_fold_range", lambda *a, **k: calls.append((a, k)))
+    base = fp.grad.data_ptr()
+    opt._early = (lo, n)
+    monkeypatch.setattr(G, "deferred", {"table": _table([(base, 8), (base + 4 * 40, 8)]), "tail": None})
+    with pytest.raises(RuntimeError, match=r"\[40\]"):
+        opt.step()
+    assert calls == []
+    opt._early = (lo, n)
+    ok = _table([(base, 8), (base + 4 * 24, 8)])
+    monkeypatch.setattr(G, "deferred", {"table": ok, "tail": None})
+    opt.step()
+    (a, k), = calls
+    assert a[5:8] == (0, lo, True) and a[-1] is ok and G.deferred is None

@@ -1056,6 +1056,14 @@ def test_adam_fold_flat_is_fold_then_adam(ops, hip_lib, rider):
     with pytest.raises(RuntimeError):
         ops.adam_fold_range(st["p"], st["g"], st["m"], st["v"], st["x"], split, n, False, 1e-3, 0.9, 0.999, 1e-8,
                             st["step"], 0.5, True, tb)
+    # ... and so is one whose destination is not inside the flat buffer at all: no launch of the step would fold it
+    # (it used to be skipped as "another launch's segment" by every range launch)
+    for off in (n, n - 8, -16):
+        tb.dst[0] = st["g"].data_ptr() + 4 * off
+        for lo_, hi_ in ((split, n), (0, split)):
+            with pytest.raises(RuntimeError):
+                ops.adam_fold_range(st["p"], st["g"], st["m"], st["v"], st["x"], lo_, hi_, False, 1e-3, 0.9, 0.999, 1e-8,
+                                    st["step"], 0.5, True, tb)
     p_before = st["p"].clone()
     st["g"][split:split + 100] = 1.0
     ops.adam_fold_range(st["p"], st["g"], st["m"], st["v"], st["x"], split, n, False, 1e-3, 0.9, 0.999, 1e-8, st["step"],
