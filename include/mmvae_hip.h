@@ -1252,6 +1252,42 @@ int mmvae_image_quality(const float* x, const float* y, double* out, long N, int
                         mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Text generation quality (EvaluationMixin.text_quality; csrc/text_quality.hip): per pair of a hypothesis
+ * and a reference token sequence the counts behind CER / WER, BLEU, ROUGE-L and exact match, and the reference's negative
+ * log-likelihood under the decoder's logits.  One launch, one wave per pair; a pair's outputs depend on nothing but the pair.
+ *   mmvae_text_quality: the hypothesis is `logits` (N, Th, V) fp32, or, with logits NULL, `hyp_ids` (N, Th) int32; the
+ *     reference `ref_ids` (N, Tr) int32 with `ref_lengths` (N,); `hyp_lengths` (N,) or NULL (every hypothesis Th long).
+ *     eos, trim, sep: token ids, negative for none.
+ *     1. logits: pred[n, t] = the first maximum over V (the rule of mmvae_text_decode_score; an all-equal row gives 0) is the
+ *        hypothesis; nll[n] = sum_{t < S} (lse_t - x_t[ref_t]), S = min(clamp(ref_length, 0, Tr), Th) = nll_steps[n], in double
+ *        from the fp32 values: lse_t = m_t + log sum_v exp(x_v - m_t), m_t the row's maximum, v rising; the steps t = l, l + 64,
+ *        .. are summed in that order per l < 64, the 64 sums by butterfly (xor 32, 16, .. 1).  Reference ids read here are
+ *        clamped into [0, V): a caller checks them.  Finite logits.
+ *     2. both sides: length = clamp(given length, 0, T); with eos the sequence ends before the first eos; with trim the
+ *        trailing tokens equal to trim are then dropped: h (Lh tokens) and r (Lr).
+ *     3. token_out (N, 13) = hyp_len Lh, ref_len Lr, same, edit, lcs, match[4], total[4]:
+ *        same = #{t < min(Lh, Lr): h_t == r_t}; edit = Levenshtein distance (unit costs); lcs = longest common subsequence;
+ *        for n = 1 .. max_order: total_n = max(Lh - n + 1, 0), match_n = sum over the distinct n-grams g of h of
+ *        min(count_h(g), count_r(g)); the columns n > max_order are 0.
+ *     4. sep >= 0: word_out (N, 12) = hyp_len, ref_len, edit, lcs, match[4], total[4] of the word sequences: words are the
+ *        maximal runs of tokens != sep inside h and r, equal iff they have the same tokens (compared token by token).
+ *        sep < 0: word_out NULL.
+ *     pred, nll, nll_steps are written for logits only (NULL otherwise).  Ids are non-negative.
+ *   mmvae_text_quality_lds_bytes(Th, Tr): the LDS of one workgroup (0 outside the limits); a host function.
+ *   1 <= Th, Tr <= MMVAE_TQ_MAX_STEPS, 2 <= V <= MMVAE_TQ_MAX_VOCAB, 1 <= max_order <= MMVAE_TQ_MAX_ORDER,
+ *   1 <= N <= MMVAE_TQ_MAX_ROWS = 2^26 - 1 (one launch of N workgroups of 64 threads: the grid stays below 2^32 threads; a
+ *   caller with more pairs calls again); anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_TQ_MAX_STEPS 256
+#define MMVAE_TQ_MAX_VOCAB 256
+#define MMVAE_TQ_MAX_ORDER 4
+#define MMVAE_TQ_MAX_ROWS 67108863L
+size_t mmvae_text_quality_lds_bytes(int Th, int Tr);
+int mmvae_text_quality(const float* logits, const int* hyp_ids, const int* ref_ids, const int* ref_lengths,
+                       const int* hyp_lengths, int* pred, int* token_out, int* word_out, double* nll, int* nll_steps, long N,
+                       int Th, int Tr, int V, int eos, int trim, int sep, int max_order, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

@@ -85,6 +85,7 @@ KID_MAX_SUBSET, KID_MAX_SUBSETS, KID_MAX_DEGREE = 16384, 1024, 8      # csrc/kid
 CCA_MAX_K, CCA_MAX_VIEWS, CCA_MAX_ROWS, SENTENCE_MAX_E, SENTENCE_MAX_T = 64, 8, 2 ** 31 - 1, 1024, 512      # csrc/cca.hip
 CLUSTER_MAX_K, CLUSTER_MAX_INIT, CLUSTER_MAX_ITER = 64, 64, 1000      # csrc/cluster.hip
 IQ_MIN_WIN, IQ_MAX_WIN, IQ_MAX_SIDE, IQ_MAX_CHANNELS, IQ_MAX_SCALES, IQ_MAX_ROWS = 3, 11, 64, 4, 4, 2 ** 31 - 1      # csrc/image_quality.hip
+TQ_MAX_STEPS, TQ_MAX_VOCAB, TQ_MAX_ORDER, TQ_MAX_ROWS = 256, 256, 4, 2 ** 26 - 1    # csrc/text_quality.hip
 
 
 class LmeRows(ctypes.Structure):
@@ -351,6 +352,8 @@ SIGNATURES = {
     "mmvae_image_quality_max_scales": (c_i, [c_i, c_i, c_i]),
     "mmvae_image_quality_lds_bytes": (c_sz, [c_i, c_i, c_i]),
     "mmvae_image_quality": (c_i, [c_p] * 3 + [c_l] + [c_i] * 4 + [c_p] + [c_d] * 4 + [c_i, c_p, c_p]),
+    "mmvae_text_quality_lds_bytes": (c_sz, [c_i, c_i]),
+    "mmvae_text_quality": (c_i, [c_p] * 10 + [c_l] + [c_i] * 7 + [c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

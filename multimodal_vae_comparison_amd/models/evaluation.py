@@ -1,8 +1,9 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7l) as a mixin: held-out log-likelihood, latent
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7m) as a mixin: held-out log-likelihood, latent
 classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
 density / coverage and kernel inception distance of generated images, the disentanglement of the latent code, the
 cross-modal (canonical) correlation of generations, the cluster analysis of the latents and the reconstruction quality of
-generated images against the images they were generated for (PSNR, SSIM, MS-SSIM).  What they share is here once: the
+generated images against the images they were generated for (PSNR, SSIM, MS-SSIM) and of generated text against the captions
+it was generated for (error rates, BLEU, ROUGE-L, perplexity).  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -13,6 +14,7 @@ import torch
 import torch.distributions as dist
 
 from .. import coherence as coh, ops
+from .decoders import Dec_TxtTransformer
 from .objectives import recon_rowsum
 
 # what dropout would make of a metric: the reason clauses of `_need_eval`
@@ -1115,3 +1117,117 @@ class EvaluationMixin:
                         r[key], r["per_sample"][key] = means, per
                 res[m] = r
         return res
+
+    # ---- text generation quality ---------------------------------------------------------------------
+    def text_quality(self, batches, texts=None, eps=None, eos=None, trim=0, sep=0, max_order=4):
+        """How close a generated caption is to the caption it was generated for: character and word error rate (Levenshtein
+        distance), BLEU, ROUGE-L, exact match and position accuracy of the decoder's argmax string, and the perplexity of
+        the true tokens under the decoder's logits, pair by pair on the device (ops.text_quality; csrc/text_quality.hip).
+        Row i of a reconstruction and of a cross-generation belongs to row i of the batch's data; joint samples have no
+        partner and are not walked, so that the metric works for every mixer.  `batches`: an iterable of batch dicts holding
+        every modality, the text ones one-hot (B, T, V); the references are read from the batches themselves as
+        cross_coherence reads them (argmax of the one-hot rows, the length from the mask, T where masks are None).
+        `texts`: the modalities to score; the default takes every modality with a Dec_TxtTransformer decoder and a data_dim
+        (T, V, 1) inside the kernel's limits.  `eos`, `trim`, `sep`, `max_order`: as ops.text_quality; the defaults trim = 0,
+        sep = 0 are the convention of the CdSprites+ and CUB captions here (id 0 is the space, padding decodes to 0).
+        The sets and the order of the forward() calls are those of reconstruction_quality: per batch the full batch, then only
+        modality g given for every g that a scored modality is generated from, in modality order.  A text modality that is
+        not given to a call decodes at full length (its masks are None for that call, as in cross_coherence); where it is
+        given -- the reconstruction -- its masks stay, since its encoder reads them, and the decoder's zero rows at the
+        padded steps decode to id 0.  So the "recon" figures mean what they say only while `trim` is that padding id, 0
+        (the default): with trim None or another id, every masked reconstruction carries its T - length trailing zeros
+        into the edit distance, the n-gram totals and, through sep, the word counts; the "cross" figures do not depend on it.
+        Of a generation's rows the first B are scored (the first component of a mixer that decodes several).
+        -> {m: {"recon": S, "cross": {g: S}, "n": rows, "per_sample": {"recon": P, "cross": {g: P}}}}, S the
+        ops.text_quality_summary dict {"token": {...}, "word": {...}}, P the ops.text_quality dict of the concatenated
+        per-pair device tensors (`pred` padded with -1 to the longest decoding).
+        Needs eval mode; runs without gradients; noise from the evaluation generator, or from `eps`: a list of (B, D)
+        tensors consumed in forward()'s draw order over all calls (as `eps_override`).  The training noise state, the
+        dropout counters, gradients and the optimiser stay as they are."""
+        who = "text_quality"
+        self._need_eval(who, _GENERATIONS)
+        names, batches = list(self.vaes.keys()), list(batches)
+        if not batches:
+            raise ValueError(f"{who}: `batches` is empty")
+        dims = {m: tuple(self.vaes[m].data_dim) for m in names}
+        if texts is None:
+            texts = [m for m in names if isinstance(self.vaes[m].dec, Dec_TxtTransformer) and len(dims[m]) == 3
+                     and dims[m][2] == 1 and 1 <= dims[m][0] <= ops.H.TQ_MAX_STEPS and 2 <= dims[m][1] <= ops.H.TQ_MAX_VOCAB]
+            if not texts:
+                raise ValueError(f"{who}: no modality of this model is a text tower (a Dec_TxtTransformer with data_dim (T, V, 1), "
+                                 f"T <= {ops.H.TQ_MAX_STEPS}, V <= {ops.H.TQ_MAX_VOCAB}; the data dims are "
+                                 f"{[dims[m] for m in names]}): name them in `texts`")
+        else:
+            texts = [texts] if isinstance(texts, str) else list(texts)
+            if not texts or len(set(texts)) != len(texts) or any(m not in names for m in texts):
+                raise ValueError(f"{who}: `texts` lists modalities of this model ({names})")
+        texts = [m for m in names if m in texts]
+        refs = {m: [] for m in texts}
+        for batch in batches:
+            if any(m not in batch or batch[m]["data"] is None for m in names):
+                raise ValueError(f"{who}: every batch must hold every modality (a modality without data)")
+            for m in texts:
+                onehot, masks = batch[m]["data"], batch[m]["masks"]
+                if onehot.dim() != 3 or not onehot.is_floating_point():
+                    raise ValueError(f"{who}: the text modality {m!r} must be one-hot (B, T, V), got {tuple(onehot.shape)}")
+                B, T, V = onehot.shape
+                ops.text_quality_plan(dims[m][0], T, V, eos, trim, sep, max_order)      # (refusals before the first forward())
+                if masks is not None and tuple(masks.reshape(B, -1).shape) != (B, T):
+                    raise ValueError(f"{who}: the masks of {m!r} are {tuple(masks.shape)} for data {tuple(onehot.shape)}")
+                refs[m].append((B, onehot, masks))
+        scores = {}
+
+        def score(m, key, b, loc):
+            B, V, ids, lens = refs[m][b]
+            if loc.dim() < 3 or loc.shape[-1] != V:
+                raise ValueError(f"{who}: the decoder of {m!r} returned {tuple(loc.shape)}; logits (rows, T, {V})")
+            logits = loc.reshape(-1, *loc.shape[-2:])
+            if logits.shape[0] < B:
+                raise ValueError(f"{who}: {logits.shape[0]} generated rows of {m!r} for the {B} rows of batch {b}")
+            scores.setdefault((m, key), []).append(
+                ops.text_quality(logits[:B].detach(), ids, lens, None, eos=eos, trim=trim, sep=sep, max_order=max_order))
+
+        with self._eval_noise(eps):
+            for m in texts:
+                for b, (B, onehot, masks) in enumerate(refs[m]):
+                    ids, _ = ops.text_decode_score(onehot.float().contiguous())
+                    lens = (torch.full((B,), onehot.shape[1], dtype=torch.int32, device=onehot.device) if masks is None
+                            else torch.count_nonzero(masks.reshape(B, -1), dim=-1).to(torch.int32))
+                    refs[m][b] = (B, onehot.shape[2], ids, lens)
+            for b, batch in enumerate(batches):
+                out = self.forward(batch)
+                for m in texts:
+                    score(m, "recon", b, out.mods[m].decoder_dist.loc)
+                for g in names:
+                    if any(m != g for m in texts):
+                        x = self._given_only(batch, [g])
+                        for m in texts:
+                            if m != g:
+                                x[m] = dict(x[m], masks=None)
+                        out = self.forward(x)
+                        for m in texts:
+                            if m != g:
+                                score(m, ("cross", g), b, out.mods[m].decoder_dist.loc)
+            res = {}
+            for m in texts:
+                r = {"recon": None, "cross": {}, "n": sum(ref[0] for ref in refs[m]), "per_sample": {"recon": None, "cross": {}}}
+                for (mm, key), parts in scores.items():
+                    if mm != m:
+                        continue
+                    S, P = ops.text_quality_summary(parts), self._cat_text_quality(parts)
+                    if isinstance(key, tuple):
+                        r["cross"][key[1]], r["per_sample"]["cross"][key[1]] = S, P
+                    else:
+                        r[key], r["per_sample"][key] = S, P
+                res[m] = r
+        return res
+
+    @staticmethod
+    def _cat_text_quality(parts):
+        """the ops.text_quality dicts of several batches as one (`pred` padded with -1 to the longest decoding)"""
+        level = lambda name: (None if parts[0][name] is None
+                              else {k: torch.cat([p[name][k] for p in parts]) for k in parts[0][name]})
+        Th = max(p["pred"].shape[1] for p in parts)
+        pred = torch.cat([torch.nn.functional.pad(p["pred"], (0, Th - p["pred"].shape[1]), value=-1) for p in parts])
+        return {"token": level("token"), "word": level("word"), "pred": pred, "nll": torch.cat([p["nll"] for p in parts]),
+                "nll_steps": torch.cat([p["nll_steps"] for p in parts]), "max_order": parts[0]["max_order"]}
