@@ -1288,6 +1288,53 @@ int mmvae_text_quality(const float* logits, const int* hyp_ids, const int* ref_i
                        int Th, int Tr, int V, int eos, int trim, int sep, int max_order, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Cross-modal retrieval of latents (EvaluationMixin.cross_modal_retrieval; csrc/retrieval.hip): are the
+ * sets aligned row by row?  loc (S, N, D) fp32, scale (S, N, D) fp32 or NULL (l2, cosine); pairs (P, 2) int32 = (query set,
+ * gallery set) in [0, S), the two different; match (N,) int32 or NULL for the identity: match[i] = the gallery row that is
+ * query row i's partner, -1 (or anything outside [0, N)) = no partner.  Distance of a query row q and a gallery row g, in
+ * double from the fp32 values converted on load, by direct differences, the dimensions summed in order with fma:
+ *   MMVAE_RETRIEVAL_L2      sum (mq - mg)^2
+ *   MMVAE_RETRIEVAL_COSINE  1 - sum mq mg / sqrt(sum mq^2 . sum mg^2); 1 when either norm is 0
+ *   MMVAE_RETRIEVAL_W2      sum (mq - mg)^2 + (sq - sg)^2          (squared 2-Wasserstein distance of diagonal Gaussians)
+ *   MMVAE_RETRIEVAL_SKL     sum 1/2 [(sq^2 + D^2) / sg^2 + (sg^2 + D^2) / sq^2] - 1, D = mq - mg     (KL(q || g) + KL(g || q))
+ * A pair's distance is a function of its two rows alone (one accumulator type serves the matched pair and every other pair;
+ * no dependence on tile, chunk or launch shape), so the comparisons below are exact with respect to these distances.
+ * Per (pair p, query row i), with m = match[i]:
+ *   d_match (P, N) doubles   d(i, m); NaN without a partner
+ *   less, equal (P, N) int32 #{j != m : d(i, j) < d_match}, #{j != m : d(i, j) == d_match}; -1, -1 without a partner
+ *   nn_d, nn_idx (P, N, keep) doubles / int32, keep > 0: the keep nearest gallery rows (the partner among them), ordered by
+ *     (distance, index); (+inf, -1) in the slots beyond N
+ * The N x N distances are never written; no atomics.  A workgroup owns 64 query rows and a chunk of gallery rows staged 32 at a
+ * time in LDS as doubles (mean; w2: scale; skl: variance and its reciprocal -- one divide per staged element); grid (chunks,
+ * row tiles, P): one launch serves all pairs, and with more than one chunk a second merges the chunks' partials in chunk order
+ * (integer sums; the keep smallest by (distance, index)).  The outputs are the same bits under any chunks, for two runs, and
+ * for a pair alone or beside other pairs.
+ *   chunks: 0 = the default plan, mmvae_retrieval_chunks(N, P) = min(ceil(1024 / (ceil(N / 64) P)), ceil(tiles / 8)), tiles =
+ *     ceil(N / 32); a positive value asks for that many (at most one per tile); chunks that would be empty are not launched.
+ *   ws: mmvae_retrieval_ws_bytes(N, P, keep, chunks) bytes, a multiple of 8 (0 for one chunk: ws may be NULL), 8-byte
+ *     aligned = (chunk, P, N, keep) doubles | the same int32 | less (chunk, P, N) | equal.
+ *   1 <= N <= MMVAE_RETRIEVAL_MAX_ROWS, 1 <= D <= MMVAE_RETRIEVAL_MAX_DIM, 2 <= S <= MMVAE_RETRIEVAL_MAX_SETS, 1 <= P <=
+ *   MMVAE_RETRIEVAL_MAX_PAIRS, 0 <= keep <= MMVAE_RETRIEVAL_MAX_KEEP, chunks >= 0; anything else returns
+ *   MMVAE_ERR_UNSUPPORTED and writes nothing; w2 / skl without scale is MMVAE_ERR_ARG.  Finite loc, scale > 0 and the entries
+ *   of pairs are the caller's to check (a pair outside [0, S) is skipped).  The two helpers are host functions (0 outside the
+ *   limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_RETRIEVAL_MAX_ROWS 16384
+#define MMVAE_RETRIEVAL_MAX_DIM 256
+#define MMVAE_RETRIEVAL_MAX_SETS 16
+#define MMVAE_RETRIEVAL_MAX_PAIRS 240
+#define MMVAE_RETRIEVAL_MAX_KEEP 16
+#define MMVAE_RETRIEVAL_L2 0
+#define MMVAE_RETRIEVAL_COSINE 1
+#define MMVAE_RETRIEVAL_W2 2
+#define MMVAE_RETRIEVAL_SKL 3
+int mmvae_retrieval_chunks(long N, int P);
+size_t mmvae_retrieval_ws_bytes(long N, int P, int keep, int chunks);
+int mmvae_retrieval_ranks(const float* loc, const float* scale, const int* pairs, const int* match, void* ws, double* d_match,
+                          int* less, int* equal, double* nn_d, int* nn_idx, long N, int D, int S, int P, int metric, int keep,
+                          int chunks, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)
  * ---------------------------------------------------------------------------------------------- */
 /* Embedding(one-hot.long()) + PositionalEncoding quirk (models/nn_modules.py:430-438, encoders.py:833-835).

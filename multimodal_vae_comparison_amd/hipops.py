@@ -86,6 +86,8 @@ CCA_MAX_K, CCA_MAX_VIEWS, CCA_MAX_ROWS, SENTENCE_MAX_E, SENTENCE_MAX_T = 64, 8, 
 CLUSTER_MAX_K, CLUSTER_MAX_INIT, CLUSTER_MAX_ITER = 64, 64, 1000      # csrc/cluster.hip
 IQ_MIN_WIN, IQ_MAX_WIN, IQ_MAX_SIDE, IQ_MAX_CHANNELS, IQ_MAX_SCALES, IQ_MAX_ROWS = 3, 11, 64, 4, 4, 2 ** 31 - 1      # csrc/image_quality.hip
 TQ_MAX_STEPS, TQ_MAX_VOCAB, TQ_MAX_ORDER, TQ_MAX_ROWS = 256, 256, 4, 2 ** 26 - 1    # csrc/text_quality.hip
+RETRIEVAL_MAX_ROWS, RETRIEVAL_MAX_DIM, RETRIEVAL_MAX_SETS, RETRIEVAL_MAX_PAIRS, RETRIEVAL_MAX_KEEP = 16384, 256, 16, 240, 16      # csrc/retrieval.hip
+RETRIEVAL_METRICS = {"l2": 0, "cosine": 1, "w2": 2, "skl": 3}      # MMVAE_RETRIEVAL_*; w2 and skl need the scales
 
 
 class LmeRows(ctypes.Structure):
@@ -354,6 +356,9 @@ SIGNATURES = {
     "mmvae_image_quality": (c_i, [c_p] * 3 + [c_l] + [c_i] * 4 + [c_p] + [c_d] * 4 + [c_i, c_p, c_p]),
     "mmvae_text_quality_lds_bytes": (c_sz, [c_i, c_i]),
     "mmvae_text_quality": (c_i, [c_p] * 10 + [c_l] + [c_i] * 7 + [c_p]),
+    "mmvae_retrieval_chunks": (c_i, [c_l, c_i]),
+    "mmvae_retrieval_ws_bytes": (c_sz, [c_l, c_i, c_i, c_i]),
+    "mmvae_retrieval_ranks": (c_i, [c_p] * 10 + [c_l] + [c_i] * 6 + [c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

@@ -1,9 +1,10 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7m) as a mixin: held-out log-likelihood, latent
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7n) as a mixin: held-out log-likelihood, latent
 classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
 density / coverage and kernel inception distance of generated images, the disentanglement of the latent code, the
 cross-modal (canonical) correlation of generations, the cluster analysis of the latents and the reconstruction quality of
 generated images against the images they were generated for (PSNR, SSIM, MS-SSIM) and of generated text against the captions
-it was generated for (error rates, BLEU, ROUGE-L, perplexity).  What they share is here once: the
+it was generated for (error rates, BLEU, ROUGE-L, perplexity), and the cross-modal retrieval of latents (recall@k, median
+rank, MRR).  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -933,6 +934,30 @@ class EvaluationMixin:
         dmvae), from what `_sample` returns first; None where the joint is a mixture (moe, mopoe): out of scope"""
         return None
 
+    def _walk_posteriors(self, batches):
+        """Inside `_eval_noise`: per batch the encoders, the mixing and the draws of forward() (the decoders are skipped)
+        -> ({key: loc (N,D) fp32}, {key: scale (N,D) fp32}, {key: family}) over the rows of all batches, D = n_latents (the
+        first columns: DMVAE's shared code); keys: every modality's unimodal posterior and, where `_joint_posterior`
+        gives one Gaussian, "joint".  What disentanglement and cross_modal_retrieval read."""
+        locs, scales, family = {}, {}, {}
+        for batch in batches:
+            head, drawn = self._sample(batch)
+            for _ in drawn:      # (read to its end: the draws forward() takes)
+                pass
+            found = dict(self._unimodal(head))
+            joint = self._joint_posterior(head)
+            if joint is not None:
+                found["joint"] = (joint[0], joint[1], dist.Normal)
+            for key, (loc, scale, fam) in found.items():
+                locs.setdefault(key, []).append(loc)
+                scales.setdefault(key, []).append(scale)
+                family[key] = fam
+        D = self.n_latents
+
+        def rows(ts):
+            return torch.cat([t.reshape(-1, t.shape[-1])[:, :D] for t in ts]).float().contiguous()
+        return {k: rows(v) for k, v in locs.items()}, {k: rows(v) for k, v in scales.items()}, family
+
     def disentanglement(self, batches, labels=None, eps=None, chunks=0):
         """Disentanglement of the latent code, per posterior: the decomposition of the ELBO's KL term into index-code mutual
         information, total correlation and dimension-wise KL, and the mutual information gap against labelled generative
@@ -986,28 +1011,14 @@ class EvaluationMixin:
         for key, e in eps.items():
             if key not in names + ["joint"] or not torch.is_tensor(e) or tuple(e.shape) != (N, D):
                 raise ValueError(f"{who}: eps maps {names + ['joint']} to ({N}, {D}) tensors (entry {key!r})")
-        locs, scales, family = ({m: [] for m in names + ["joint"]} for _ in range(3))
         with self._eval_noise():
-            for batch in batches:
-                head, drawn = self._sample(batch)
-                for _ in drawn:      # (read to its end: the draws forward() takes)
-                    pass
-                for m, (loc, scale, fam) in self._unimodal(head).items():
-                    locs[m].append(loc)
-                    scales[m].append(scale)
-                    family[m] = fam
-                joint = self._joint_posterior(head)
-                if joint is not None:
-                    locs["joint"].append(joint[0])
-                    scales["joint"].append(joint[1])
-                    family["joint"] = dist.Normal
-            if "joint" in eps and not locs["joint"]:
+            locs, scales, family = self._walk_posteriors(batches)
+            if "joint" in eps and "joint" not in locs:
                 raise ValueError(f"{who}: eps['joint'] given, but the joint posterior of {self.modelName} is not one Gaussian")
             pz_loc, pz_scale = (p.detach().double() for p in self.pz_params)
             res = {}
-            for key in names + (["joint"] if locs["joint"] else []):
-                loc = torch.cat([t.reshape(-1, t.shape[-1])[:, :D] for t in locs[key]]).float().contiguous()
-                scale = torch.cat([t.reshape(-1, t.shape[-1])[:, :D] for t in scales[key]]).float().contiguous()
+            for key in names + (["joint"] if "joint" in locs else []):
+                loc, scale = locs[key], scales[key]
                 laplace = family[key] is dist.Laplace
                 if key in eps:
                     e = eps[key].to(device=loc.device, dtype=torch.float32)
@@ -1024,6 +1035,104 @@ class EvaluationMixin:
                     r.update(mig=gap["mig"], per_factor=gap["per_factor"], mi_table=gap["mi"], h_z=gap["h_z"])
                 r.update(z=z, loc=loc, scale=scale)
                 res[key] = r
+        return res
+
+    # ---- cross-modal retrieval of latents -----------------------------------------------------------------
+    def cross_modal_retrieval(self, batches, metric="l2", ks=(1, 5, 10), keep=10, labels=None, use="posterior", given=None):
+        """Are the modalities aligned in the latent space, sample by sample?  For every ordered pair (a, b) of sets, query
+        row n of a retrieves from the N rows of b; its partner is row n of b, the same sample (ops.retrieval_ranks;
+        csrc/retrieval.hip: float64 distances, exact ranks).  No labels, no classifier, no weights.
+        `batches`: an iterable of batch dicts.
+        use "posterior": the sets are the modalities' unimodal posteriors (loc, scale), collected as disentanglement
+          collects them (deterministic: no draw enters; every batch must hold every modality); metric "l2" / "cosine" on
+          the means, "w2" / "skl" (squared 2-Wasserstein, symmetrised KL) on the Gaussians -- a family other than Normal
+          raises NotImplementedError there.  Keys are the modality names.
+        use "sample": the sets are latents_for(batch, g) for g in `given` (default: every single modality; keys
+          "+".join(g)); "l2" / "cosine" only.  The draws come from the evaluation generator or `eps_override`.
+        `labels`: (N,) or (N, A) integers >= 0, ROW n the label columns of sample n in batch order: per column, the share of
+        a query's k nearest rows that carry its label and the hit rate (ops.retrieval_label_precision, k <= keep).
+        Ranks are PESSIMISTIC (ops.retrieval_summary): rank = 1 + nearer rows + rows exactly as near, so collapsed
+        posteriors, all equidistant, score rank N and recall 0, not rank 1.
+        -> {"a->b": {"recall@k", "chance@k", "median_rank", "mean_rank", "mrr", "normalised_rank", "tied_rows", "n",
+                     "d_match" (N,) float64, "rank" (N,) int32, "nn_idx" (N, keep) int32,
+                     "label_precision": {column: {k: {"precision", "hit"}}} with labels}, ...,
+            "mean": the summary fields averaged over the pairs}.
+        Needs eval mode, N <= 16384 rows, D <= 256, 2 .. 16 sets, keep <= 16.  Runs without gradients: the training noise
+        state, the dropout counters, gradients and the optimiser stay as they are (use "posterior": `eps_override` too)."""
+        who = "cross_modal_retrieval"
+        self._need_eval(who, _LATENTS)
+        names, batches, D, H = list(self.vaes.keys()), list(batches), self.n_latents, ops.H
+        if not batches:
+            raise ValueError(f"{who}: `batches` is empty")
+        if metric not in H.RETRIEVAL_METRICS:
+            raise ValueError(f"{who}: metric = {metric!r} ({', '.join(H.RETRIEVAL_METRICS)})")
+        if use not in ("posterior", "sample"):
+            raise ValueError(f"{who}: use = {use!r} ('posterior' or 'sample')")
+        if use == "sample" and metric in ("w2", "skl"):
+            raise ValueError(f"{who}: metric {metric!r} compares posteriors; samples are compared by 'l2' or 'cosine'")
+        if use == "posterior" and given is not None:
+            raise ValueError(f"{who}: `given` selects the sets of use='sample'; the posteriors are the modalities' own")
+        given = [[m] for m in names] if given is None else [list(g) for g in given]
+        for g in given:
+            if not g or any(m not in names for m in g):
+                raise ValueError(f"{who}: `given` entry {g} must name modalities of this model ({names})")
+        given = [[m for m in names if m in g] for g in given]
+        keys = names if use == "posterior" else ["+".join(g) for g in given]
+        need = [names] if use == "posterior" else given
+        for batch in batches:
+            for g in need:
+                if any(m not in batch or batch[m]["data"] is None for m in g):
+                    raise ValueError(f"{who}: every batch must hold every modality" if use == "posterior" else
+                                     f"{who}: `given` entry {g} names a modality without data")
+        N, keep, ks = sum(len(b[need[0][0]]["data"]) for b in batches), int(keep), [int(k) for k in ks]
+        if len(set(keys)) != len(keys) or not 2 <= len(keys) <= H.RETRIEVAL_MAX_SETS:
+            raise ValueError(f"{who}: the sets {keys} (2 .. {H.RETRIEVAL_MAX_SETS} different sets are on the MI355X path)")
+        if not 1 <= N <= H.RETRIEVAL_MAX_ROWS or not 1 <= D <= H.RETRIEVAL_MAX_DIM or not 0 <= keep <= H.RETRIEVAL_MAX_KEEP:
+            raise ValueError(f"{who}: {N} rows of {D} latent dimensions, keep = {keep} (1 .. {H.RETRIEVAL_MAX_ROWS} rows of "
+                             f"1 .. {H.RETRIEVAL_MAX_DIM} dimensions and 0 .. {H.RETRIEVAL_MAX_KEEP} neighbours are on the "
+                             f"MI355X path)")
+        if not ks or min(ks) < 1 or len(set(ks)) != len(ks):
+            raise ValueError(f"{who}: ks = {ks} (different positive numbers of neighbours)")
+        if labels is not None:
+            labels = torch.as_tensor(labels).detach().cpu()
+            if labels.is_floating_point() or labels.dtype == torch.bool or labels.dim() not in (1, 2):
+                raise ValueError(f"{who}: labels must be an integer (N, A) array, one row per sample")
+            labels = labels.reshape(labels.shape[0], -1)
+            if labels.shape[0] != N or labels.shape[1] < 1:
+                raise ValueError(f"{who}: labels is {tuple(labels.shape)}, the batches hold {N} rows (one ROW of label "
+                                 f"columns per sample, in batch order)")
+            if int(labels.min()) < 0:
+                raise ValueError(f"{who}: labels holds negative values (classes are numbered from 0)")
+            if not [k for k in ks if k <= keep]:
+                raise ValueError(f"{who}: labels are read against the k <= keep nearest rows; ks = {ks}, keep = {keep}")
+        scale = None
+        if use == "posterior":
+            with self._eval_noise():
+                locs, scales, family = self._walk_posteriors(batches)
+            if metric in ("w2", "skl"):
+                for m in names:
+                    if family[m] is not dist.Normal:
+                        raise NotImplementedError(f"{who}: metric {metric!r} is the distance of diagonal Gaussians; the "
+                                                  f"posterior of {m!r} is {family[m].__name__}")
+                scale = torch.stack([scales[m] for m in names]).contiguous()
+            loc = torch.stack([locs[m] for m in names]).contiguous()
+        else:
+            loc = torch.stack([torch.cat([self.latents_for(b, g) for b in batches]).float() for g in given]).contiguous()
+        with torch.no_grad():
+            got = ops.retrieval_ranks(loc, scale, metric=metric, keep=keep)
+        less, equal = got["less"].cpu(), got["equal"].cpu()
+        summary = ops.retrieval_summary(less, equal, ks=ks, n_gallery=N)
+        nn_idx = got["nn_idx"].cpu()
+        res = {}
+        for p, (a, b) in enumerate(got["pairs"]):
+            r = dict(summary[p])
+            r.update(d_match=got["d_match"][p], rank=(1 + less[p] + equal[p]).to(torch.int32), nn_idx=got["nn_idx"][p])
+            if labels is not None:
+                r["label_precision"] = {c: ops.retrieval_label_precision(nn_idx[p], labels[:, c], labels[:, c],
+                                                                         [k for k in ks if k <= keep])
+                                        for c in range(labels.shape[1])}
+            res[f"{keys[a]}->{keys[b]}"] = r
+        res["mean"] = {k: sum(s[k] for s in summary) / len(summary) for k in summary[0]}
         return res
 
     # ---- reconstruction quality of generated images (DESIGN.md section 7l) ---------------------------------------------------

@@ -247,6 +247,17 @@ class MultimodalVAE(nn.Module):
                                for a, v in r["label_silhouette"].items()])
         return out
 
+    def cross_modal_retrieval(self, batches, **kwargs):
+        """cross-modal retrieval of the latents (TorchMMVAE.cross_modal_retrieval: exact ranks of every sample's partner
+        among the other modality's rows; the model must be in eval mode), logged per ordered pair as
+        test_retrieval_{recall@k,median_rank,mrr}_<a>-><b>"""
+        out = self.model.cross_modal_retrieval(batches, **kwargs)
+        for key, r in out.items():
+            if key != "mean":
+                self._log_metrics(("test_retrieval_{}_{}".format(name, key), v) for name, v in r.items()
+                                  if name.startswith("recall@") or name in ("median_rank", "mrr"))
+        return out
+
     def reconstruction_quality(self, batches, **kwargs):
         """PSNR, SSIM and MS-SSIM of reconstructions and cross-generations against the images they were generated for
         (TorchMMVAE.reconstruction_quality; the model must be in eval mode), logged as test_{psnr,ssim,ms_ssim}_<m>_recon and
