@@ -1204,6 +1204,8 @@ int mmvae_sentence_features(const int* ids, const float* emb, const float* weigh
 #define MMVAE_CLUSTER_MAX_K 64
 #define MMVAE_CLUSTER_MAX_INIT 64
 #define MMVAE_CLUSTER_MAX_ITER 1000
+#define MMVAE_GMM_MAX_D 64              /* csrc/gmm.hip: dimensions of a mixture's rows */
+#define MMVAE_GMM_MAX_DRAWS 16777216L  /* draws of one mmvae_gmm_sample call */
 size_t mmvae_cluster_lloyd_ws_ints(long rows, int restarts);
 int mmvae_cluster_sil_tiles_per_chunk(long rows, int col_tiles, int chunks);
 size_t mmvae_cluster_sil_ws_doubles(long rows, int chunks);
@@ -1333,6 +1335,50 @@ size_t mmvae_retrieval_ws_bytes(long N, int P, int keep, int chunks);
 int mmvae_retrieval_ranks(const float* loc, const float* scale, const int* pairs, const int* match, void* ws, double* d_match,
                           int* less, int* equal, double* nn_d, int* nn_idx, long N, int D, int S, int P, int metric, int keep,
                           int chunks, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Latent density estimation (EvaluationMixin.fit_latent_density / sample_latent_density; csrc/gmm.hip):
+ * EM for a mixture of C Gaussians on the rows of X (rows, D) fp32, read as double, `restarts` independent fits side by side,
+ * covariances MMVAE_GMM_FULL or MMVAE_GMM_DIAG, everything in double with scikit-learn's GaussianMixture arithmetic.
+ * Parameters per restart: weights (R, C), means (R, C, D), cov / chol / prec (R, C, D, D) (diag: (R, C, D)) = the covariance,
+ * its lower Cholesky factor L (diag: its square root) and the precision factor P = L^-T, upper triangular (diag: 1 / sqrt),
+ * logdet (R, C) = sum_d log P[d, d]; resp (R, rows, C).
+ *   E-step   log p_ik = log w_k - (D log 2 pi + |(x_i - mu_k)^T P_k|^2) / 2 + logdet_k; norm_i = logsumexp_k log p_ik (the largest
+ *            taken out); resp_ik = exp(log p_ik - norm_i); the lower bound is the mean of norm_i.
+ *   M-step   n_k = sum_i r_ik + 10 DBL_EPSILON; mu_k = sum_i r_ik x_i / n_k; full: S_k = sum_i r_ik (x_i - mu_k)(x_i - mu_k)^T
+ *            / n_k + reg_covar I; diag: sum_i r_ik x_i^2 / n_k - mu_k^2 + reg_covar; w_k = (n_k / rows) / sum_k (n_k / rows);
+ *            then L_k, P_k, logdet_k.  Sums over rows: 64-row blocks (1024-row chunks for the covariances) summed in row order
+ *            and merged in block order.  No atomics.
+ *   mmvae_gmm_em: enqueues the iterations it0 .. it0 + n_iter - 1 (numbered from 1; it0 + n_iter - 1 <= max_iter <=
+ *     MMVAE_CLUSTER_MAX_ITER) for all restarts, three launches per iteration and no host synchronisation; with it0 = 1 the
+ *     start comes first: resp = the one-hot of init (R, rows) int32 (an id outside [0, C) leaves the row out) and an M-step.
+ *     Iteration t: an E-step with the current parameters, an M-step; lb_t = that E-step's bound; |lb_t - lb_{t-1}| < tol
+ *     (lb_0 = -inf): the restart has converged, with the parameters of this M-step.  A Cholesky pivot that is not positive
+ *     and finite makes the restart degenerate.  Workgroups of a converged or degenerate restart return at once.
+ *     ws: mmvae_gmm_ws_doubles(rows, D, C, restarts, diag) doubles, ZEROED by the caller before iteration 1 and carried
+ *     between calls.  It begins with (restarts, 4) = (lb_t, n_iter = t of the last iteration run, converged, stamp: nonzero
+ *     once converged), then (restarts, MMVAE_CLUSTER_MAX_K): nonzero where a component's factorisation failed.  Neither
+ *     resp nor a density of the final parameters is left behind: mmvae_gmm_score gives them.
+ *   mmvae_gmm_score: the E-step's code on any rows under given parameters: logdens (R, rows) = norm_i; resp (R, rows, C) and
+ *     labels (R, rows) int32 = the first largest log p_ik, either may be NULL.
+ *   mmvae_gmm_sample: n draws from ONE mixture (weights (C), means (C, D), chol): draw i takes the first component k with
+ *     u[i] < w_0 + .. + w_k (summed in order, the last component takes the rest) and z = mu_k + L_k eps[i] (diag: mu_k +
+ *     sqrt(S_k) eps[i]) in double, rounded to fp32 once; u (n) doubles in [0, 1), eps (n, D) fp32; z (n, D) fp32, comp (n) int32.
+ *   1 <= rows <= MMVAE_MANIFOLD_MAX_ROWS, 1 <= D <= MMVAE_GMM_MAX_D, 1 <= C <= MMVAE_CLUSTER_MAX_K, 1 <= restarts <=
+ *   MMVAE_CLUSTER_MAX_INIT, reg_covar >= 0, tol >= 0, 1 <= n <= MMVAE_GMM_MAX_DRAWS; anything else returns
+ *   MMVAE_ERR_UNSUPPORTED and writes nothing.  The size helper is a host function (0 outside the limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_GMM_FULL 0
+#define MMVAE_GMM_DIAG 1
+size_t mmvae_gmm_ws_doubles(long rows, int D, int C, int restarts, int diag);
+int mmvae_gmm_em(const float* X, const int* init, double* weights, double* means, double* cov, double* chol, double* prec,
+                 double* logdet, double* resp, double* ws, long rows, int D, int C, int restarts, int diag, double reg_covar,
+                 double tol, int it0, int n_iter, int max_iter, mmvae_stream_t stream);
+int mmvae_gmm_score(const float* X, const double* weights, const double* means, const double* prec, const double* logdet,
+                    double* logdens, double* resp, int* labels, long rows, int D, int C, int restarts, int diag,
+                    mmvae_stream_t stream);
+int mmvae_gmm_sample(const double* weights, const double* means, const double* chol, const double* u, const float* eps,
+                     float* z, int* comp, long n, int D, int C, int diag, mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Text towers (Enc_TxtTransformer / Dec_TxtTransformer, models/encoders.py:790-837, decoders.py:668-723)

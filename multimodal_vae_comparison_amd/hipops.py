@@ -84,6 +84,7 @@ AGGPOST_MAX_ROWS, AGGPOST_MAX_FACTORS, AGGPOST_MAX_DIM = 16384, 8, 256      # cs
 KID_MAX_SUBSET, KID_MAX_SUBSETS, KID_MAX_DEGREE = 16384, 1024, 8      # csrc/kid.hip
 CCA_MAX_K, CCA_MAX_VIEWS, CCA_MAX_ROWS, SENTENCE_MAX_E, SENTENCE_MAX_T = 64, 8, 2 ** 31 - 1, 1024, 512      # csrc/cca.hip
 CLUSTER_MAX_K, CLUSTER_MAX_INIT, CLUSTER_MAX_ITER = 64, 64, 1000      # csrc/cluster.hip
+GMM_MAX_D, GMM_MAX_DRAWS, GMM_COVARIANCES = 64, 2 ** 24, {"full": 0, "diag": 1}      # csrc/gmm.hip (MMVAE_GMM_FULL / _DIAG)
 IQ_MIN_WIN, IQ_MAX_WIN, IQ_MAX_SIDE, IQ_MAX_CHANNELS, IQ_MAX_SCALES, IQ_MAX_ROWS = 3, 11, 64, 4, 4, 2 ** 31 - 1      # csrc/image_quality.hip
 TQ_MAX_STEPS, TQ_MAX_VOCAB, TQ_MAX_ORDER, TQ_MAX_ROWS = 256, 256, 4, 2 ** 26 - 1    # csrc/text_quality.hip
 RETRIEVAL_MAX_ROWS, RETRIEVAL_MAX_DIM, RETRIEVAL_MAX_SETS, RETRIEVAL_MAX_PAIRS, RETRIEVAL_MAX_KEEP = 16384, 256, 16, 240, 16      # csrc/retrieval.hip
@@ -351,6 +352,10 @@ SIGNATURES = {
     "mmvae_cluster_spread": (c_i, [c_p] * 6 + [c_l, c_i, c_i, c_p]),
     "mmvae_cluster_lloyd": (c_i, [c_p] * 4 + [c_l] + [c_i] * 6 + [c_p]),
     "mmvae_cluster_sil_sums": (c_i, [c_p] * 7 + [c_l, c_i, c_i, c_l, c_i, c_p]),
+    "mmvae_gmm_ws_doubles": (c_sz, [c_l, c_i, c_i, c_i, c_i]),
+    "mmvae_gmm_em": (c_i, [c_p] * 10 + [c_l] + [c_i] * 4 + [c_d, c_d] + [c_i] * 3 + [c_p]),
+    "mmvae_gmm_score": (c_i, [c_p] * 8 + [c_l] + [c_i] * 4 + [c_p]),
+    "mmvae_gmm_sample": (c_i, [c_p] * 7 + [c_l] + [c_i] * 3 + [c_p]),
     "mmvae_image_quality_max_scales": (c_i, [c_i, c_i, c_i]),
     "mmvae_image_quality_lds_bytes": (c_sz, [c_i, c_i, c_i]),
     "mmvae_image_quality": (c_i, [c_p] * 3 + [c_l] + [c_i] * 4 + [c_p] + [c_d] * 4 + [c_i, c_p, c_p]),

@@ -1,16 +1,18 @@
-"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7n) as a mixin: held-out log-likelihood, latent
+"""The evaluation metrics of TorchMMVAE (DESIGN.md sections 7a-7o) as a mixin: held-out log-likelihood, latent
 classification, CdSprites+ and MNIST-SVHN generation coherence, latent analysis, Frechet distance, precision / recall /
 density / coverage and kernel inception distance of generated images, the disentanglement of the latent code, the
 cross-modal (canonical) correlation of generations, the cluster analysis of the latents and the reconstruction quality of
 generated images against the images they were generated for (PSNR, SSIM, MS-SSIM) and of generated text against the captions
-it was generated for (error rates, BLEU, ROUGE-L, perplexity), and the cross-modal retrieval of latents (recall@k, median
-rank, MRR).  What they share is here once: the
+it was generated for (error rates, BLEU, ROUGE-L, perplexity), the cross-modal retrieval of latents (recall@k, median
+rank, MRR), and the ex-post density estimation of the latents (a Gaussian mixture per conditioning subset, and draws from it
+for the joint metrics).  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
 import contextlib
 import itertools
 
+import numpy as np
 import torch
 import torch.distributions as dist
 
@@ -423,6 +425,123 @@ class EvaluationMixin:
                 r["label_silhouette"][a] = ops.silhouette(z, column.to(z.device))["score"]
             res["+".join(g)] = r
         return res
+
+    # ---- latent density estimation ---------------------------------------------------------------
+    def fit_latent_density(self, batches, n_components, given=None, held_out=None, labels=None, covariance_type="full",
+                           n_init=5, max_iter=100, tol=1e-3, reg_covar=1e-6, kmeans_iter=300, seed=0):
+        """Ex-post density estimation (Ghosh et al. 2020): per conditioning subset a mixture of `n_components` Gaussians
+        fitted by EM to the latents `latents_for` gives for every batch (ops.gmm_fit, scikit-learn's GaussianMixture
+        arithmetic in float64: `covariance_type` "full" or "diag", `tol`, `max_iter`, `reg_covar`).  `n_init` restarts run
+        side by side, restart r from the labels of restart r of ops.kmeans_fit (`kmeans_iter` iterations at the most) on
+        the start rows ops.kmeans_draw(N, n_components, n_init, seed); the restart with the largest lower bound is kept.
+        `batches`, `held_out`: iterables of batch dicts; `given`: modality-name lists (default_given()), keys
+        "+".join(names); per subset the latents of `batches` are drawn first, then those of `held_out`.
+        `labels`: (N,) or (N, A) integers >= 0, ROW n the label columns of sample n in batch order.
+        -> {key: {"weights" (C,), "means" (C,D), "covariances", "cholesky", "precisions_cholesky" (C,D,D) | (C,D), "log_det"
+                  (C,), "covariance_type", "lower_bound", "n_iter", "converged", "restarts": {"lower_bound", "n_iter",
+                  "converged", "degenerate"} (R,), "labels" (N,) int32 (the most probable component), "log_density" (N,),
+                  "score": the mean log-density of the fitted latents, "held_out_score": that of the held-out latents under
+                  the fit | None, "n_parameters", "bic", "aic" (ops.gmm_information), "n_rows",
+                  "agreement": {a: ops.cluster_agreement(labels[:, a], the hard assignments)}}}.
+        An entry is what sample_latent_density, ops.gmm_score and ops.gmm_sample take.
+        Needs eval mode, 1 <= n_components <= min(64, N), N <= 16384 rows, D <= 64.  Runs without gradients; the draws come
+        from the evaluation generator or `eps_override`: the training noise state, the dropout counters, gradients and the
+        optimiser stay as they are."""
+        who = "fit_latent_density"
+        self._need_eval(who, _LATENTS)
+        names, batches = list(self.vaes.keys()), list(batches)
+        held_out = None if held_out is None else list(held_out)
+        if not batches or (held_out is not None and not held_out):
+            raise ValueError(f"{who}: `batches` is empty" if not batches else f"{who}: `held_out` is empty (None: no held-out "
+                             f"score)")
+        given = self.default_given() if given is None else [list(g) for g in given]
+        for g in given:
+            if not g or any(m not in names for m in g):
+                raise ValueError(f"{who}: `given` entry {g} must name modalities of this model ({names})")
+        given = [[m for m in names if m in g] for g in given]
+        for batch in batches + (held_out or []):
+            for g in given:
+                if any(m not in batch or batch[m]["data"] is None for m in g):
+                    raise ValueError(f"{who}: `given` entry {g} names a modality without data")
+        N = sum(len(b[given[0][0]]["data"]) for b in batches)
+        H = ops.H
+        if not 1 <= N <= H.MANIFOLD_MAX_ROWS or not 1 <= self.n_latents <= H.GMM_MAX_D:
+            raise ValueError(f"{who}: {N} rows of {self.n_latents} latent dimensions (1 .. {H.MANIFOLD_MAX_ROWS} rows of 1 .. "
+                             f"{H.GMM_MAX_D} dimensions are on the MI355X path)")
+        if held_out is not None and sum(len(b[given[0][0]]["data"]) for b in held_out) > H.MANIFOLD_MAX_ROWS:
+            raise ValueError(f"{who}: `held_out` holds more than {H.MANIFOLD_MAX_ROWS} rows")
+        C, n_init, kmeans_iter = int(n_components), int(n_init), int(kmeans_iter)
+        if not 1 <= C <= H.CLUSTER_MAX_K or C > N:
+            raise ValueError(f"{who}: n_components = {C} for {N} rows (1 .. {H.CLUSTER_MAX_K} components, at most one per row, "
+                             f"are on the MI355X path)")
+        if not 1 <= n_init <= H.CLUSTER_MAX_INIT or not 1 <= kmeans_iter <= H.CLUSTER_MAX_ITER:
+            raise ValueError(f"{who}: n_init = {n_init}, kmeans_iter = {kmeans_iter} (1 .. {H.CLUSTER_MAX_INIT} restarts of 1 .. "
+                             f"{H.CLUSTER_MAX_ITER} iterations are on the MI355X path)")
+        if covariance_type not in H.GMM_COVARIANCES:
+            raise ValueError(f"{who}: covariance_type = {covariance_type!r} ({', '.join(map(repr, H.GMM_COVARIANCES))})")
+        reg_covar, tol, max_iter = ops._gmm_fit_args(who, reg_covar, tol, max_iter)
+        if labels is not None:
+            labels = torch.as_tensor(labels).detach().cpu()
+            if labels.is_floating_point() or labels.dtype == torch.bool or labels.dim() not in (1, 2):
+                raise ValueError(f"{who}: labels must be an integer (N, A) array, one row per sample")
+            labels = labels.reshape(labels.shape[0], -1)
+            if labels.shape[0] != N or labels.shape[1] < 1:
+                raise ValueError(f"{who}: labels is {tuple(labels.shape)}, the batches hold {N} rows (one ROW of label "
+                                 f"columns per sample, in batch order)")
+            if int(labels.min()) < 0:
+                raise ValueError(f"{who}: labels holds negative values (classes are numbered from 0)")
+        res = {}
+        for g in given:
+            z = torch.cat([self.latents_for(b, g) for b in batches]).float().contiguous()
+            z_held = None if held_out is None else torch.cat([self.latents_for(b, g) for b in held_out]).float().contiguous()
+            start = torch.from_numpy(ops.kmeans_draw(N, C, n_init, seed)).to(z.device)
+            km = ops.kmeans_fit(z, start, max_iter=kmeans_iter)
+            fit = ops.gmm_fit(z, km["labels"], covariance_type=covariance_type, reg_covar=reg_covar, tol=tol,
+                              max_iter=max_iter, n_components=C)
+            best = fit["best"]
+            r = {k: fit[k][best].contiguous() for k in ("weights", "means", "covariances", "cholesky", "precisions_cholesky",
+                                                        "log_det", "labels", "log_density")}
+            r.update({"covariance_type": covariance_type, "lower_bound": float(fit["lower_bound"][best]),
+                      "n_iter": int(fit["n_iter"][best]), "converged": bool(fit["converged"][best]),
+                      "restarts": {k: fit[k] for k in ("lower_bound", "n_iter", "converged", "degenerate")},
+                      "score": float(fit["log_density"][best].cpu().numpy().mean()), "held_out_score": None, "n_rows": N,
+                      "agreement": {}})
+            r.update(ops.gmm_information(fit, N))
+            if z_held is not None:
+                r["held_out_score"] = ops.gmm_score(z_held, r)["score"]
+            for a in range(0 if labels is None else labels.shape[1]):
+                r["agreement"][a] = ops.cluster_agreement(labels[:, a].contiguous(), r["labels"].cpu())
+            res["+".join(g)] = r
+        return res
+
+    def sample_latent_density(self, density, n, seed=0, u=None, eps=None):
+        """n latents from a fitted density (one subset's entry of fit_latent_density) in the form the joint metrics take:
+        ops.gmm_sample picks the components with `u` ((n,) float64 in [0, 1); None: numpy.random.RandomState(seed)
+        .random_sample(n)) and draws z = mu_k + L_k eps (`eps` (n, D); None: the evaluation generator).
+        -> {"latents" (n, D) fp32, "components" (n,) int32, "joint_eps" (n, D) fp32 = (z - loc) / scale of pz_params}:
+        handed as `eps=` to joint_coherence / digit_joint_coherence or as `joint_eps=` to frechet_distances,
+        manifold_metrics, kernel_distances and cross_modal_correlation, `_prior_sample` decodes these latents in place of a
+        prior sample (loc + scale joint_eps = z up to one rounding).
+        Needs eval mode; runs without gradients; models with private latents (DMVAE) have no joint latent to decode:
+        NotImplementedError."""
+        who = "sample_latent_density"
+        self._need_eval(who, _GENERATIONS, shared_latents=True)
+        n = int(n)
+        if n < 1:
+            raise ValueError(f"{who}: n = {n}")
+        if not isinstance(density, dict) or not torch.is_tensor(density.get("weights")) or density["weights"].dim() != 1 or \
+                not torch.is_tensor(density.get("means")) or density["means"].dim() != 2:
+            raise ValueError(f"{who}: density is one subset's entry of fit_latent_density (weights (C,), means (C, D), ...)")
+        D = density["means"].shape[1]
+        if D != self.n_latents:
+            raise ValueError(f"{who}: the density has D = {D} dimensions, the model {self.n_latents} latent dimensions")
+        if u is None:
+            u = torch.from_numpy(np.random.RandomState(seed).random_sample(n))
+        with torch.no_grad():
+            z, comp = ops.gmm_sample(density, n, u=u, eps=eps, state=self._noise_state(evaluation=True))
+            loc, scale = self.pz_params
+            joint_eps = ((z.double() - loc.double()) / scale.double()).float()      # (one rounding)
+        return {"latents": z, "components": comp, "joint_eps": joint_eps}
 
     # ---- generation coherence (DESIGN.md section 7c) ------------------------------------------------------------------
     def _image_text(self, image, text):

@@ -247,6 +247,24 @@ class MultimodalVAE(nn.Module):
                                for a, v in r["label_silhouette"].items()])
         return out
 
+    def fit_latent_density(self, batches, n_components, **kwargs):
+        """ex-post density estimation of the latents (TorchMMVAE.fit_latent_density: a Gaussian mixture per conditioning
+        subset; the model must be in eval mode), logged as test_density_{score,bic,aic}_<key>, test_density_held_out_<key>
+        where held-out batches were given and test_density_{ari,nmi,purity}_<key>_<a> where labels were"""
+        out = self.model.fit_latent_density(batches, n_components, **kwargs)
+        for key, r in out.items():
+            self._log_metrics([("test_density_{}_{}".format(name, key), r[name]) for name in ("score", "bic", "aic")] +
+                              ([] if r["held_out_score"] is None
+                               else [("test_density_held_out_{}".format(key), r["held_out_score"])]) +
+                              [("test_density_{}_{}_{}".format(name, key, a), agree[name])
+                               for a, agree in r["agreement"].items() for name in ("ari", "nmi", "purity")])
+        return out
+
+    def sample_latent_density(self, density, n, **kwargs):
+        """latents drawn from a fitted density, as the joint metrics take them (TorchMMVAE.sample_latent_density; nothing
+        is logged)"""
+        return self.model.sample_latent_density(density, n, **kwargs)
+
     def cross_modal_retrieval(self, batches, **kwargs):
         """cross-modal retrieval of the latents (TorchMMVAE.cross_modal_retrieval: exact ranks of every sample's partner
         among the other modality's rows; the model must be in eval mode), logged per ordered pair as
