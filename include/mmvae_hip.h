@@ -352,6 +352,44 @@ int mmvae_poe_reparam_kl_bwd_acc(const mmvae_poe_bwd_args* a, const float* theta
                                  int ld_in, int raw_heads, int accumulate, unsigned acc_packed, mmvae_stream_t stream);
 size_t mmvae_poe_ws_floats(int B, int D);
 
+/* ------------------------------------------------------------------------------------------------
+ * Total-correlation fusion (MVTCAE: Hwang et al., NeurIPS 2021): product of experts -> ONE reparameterised sample ->
+ * KL of the joint to the prior AND KL of the joint to every expert, forward and backward (csrc/tcfusion.hip).
+ * The conventions are those of mmvae_poe_reparam_kl_*: up to MMVAE_MAX_EXPERTS expert pointers by value, mu[e] / lv[e]
+ * (and dmu[e] / dlv[e]) with row stride ld_in, eps / z / dz contiguous (B,D), raw_heads != 0: lv[e] points at the raw
+ * logvar-head output u and lv = softmax(u, -1) + 1e-6 is applied here, forward and backward (dlv[e] receives d/du; one
+ * column: du = 0).  The product's variance is used as the scale, as everywhere in this library.
+ *   T_e = 1 / (exp(lv_e) + 1e-8), P = sum_e T_e, mu_J = sum_e mu_e T_e / P, V_J = 1 / P (no prior expert),
+ *   z = mu_J + V_J eps, sp = softmax(theta) D
+ *   joint (2,B,D) : mu_J, V_J
+ *   kl (E+1,B)    : row E: sum_d KL(N(mu_J, sigma = V_J) || N(0, sp))
+ *                   row e: sum_d KL(N(mu_J, sigma = V_J) || N(mu_e, sigma = 1 / T_e))
+ *                          = sum_d [ -log(T_e V_J) + T_e^2 (V_J^2 + (mu_J - mu_e)^2) / 2 - 1 / 2 ]
+ * bwd: dz (B,D), dkl (E+1,B) -> dmu[e], dlv[e], dtheta (D) (accumulate != 0: added to what dtheta holds).  dz / dkl NULL: an
+ *   absent upstream gradient, taken as zeros; dtheta NULL: the prior gradient is not wanted (no second launch).  Nothing is
+ *   detached: row e differentiates through the joint and through expert e's own parameters.  Every workgroup writes its
+ *   partial prior-gradient row to ws (mmvae_tc_fusion_ws_floats(B, D) floats), a second one-workgroup launch folds them:
+ *   every sum in one fixed order, no atomics -- the results are bit-reproducible from run to run.
+ * 1 <= E <= MMVAE_MAX_EXPERTS and D <= 256; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing
+ * (mmvae_tc_fusion_ws_floats: 0).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* mu[MMVAE_MAX_EXPERTS];
+  const float* lv[MMVAE_MAX_EXPERTS];
+} mmvae_tc_fwd_args;
+typedef struct {
+  const float* mu[MMVAE_MAX_EXPERTS];
+  const float* lv[MMVAE_MAX_EXPERTS];
+  float* dmu[MMVAE_MAX_EXPERTS];
+  float* dlv[MMVAE_MAX_EXPERTS];
+} mmvae_tc_bwd_args;
+int mmvae_tc_fusion_fwd(const mmvae_tc_fwd_args* a, const float* theta, const float* eps, float* joint, float* kl,
+                        float* z, int E, int B, int D, int ld_in, int raw_heads, mmvae_stream_t stream);
+int mmvae_tc_fusion_bwd(const mmvae_tc_bwd_args* a, const float* theta, const float* eps, const float* dz,
+                        const float* dkl, float* dtheta, float* ws, int E, int B, int D, int ld_in, int raw_heads,
+                        int accumulate, mmvae_stream_t stream);
+size_t mmvae_tc_fusion_ws_floats(int B, int D);
+
 /* Latent samples -> decoder inputs, and the transpose (round 6).  The reference decodes every subset's sample in a call of its
  * own (POE.objective, models/mmvae_models.py:159-187) and builds DMVAE's decoder inputs with torch.cat([z_shared, z_private], -1)
  * per pass (:494-502); here a decoder's passes are one batch, and the batches of ALL decoders are written by one launch:

@@ -3,13 +3,8 @@
 // lanes over the latent dimension, wave-shuffle reductions; no LDS, no atomics (deterministic).
 #include "common.hpp"
 #include "noise.hpp"
+#include "latent_rows.hpp"
 #include <type_traits>
-
-// one wave per sample up to this many waves, then samples round robin (round 4: 128 -> 512; a wave's samples are a serial
-// chain of L2 round trips: same box, ms/step of the cfg2 step at batch 512 / 1000 with 128 / 256 / 512 waves: 0.928 / 0.921 /
-// 0.919 and 1.581 / 1.564 / 1.557)
-#define POE_MAX_WAVES 512
-#define POE_SLOTS 4  // D <= 64 * POE_SLOTS
 
 // ---------------------------------------------------------------------------------------------
 // VaeComponent.process_output (models/encoders.py:49-54): lv = softmax(u, -1) + 1e-6 on h[:, D:2D]
@@ -52,61 +47,6 @@ extern "C" int mmvae_head_softmax_bwd(const float* h, float* dh, int B, int D, m
   MMVAE_CHECK_ARG(h && dh && B > 0 && D > 0);
   hipLaunchKernelGGL(head_softmax_bwd_kernel, dim3((B + 3) / 4), dim3(256), 0, (hipStream_t)stream, h, dh, B, D);
   return mmvae_launch_status();
-}
-
-// ---------------------------------------------------------------------------------------------
-// prior sigma: softmax(theta) * D   (models/mmvae_models.py:274-276), computed per wave
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void prior_sigma(const float* __restrict__ theta, int D, int lane, float sp[POE_SLOTS],
-                                            float sm[POE_SLOTS]) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    int d = lane + 64 * s;
-    if (d < D) mx = fmaxf(mx, theta[d]);
-  }
-  mx = wave_max(mx);
-  float sum = 0.f;
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    int d = lane + 64 * s;
-    sm[s] = d < D ? expf(theta[d] - mx) : 0.f;
-    sum += sm[s];
-  }
-  sum = wave_sum(sum);
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    sm[s] = sm[s] / sum;
-    sp[s] = sm[s] * (float)D;
-  }
-}
-
-// statistics of softmax(u[0..D)) for one row: max and 1 / sum exp  (raw heads: lv = softmax(u) + 1e-6 computed here
-// instead of by a head_softmax launch per tower and direction)
-__device__ __forceinline__ void row_softmax_stats(const float* __restrict__ u, int D, int lane, float* mx_out,
-                                                  float* inv_out) {
-  float mx = -INFINITY;
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    if (d < D) mx = fmaxf(mx, u[d]);
-  }
-  mx = wave_max(mx);
-  float sum = 0.f;
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    if (d < D) sum += expf(u[d] - mx);
-  }
-  sum = wave_sum(sum);
-  *mx_out = mx;
-  *inv_out = 1.0f / sum;
-}
-
-__device__ __forceinline__ float kl_elem(float mu, float s, float sp) {
-  float r = s / sp, m = mu / sp;
-  float vr = r * r;
-  return 0.5f * (vr + m * m - 1.0f - logf(vr));
 }
 
 __global__ __launch_bounds__(256) void poe_fwd_kernel(mmvae_poe_fwd_args a, const float* __restrict__ theta,
@@ -613,11 +553,6 @@ static inline bool poe_fast_visit(int E, int n_z, int D, F&& f) {
   POE_CASE(3, 0) POE_CASE(3, 1) POE_CASE(3, 2) POE_CASE(3, 3)
 #undef POE_CASE
   return false;
-}
-
-static inline int poe_blocks(int B) {
-  int waves = B < POE_MAX_WAVES ? B : POE_MAX_WAVES;
-  return (waves + 3) / 4;
 }
 
 extern "C" size_t mmvae_poe_ws_floats(int B, int D) { return (size_t)poe_blocks(B) * 4 * D; }

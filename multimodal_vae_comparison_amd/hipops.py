@@ -41,6 +41,15 @@ class PoeBwdArgs(ctypes.Structure):
                 ("dz", c_p * MAX_EXPERTS), ("dmu", c_p * MAX_EXPERTS), ("dlv", c_p * MAX_EXPERTS)]
 
 
+class TcFwdArgs(ctypes.Structure):
+    _fields_ = [("mu", c_p * MAX_EXPERTS), ("lv", c_p * MAX_EXPERTS)]
+
+
+class TcBwdArgs(ctypes.Structure):
+    _fields_ = [("mu", c_p * MAX_EXPERTS), ("lv", c_p * MAX_EXPERTS), ("dmu", c_p * MAX_EXPERTS),
+                ("dlv", c_p * MAX_EXPERTS)]
+
+
 FAN_MAX_BLOCKS, FAN_MAX_SRC, FAN_MAX_USES = 16, 8, 4
 
 
@@ -191,6 +200,9 @@ SIGNATURES = {
     "mmvae_poe_reparam_kl_bwd_acc": (c_i, [ctypes.POINTER(PoeBwdArgs), c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_u, c_i,
                                            c_i, c_i, c_i, c_i, c_u, c_p]),
     "mmvae_poe_ws_floats": (c_sz, [c_i, c_i]),
+    "mmvae_tc_fusion_fwd": (c_i, [ctypes.POINTER(TcFwdArgs)] + [c_p] * 5 + [c_i] * 5 + [c_p]),
+    "mmvae_tc_fusion_bwd": (c_i, [ctypes.POINTER(TcBwdArgs)] + [c_p] * 6 + [c_i] * 6 + [c_p]),
+    "mmvae_tc_fusion_ws_floats": (c_sz, [c_i, c_i]),
     "mmvae_bce_rowsum_fwd": (c_i, [c_p] * 3 + [c_i] * 3 + [c_p]),
     "mmvae_bce_sigmoid_clamp_bwd": (c_i, [c_p] * 4 + [c_i] * 3 + [c_p]),
     "mmvae_bce_rowsum_bwd": (c_i, [c_p] * 4 + [c_i] * 2 + [c_p]),

@@ -4,6 +4,7 @@ from .mmvae_models import MOE as moe
 from .mmvae_models import POE as poe
 from .mmvae_models import MoPOE as mopoe
 from .mmvae_models import DMVAE as dmvae
+from .mmvae_models import MVTCAE as mvtcae
 from .vae import VAE
 
-__all__ = ["moe", "poe", "mopoe", "dmvae", "VAE"]
+__all__ = ["moe", "poe", "mopoe", "dmvae", "mvtcae", "VAE"]

@@ -510,6 +510,8 @@ class POE(TorchMMVAE):
             self.decoder_calls_moved += pick[k] is not streams[i]
         return out
 
+    prior_expert = True      # the N(0, 1) expert joins the product (MVTCAE: it does not)
+
     def modality_mixing(self, x):
         """mmvae_models.py:210-232: prior expert + present encoders -> product"""
         mus, lvs, single = [], [], {}
@@ -519,7 +521,7 @@ class POE(TorchMMVAE):
                 single[m] = normal(mu, lv)
                 mus.append(mu)
                 lvs.append(lv)
-        mu, var = self.product_of_experts(mus, lvs, with_prior=True)
+        mu, var = self.product_of_experts(mus, lvs, with_prior=self.prior_expert)
         return mu, var, single
 
     def _proposal_size(self, n_given):
@@ -548,6 +550,98 @@ class POE(TorchMMVAE):
         z_d = {key: {"latents": z, "masks": inputs[key]["masks"]} for key, z in zs}
         px_d = {mod: normal(*vae.dec(z_d[mod])) for mod, vae in self.vaes.items()}
         return self.make_output_dict(single, px_d, z_d, joint_dist={key: qz_x for key in z_d})
+
+
+class MVTCAE(POE):
+    """MVTCAE, total-correlation objective (Hwang et al., NeurIPS 2021; not in the reference: a plugin on the base class's
+    contract).  Joint = product of the PRESENT experts without a prior expert; one z per step, every modality decoded once
+    from it.  With M modalities, r_m the reconstruction row sums (the sign POE gives them), kl[M] = KL(joint || prior) and
+    kl[e] = KL(joint || q_e) -- the conditional terms that pull the joint towards every unimodal posterior:
+
+        loss = sum_b [ (M - alpha) / M sum_m llik_m r_m(b) + beta ((1 - alpha) kl[M][b] + alpha / M sum_e kl[e][b]) ]
+
+    `alpha` in [0, 1] comes from the config's `model_cfg: {alpha: ...}` (default 5/6).  The experts enter the KL terms
+    with the numbers the product gave them (variance used as the scale, the convention of every mixer here).  The latent
+    side of a step is ONE fused kernel each way (ops.tc_fusion).  Inference, the evaluation hooks and the metrics are POE's
+    on the product without the prior expert."""
+
+    prior_expert = False
+
+    def __init__(self, vaes, n_latents: int, obj_config: dict, model_config=None):
+        for name, vae in vaes.items():
+            if vae.prior_str not in ("normal", "gaussian"):
+                raise NotImplementedError(f"mvtcae: prior '{vae.prior_str}' ({name}): the KL terms between the joint and "
+                                          f"the experts are Gaussian; only normal priors are on this path")
+            if vae.private_latents is not None:
+                raise NotImplementedError(f"mvtcae: private_latents ({name}): the total-correlation objective has one "
+                                          f"shared latent space")
+        if obj_config.get("obj", "elbo") != "elbo":
+            raise NotImplementedError(f"mvtcae: obj '{obj_config['obj']}': the total-correlation bound is built on obj elbo")
+        if int(obj_config.get("K", 1)) != 1:
+            raise NotImplementedError(f"mvtcae: K = {obj_config['K']}: one latent sample per step (K = 1) only")
+        alpha = float((model_config or {}).get("alpha", 5.0 / 6.0))
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"mvtcae: model_cfg alpha = {alpha} must lie in [0, 1]")
+        super().__init__(vaes, n_latents, obj_config, model_config)
+        self.modelName = "mvtcae"
+        self.alpha = alpha
+
+    def _tc_weights(self):
+        """rows of the loss assembly (loss, kld, kld_prior, kld_cond) over [M recon rows, M expert KL rows, the prior's]"""
+        M, a, beta = len(self.vaes), self.alpha, float(self.obj_fn.beta)
+        lam = [float(v.llik_scaling) * (M - a) / M for v in self.vaes.values()]
+        return [lam + [beta * a / M] * M + [beta * (1.0 - a)],
+                [0.0] * M + [a / M] * M + [1.0 - a],
+                [0.0] * M + [0.0] * M + [1.0],
+                [0.0] * M + [1.0 / M] * M + [0.0]]
+
+    def objective(self, mods):
+        """one encoder pass and one decoder pass per modality (POE: 2^(M-1) and 2^M - 1), the towers on their streams"""
+        names = list(self.vaes.keys())
+        M = len(names)
+        missing = [n for n in names if mods[n]["data"] is None]
+        if missing:
+            raise ValueError(f"mvtcae.objective: {missing} has no data: training needs every modality (evaluation with "
+                             f"missing modalities goes through forward() / the metrics' given=)")
+        self._begin_step()
+        theta = self._pz_params[1]
+        dev = mods[names[0]]["data"].device
+        encs = [v.enc for v in self.vaes.values()]
+        # lv = softmax(u) + eta is applied by the fusion kernel (as POE.objective does): no softmax launch behind the heads
+        raw_heads = dev.type == "cuda" and all(hasattr(e, "raw_heads") and e.enc_mu_logvar for e in encs)
+        try:
+            for e in encs if raw_heads else []:
+                e.raw_heads = True
+            packed, streams, cur, real, dev = self._encode_towers(mods)
+        finally:
+            for e in encs if raw_heads else []:
+                e.raw_heads = False
+        # tensors that cross streams are registered with the consuming stream (see POE.objective)
+        for t in packed:
+            _uses(t, cur)
+        B, D = packed[0].shape[0], self.n_latents
+        eps = self._draw(B, D, dev)
+        _, kl, z = ops.tc_fusion(theta, packed, eps, theta.grad, raw=raw_heads)
+        for st in real:
+            _uses(z, st)
+        recs = [None] * M
+        self._fork(streams, dev, mods)
+        for i, (n, st) in enumerate(zip(names, streams)):
+            vae = self.vaes[n]
+            with torch.cuda.stream(st):
+                out, _ = vae.dec({"latents": z.unsqueeze(0), "masks": mods[n]["masks"]})
+                recs[i] = recon_rowsum(vae.ltype, out, mods[n])      # (B,)
+            _uses(recs[i], cur)
+        self._join(streams, dev)
+        out = ops.lincomb_rows(recs + [kl], self._tc_weights())
+        with torch.no_grad():      # logged only: every modality's row sum over the batch
+            if M <= ops.H.LC_MAX_OUT:
+                ind = list(ops.lincomb_rows([r.detach() for r in recs],
+                                            [[1.0 if j == i else 0.0 for j in range(M)] for i in range(M)]))
+            else:
+                ind = [r.detach().sum() for r in recs]
+        return {"loss": out[0], "reconstruction_loss": ind, "kld": out[1], "kld_prior": out[2].detach(),
+                "kld_cond": out[3].detach()}
 
 
 class MOE(TorchMMVAE):

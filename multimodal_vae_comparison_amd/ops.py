@@ -1380,6 +1380,71 @@ class PoeReparamKL(Function):
                 *([None] * ctx.n_eps_in))
 
 
+class TcFusion(Function):
+    """Product of experts (no prior expert) -> ONE reparameterised sample -> KL of the joint to the prior (row E) and to
+    every expert (rows 0 .. E-1): MVTCAE's latent op (csrc/tcfusion.hip).  packed[e]: (B, 2 D) = [mu_e | lv_e] head
+    outputs.  Returns joint (2,B,D) [not differentiable], kl (E+1,B), z (B,D)."""
+
+    @staticmethod
+    def forward(ctx, theta, gtheta, raw, eps, *packed):
+        packed = [H.f32c(t) for t in packed]
+        theta, eps = H.f32c(theta), H.f32c(eps)
+        E = len(packed)
+        B, D2 = packed[0].shape
+        D = D2 // 2
+        assert all(p.shape == (B, D2) for p in packed) and eps.shape == (B, D) and theta.numel() == D
+        dev = packed[0].device
+        joint = torch.empty(2, B, D, device=dev)
+        kl = torch.empty(E + 1, B, device=dev)
+        z = torch.empty(B, D, device=dev)
+        a = H.TcFwdArgs()
+        for e, p in enumerate(packed[:H.MAX_EXPERTS]):
+            a.mu[e] = p.data_ptr()
+            a.lv[e] = p.data_ptr() + 4 * D
+        _call("mmvae_tc_fusion_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(joint), H.ptr(kl), H.ptr(z), E, B, D,
+              D2, int(bool(raw)), H.stream())
+        ctx.save_for_backward(theta, eps, *packed)
+        ctx.cfg = (gtheta, E, B, D, int(bool(raw)))
+        ctx.mark_non_differentiable(joint)
+        ctx.set_materialize_grads(False)
+        return joint, kl, z
+
+    @staticmethod
+    def backward(ctx, _dj, dkl, dz):
+        gtheta, E, B, D, raw = ctx.cfg
+        theta, eps = ctx.saved_tensors[:2]
+        packed = ctx.saved_tensors[2:]
+        dev = theta.device
+        # (an absent upstream gradient goes in as NULL: the kernel takes it as zeros)
+        dkl = H.f32c(dkl) if dkl is not None else None
+        dz = H.f32c(dz) if dz is not None else None
+        dpacked = [torch.empty_like(p) for p in packed]
+        a = H.TcBwdArgs()
+        for e, p in enumerate(packed):
+            a.mu[e] = p.data_ptr()
+            a.lv[e] = p.data_ptr() + 4 * D
+            a.dmu[e] = dpacked[e].data_ptr()
+            a.dlv[e] = dpacked[e].data_ptr() + 4 * D
+        if gtheta is not None:
+            dth, acc, ret = gtheta, 1, None
+            GradReducer.writes(dev, gtheta)
+        elif ctx.needs_input_grad[0]:
+            dth = ret = torch.empty_like(theta)
+            acc = 0
+        else:
+            dth, acc, ret = None, 0, None
+        ws = H.workspace(H.lib().mmvae_tc_fusion_ws_floats(B, D), dev)
+        _call("mmvae_tc_fusion_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(dz), H.ptr(dkl), H.ptr(dth),
+              H.ptr(ws), E, B, D, 2 * D, raw, acc, H.stream())
+        return (ret, None, None, None, *dpacked)
+
+
+def tc_fusion(theta, packed, eps, gtheta=None, raw=False):
+    """-> joint (2,B,D), kl (E+1,B), z (B,D) of the total-correlation fusion (TcFusion); gtheta: the prior parameter's
+    preset gradient view, which the backward pass then adds to; raw: packed = [mu | raw logvar-head output]"""
+    return TcFusion.apply(theta, gtheta, raw, eps, *packed)
+
+
 class RowsFan(Function):
     """Latent samples -> the decoders' input batches in ONE launch, and every sample's gradient as ONE sum in backward
     (csrc/latent.hip: mmvae_rows_fan_fwd / _bwd).  plan = [(R, W, [(source index, row block r, first column c0), ...]), ...]:
