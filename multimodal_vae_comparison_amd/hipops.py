@@ -505,6 +505,16 @@ def check(rc, name):
         raise RuntimeError(f"{name} failed: {_ERR.get(rc, rc)}")
 
 
+CALLS = [0]      # C-ABI calls issued so far (trainer.capture reports how many one captured step holds)
+
+
+def call(name, *args):
+    """the C-ABI entry point `name`, counted and its return code checked.  Every module says `H.call(...)`: the attribute
+    is looked up at each call, so a tool that replaces hipops.call sees every one"""
+    CALLS[0] += 1
+    check(getattr(lib(), name)(*args), name)
+
+
 def stream():
     return torch.cuda.current_stream().cuda_stream
 

@@ -479,7 +479,7 @@ class EvaluationMixin:
                              f"{H.CLUSTER_MAX_ITER} iterations are on the MI355X path)")
         if covariance_type not in H.GMM_COVARIANCES:
             raise ValueError(f"{who}: covariance_type = {covariance_type!r} ({', '.join(map(repr, H.GMM_COVARIANCES))})")
-        reg_covar, tol, max_iter = ops._gmm_fit_args(who, reg_covar, tol, max_iter)
+        reg_covar, tol, max_iter = ops.gmm_check_fit_args(who, reg_covar, tol, max_iter)
         if labels is not None:
             labels = torch.as_tensor(labels).detach().cpu()
             if labels.is_floating_point() or labels.dtype == torch.bool or labels.dim() not in (1, 2):
@@ -1012,7 +1012,7 @@ class EvaluationMixin:
             for batch in fit_batches:
                 rows = torch.cat([feat(m, batch[m]["data"]) for m in mods], dim=1)
                 if state is None:
-                    widths = ops._cca_widths(who, [dims[m] for m in mods], rows.shape[1])
+                    widths = ops.cca_check_widths(who, [dims[m] for m in mods], rows.shape[1])
                     if k > min(widths):
                         raise ValueError(f"{who}: k = {k} joint dimensions, the narrowest view has {min(widths)} features")
                     state = ops.frechet_state(rows.shape[1], rows.device)

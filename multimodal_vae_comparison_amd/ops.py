@@ -1,4 +1,9 @@
-"""torch.autograd.Function wrappers around the C-ABI kernels (host plumbing only).
+"""The training path: torch.autograd.Function wrappers around the C-ABI kernels, the optimiser calls, noise and the input
+expanders (host plumbing only) -- and the one public namespace of every kernel wrapper.
+
+The forward-only evaluation metrics live in the package `metrics`, one module per kernel file (metrics/loglik.py wraps
+csrc/loglik.hip, and so on); the block at the end of this file imports their public names, so callers, the documents and
+the tests say `ops.<name>` for a metric as for a layer.  The C call itself (`H.call`) and its counter belong to hipops.
 
 Conventions used by every layer op
 ----------------------------------
@@ -11,11 +16,8 @@ Conventions used by every layer op
 """
 import bisect
 import ctypes
-import itertools
-import math
 import os
 
-import numpy as np
 import torch
 from torch.autograd import Function
 
@@ -24,13 +26,7 @@ from . import hipops as H
 _DACT = {H.ACT_NONE: H.EP_NONE, H.ACT_SILU: H.EP_MUL_SILU_GRAD, H.ACT_RELU: H.EP_MUL_RELU_MASK,
          H.ACT_GELU: H.EP_MUL_GELU_GRAD}
 
-
-CALLS = [0]      # C-ABI calls issued so far (trainer.capture reports how many one captured step holds)
-
-
-def _call(name, *args):
-    CALLS[0] += 1
-    H.check(getattr(H.lib(), name)(*args), name)
+CALLS = H.CALLS      # (the counter of H.call: the same list)
 
 
 class GradReducer:
@@ -267,7 +263,7 @@ class GradReducer:
         for j, (dy, x, dw, db, M, N, K, x_act) in zip(arr, jobs):
             j.dy, j.x, j.dw, j.db, j.ws = H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), None
             j.M, j.N, j.K, j.ldx, j.x_act, j.accumulate = M, N, K, K, x_act, H.ACC_DEFER
-        _call("mmvae_linear_bwd_weight_batch", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
+        H.call("mmvae_linear_bwd_weight_batch", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
 
     # cw_jobs: weight gradients of Dec_CNN's two large ConvTranspose2d layers (32 -> 3 on the 32 x 32 map, 32 -> 32 on the
     # 16 x 16 one) whose backward only launched the data gradient (_convT_k4s2_bwd): (x, dy, dw, db, ws, (B, Cin, Cout, Hin),
@@ -325,7 +321,7 @@ class GradReducer:
         for j, (x, dy, dw, db, ws, (B, Cin, Cout, Hin), x_act) in zip(arr, jobs):
             j.x, j.dy, j.ws = H.ptr(x), H.ptr(dy), H.ptr(ws)
             j.B, j.Cin, j.Cout, j.Hin, j.x_act, j.has_bias = B, Cin, Cout, Hin, x_act, int(db is not None)
-        _call("mmvae_conv_wgrad_batch", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
+        H.call("mmvae_conv_wgrad_batch", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
 
     # tw_jobs: {stream: [(dy2, x2, w, b, gw, gb)]} -- weight gradients of TALL-SKINNY Linear layers (the action towers'
     # attention projections: 12 800 rows, 32 .. 96 columns) whose backward only launched the data gradient.  Eight of them
@@ -435,11 +431,11 @@ class GradReducer:
             if tail is not None and i + H.MAX_SEGMENTS >= len(segs):
                 # the logged loss values ride on the last fold launch as one extra workgroup
                 rp, flat, out, n, B, k = tail["args"]
-                _call("mmvae_reduce_segments_lincomb", ctypes.byref(t), ctypes.byref(rp), flat, H.ptr(out), n, B, k,
-                      H.stream())
+                H.call("mmvae_reduce_segments_lincomb", ctypes.byref(t), ctypes.byref(rp), flat, H.ptr(out), n, B, k,
+                       H.stream())
                 tail["done"] = True
             else:
-                _call("mmvae_reduce_segments", ctypes.byref(t), H.stream())
+                H.call("mmvae_reduce_segments", ctypes.byref(t), H.stream())
         if st["spill"]:        # the step did not fit one chunk: one arena of the full size from the next step on
             st["spill"], st["spilled"] = [], 0
             if not torch.cuda.is_current_stream_capturing():
@@ -461,7 +457,7 @@ class Marks:
         if name not in cls.names:
             cls.names.append(name)
         i = cls.names.index(name)
-        _call("mmvae_debug_timestamp", cls.buf.data_ptr() + 8 * i, H.stream())
+        H.call("mmvae_debug_timestamp", cls.buf.data_ptr() + 8 * i, H.stream())
 
 
 class Mark(Function):
@@ -560,18 +556,18 @@ def _dp(drop, n=0):
 
 
 def dropout_advance(state, slot):
-    _call("mmvae_dropout_advance", H.ptr(state), int(slot), H.stream())
+    H.call("mmvae_dropout_advance", H.ptr(state), int(slot), H.stream())
 
 
 def dropout_advance_many(states):
     """dropout_advance(st, 0) for every state tensor in `states` (distinct towers) in one launch"""
     arr = (ctypes.c_void_p * len(states))(*[H.ptr(t) for t in states])
-    _call("mmvae_dropout_advance_many", ctypes.cast(arr, ctypes.c_void_p), len(states), H.stream())
+    H.call("mmvae_dropout_advance_many", ctypes.cast(arr, ctypes.c_void_p), len(states), H.stream())
 
 
 def dropout_mask(drop, n):
     out = torch.empty(n, device=drop.state.device)
-    _call("mmvae_dropout_mask", drop.c(), H.ptr(out), n, H.stream())
+    H.call("mmvae_dropout_mask", drop.c(), H.ptr(out), n, H.stream())
     return out
 
 
@@ -607,8 +603,8 @@ class Conv2dK4S2(Function):
         B, Cin, Hin, _ = x.shape
         Cout = w.shape[0]
         y = torch.empty(B, Cout, Hin // 2, Hin // 2, device=x.device, dtype=torch.float32)
-        _call("mmvae_conv2d_k4s2_fwd", H.ptr(x), H.ptr(w), H.ptr(b), None, H.ptr(y), B, Cin, Cout, Hin, in_act,
-              H.EP_NONE, H.stream())
+        H.call("mmvae_conv2d_k4s2_fwd", H.ptr(x), H.ptr(w), H.ptr(b), None, H.ptr(y), B, Cin, Cout, Hin, in_act,
+               H.EP_NONE, H.stream())
         ctx.save_for_backward(x, w)
         ctx.cfg = (in_act, gw, gb, b is not None)
         return y
@@ -628,11 +624,11 @@ class Conv2dK4S2(Function):
         dx = None
         if ctx.needs_input_grad[0]:       # input- and weight-gradient workgroups in ONE launch
             dx = torch.empty_like(x)
-            _call("mmvae_conv2d_k4s2_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
-                  B, Cin, Cout, Hout, in_act, acc, H.stream())
+            H.call("mmvae_conv2d_k4s2_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
+                   B, Cin, Cout, Hout, in_act, acc, H.stream())
         else:
-            _call("mmvae_conv2d_k4s2_wgrad", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), B, Cin, Cout, Hout,
-                  in_act, acc, H.stream())
+            H.call("mmvae_conv2d_k4s2_wgrad", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), B, Cin, Cout, Hout,
+                   in_act, acc, H.stream())
         if defer:
             _conv_segments(ws, dw, db, B, Cout, Cin, Hout, Cout)
         return dx, ret_w, ret_b, None, None, None
@@ -649,8 +645,8 @@ class ConvT2dK4S2(Function):
         B, Cin, Hin, _ = x.shape
         Cout = w.shape[1]
         y = torch.empty(B, Cout, 2 * Hin, 2 * Hin, device=x.device, dtype=torch.float32)
-        _call("mmvae_convT2d_k4s2_fwd", H.ptr(x), H.ptr(w), H.ptr(b), None, H.ptr(y), B, Cin, Cout, Hin, in_act,
-              out_ep, H.stream())
+        H.call("mmvae_convT2d_k4s2_fwd", H.ptr(x), H.ptr(w), H.ptr(b), None, H.ptr(y), B, Cin, Cout, Hin, in_act,
+               out_ep, H.stream())
         if not ep_bwd:
             out_ep = H.EP_NONE
         ctx.save_for_backward(x, w, y if out_ep in (H.EP_SIGMOID_CLAMP, H.EP_SIGMOID) else None)
@@ -666,11 +662,11 @@ class ConvT2dK4S2(Function):
         Cout = w.shape[1]
         if out_ep == H.EP_SIGMOID_CLAMP:
             dl = torch.empty_like(dy)
-            _call("mmvae_sigmoid_clamp_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
+            H.call("mmvae_sigmoid_clamp_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
             dy = dl
         elif out_ep == H.EP_SIGMOID:
             dl = torch.empty_like(dy)
-            _call("mmvae_sigmoid_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
+            H.call("mmvae_sigmoid_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
             dy = dl
         dx, ret_w, ret_b = _convT_k4s2_bwd(x, w, dy, in_act, gw, gb, has_b, ctx.needs_input_grad[0])
         return dx, ret_w, ret_b, None, None, None, None, None
@@ -693,17 +689,17 @@ def _convT_k4s2_bwd(x, w, dy, in_act, gw, gb, has_b, need_dx):
         dx = torch.empty_like(x)
         go = GradReducer.cw_park((x, dy, dw, db, ws, (B, Cin, Cout, Hin), in_act))
         ep = _DACT[in_act]
-        _call("mmvae_convT2d_k4s2_dgrad", H.ptr(dy), H.ptr(w), H.ptr(x) if ep else None, H.ptr(dx), B, Cin, Cout, Hin, ep,
-              H.stream())
+        H.call("mmvae_convT2d_k4s2_dgrad", H.ptr(dy), H.ptr(w), H.ptr(x) if ep else None, H.ptr(dx), B, Cin, Cout, Hin, ep,
+               H.stream())
         if go is not None:
             go()
     elif need_dx:       # input- and weight-gradient workgroups in ONE launch
         dx = torch.empty_like(x)
-        _call("mmvae_convT2d_k4s2_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
-              B, Cin, Cout, Hin, in_act, acc, H.stream())
+        H.call("mmvae_convT2d_k4s2_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
+               B, Cin, Cout, Hin, in_act, acc, H.stream())
     else:
-        _call("mmvae_convT2d_k4s2_wgrad", H.ptr(x), H.ptr(dy), H.ptr(dw), H.ptr(db), H.ptr(ws), B, Cin, Cout, Hin,
-              in_act, acc, H.stream())
+        H.call("mmvae_convT2d_k4s2_wgrad", H.ptr(x), H.ptr(dy), H.ptr(dw), H.ptr(db), H.ptr(ws), B, Cin, Cout, Hin,
+               in_act, acc, H.stream())
     if defer:
         _conv_segments(ws, dw, db, B, Cin, Cout, Hin, Cout)
     return dx, ret_w, ret_b
@@ -740,8 +736,8 @@ class ConvT3Bce(Function):
                     "ConvT3Bce: first call at this batch size inside a graph capture (run one eager warm-up step first)"
                 ent = _T3_SCRATCH[key] = (torch.zeros(B * S, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
             part, tick = ent
-        _call("mmvae_convT3_bce_seeded", H.ptr(x), H.ptr(w), H.ptr(b), H.ptr(target), H.ptr(row), H.ptr(dl), H.ptr(part),
-              H.ptr(tick), B, in_act, cs.value, H.stream())
+        H.call("mmvae_convT3_bce_seeded", H.ptr(x), H.ptr(w), H.ptr(b), H.ptr(target), H.ptr(row), H.ptr(dl), H.ptr(part),
+               H.ptr(tick), B, in_act, cs.value, H.stream())
         ctx.save_for_backward(x, w, dl)
         ctx.cfg = (in_act, gw, gb, b is not None, cs.seed.data_ptr(), cs.value)
         return row
@@ -788,7 +784,7 @@ class SigmoidClampOut(Function):
         (y,) = ctx.saved_tensors
         dy = H.f32c(dy)
         dl = torch.empty_like(dy)
-        _call("mmvae_sigmoid_clamp_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
+        H.call("mmvae_sigmoid_clamp_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
         return dl
 
 
@@ -828,11 +824,11 @@ class BceSigmoidRowsum(Function):
         ctx.seeded = None
         if cs is not None and y_raw.requires_grad and trows == B:
             dl = torch.empty_like(y_raw)
-            _call("mmvae_bce_rowsum_seeded", H.ptr(y_raw), H.ptr(target), H.ptr(row), cs.value, H.ptr(dl), B, F_,
-                  H.stream())
+            H.call("mmvae_bce_rowsum_seeded", H.ptr(y_raw), H.ptr(target), H.ptr(row), cs.value, H.ptr(dl), B, F_,
+                   H.stream())
             ctx.seeded = (cs.seed.data_ptr(), dl)
         else:
-            _call("mmvae_bce_rowsum_fwd", H.ptr(y_raw), H.ptr(target), H.ptr(row), B, F_, trows, H.stream())
+            H.call("mmvae_bce_rowsum_fwd", H.ptr(y_raw), H.ptr(target), H.ptr(row), B, F_, trows, H.stream())
         ctx.save_for_backward(y_raw, target)
         ctx.trows = trows
         return row
@@ -844,8 +840,8 @@ class BceSigmoidRowsum(Function):
         y, target = ctx.saved_tensors
         B = y.shape[0]
         dl = torch.empty_like(y)
-        _call("mmvae_bce_sigmoid_clamp_bwd", H.ptr(y), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(dl), B, y.numel() // B,
-              ctx.trows, H.stream())
+        H.call("mmvae_bce_sigmoid_clamp_bwd", H.ptr(y), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(dl), B, y.numel() // B,
+               ctx.trows, H.stream())
         return dl, None
 
 
@@ -865,8 +861,8 @@ class ConvGeneric(Function):
             Cout = w.shape[0]
             Ho, Wo = (Hin + 2 * pad - K) // stride + 1, (Win + 2 * pad - K) // stride + 1
         y = torch.empty(B, Cout, Ho, Wo, device=x.device)
-        _call("mmvae_convT2d_generic_fwd" if transposed else "mmvae_conv2d_generic_fwd", H.ptr(x), H.ptr(w), H.ptr(b),
-              None, H.ptr(y), B, Cin, Cout, Hin, Win, K, stride, pad, in_act, out_ep, H.stream())
+        H.call("mmvae_convT2d_generic_fwd" if transposed else "mmvae_conv2d_generic_fwd", H.ptr(x), H.ptr(w), H.ptr(b),
+               None, H.ptr(y), B, Cin, Cout, Hin, Win, K, stride, pad, in_act, out_ep, H.stream())
         ctx.save_for_backward(x, w, y if out_ep in (H.EP_SIGMOID_CLAMP, H.EP_SIGMOID) else None)
         ctx.cfg = (transposed, stride, pad, in_act, out_ep, gw, gb, b is not None, Cout)
         return y
@@ -880,19 +876,19 @@ class ConvGeneric(Function):
         K = w.shape[-1]
         if out_ep in (H.EP_SIGMOID_CLAMP, H.EP_SIGMOID):
             dl = torch.empty_like(dy)
-            _call("mmvae_sigmoid_clamp_bwd" if out_ep == H.EP_SIGMOID_CLAMP else "mmvae_sigmoid_bwd", H.ptr(dy), H.ptr(y),
-                  H.ptr(dl), dy.numel(), H.stream())
+            H.call("mmvae_sigmoid_clamp_bwd" if out_ep == H.EP_SIGMOID_CLAMP else "mmvae_sigmoid_bwd", H.ptr(dy), H.ptr(y),
+                   H.ptr(dl), dy.numel(), H.stream())
             dy = dl
         dw, db, acc_w, ret_w, ret_b = _grad_dst(w, gw, gb, has_b, Cout)
         pre = "mmvae_convT2d_generic" if transposed else "mmvae_conv2d_generic"
-        _call(pre + "_wgrad", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), B, Cin, Cout, Hin, Win, K, stride, pad, in_act,
-              acc_w, H.stream())
+        H.call(pre + "_wgrad", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), B, Cin, Cout, Hin, Win, K, stride, pad, in_act,
+               acc_w, H.stream())
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             ep = _DACT[in_act]
-            _call(pre + "_dgrad", H.ptr(dy), H.ptr(w), H.ptr(x) if ep else None, H.ptr(dx), B, Cin, Cout, Hin, Win, K,
-                  stride, pad, ep, H.stream())
+            H.call(pre + "_dgrad", H.ptr(dy), H.ptr(w), H.ptr(x) if ep else None, H.ptr(dx), B, Cin, Cout, Hin, Win, K,
+                   stride, pad, ep, H.stream())
         return dx, ret_w, ret_b, None, None, None, None, None, None, None
 
 
@@ -1028,7 +1024,7 @@ class Linear(Function):
         N = w.shape[0]
         y = torch.empty(*x.shape[:-1], N, device=x.device, dtype=torch.float32)
         if not lazy:
-            _call("mmvae_linear_fwd", H.ptr(x), H.ptr(w), H.ptr(b), None, H.ptr(y), M, N, K, K, in_act, out_ep, H.stream())
+            H.call("mmvae_linear_fwd", H.ptr(x), H.ptr(w), H.ptr(b), None, H.ptr(y), M, N, K, K, in_act, out_ep, H.stream())
         ctx.save_for_backward(x, w)
         ctx.cfg = (in_act, gw, gb, b is not None)
         return y
@@ -1061,7 +1057,7 @@ class Linear(Function):
         if need_dx and defer and radd is None and GradReducer.tw_ok(M, N, K, in_act, has_b, dy, x):
             # tall-skinny layer: the data gradient now, the weight gradient with up to seven others in one launch of the
             # tall-skinny kernel (GradReducer.tw_park)
-            _call("mmvae_linear_bwd_data", H.ptr(dy), H.ptr(w), aux, H.ptr(dx), M, N, K, ep, 0, H.stream())
+            H.call("mmvae_linear_bwd_data", H.ptr(dy), H.ptr(w), aux, H.ptr(dx), M, N, K, ep, 0, H.stream())
             GradReducer.tw_park((dy.view(M, N), x.view(M, K), w, True, gw, gb))
             del kadd
             return dx, ret_w, ret_b, None, None, None, None, None, None
@@ -1070,7 +1066,7 @@ class Linear(Function):
             # the captured one-GPU MoPoE step, a Linear of the decoder that shares the fusion's stream: only the DATA
             # gradient sits on the critical chain decoder -> fusion -> encoders; the weight gradients of all such layers
             # follow in ONE launch behind the fusion's backward (GradReducer.flush_dw)
-            _call("mmvae_linear_bwd_data", H.ptr(dy), H.ptr(w), aux, H.ptr(dx), M, N, K, ep, 0, H.stream())
+            H.call("mmvae_linear_bwd_data", H.ptr(dy), H.ptr(w), aux, H.ptr(dx), M, N, K, ep, 0, H.stream())
             GradReducer.dw_jobs.append((dy, x, dw, db, M, N, K, in_act))
             del kadd
             return dx, ret_w, ret_b, None, None, None, None, None, None
@@ -1082,12 +1078,12 @@ class Linear(Function):
         direct = (gw, gb) if (gw is not None and not (defer and nz > 1)) else ()      # accumulated in place by the launch
         if need_dx:   # data and weight gradients in ONE grouped launch
             GradReducer.writes(x.device, *direct)
-            _call("mmvae_linear_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), aux, H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
-                  M, N, K, K, in_act, ep, acc, H.stream())
+            H.call("mmvae_linear_bwd", H.ptr(dy), H.ptr(x), H.ptr(w), aux, H.ptr(dx), H.ptr(dw), H.ptr(db), H.ptr(ws),
+                   M, N, K, K, in_act, ep, acc, H.stream())
         else:
             GradReducer.writes(x.device, *direct)
-            _call("mmvae_linear_bwd_weight", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), M, N, K, K, in_act, acc,
-                  H.stream())
+            H.call("mmvae_linear_bwd_weight", H.ptr(dy), H.ptr(x), H.ptr(dw), H.ptr(db), H.ptr(ws), M, N, K, K, in_act, acc,
+                   H.stream())
         if defer and nz > 1:
             GradReducer.add(ws.data_ptr(), dw, nz, N * K, N * K)
             if db is not None:
@@ -1124,7 +1120,7 @@ class SigmoidOut(Function):
         (y,) = ctx.saved_tensors
         dy = H.f32c(dy)
         dl = torch.empty_like(dy)
-        _call("mmvae_sigmoid_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
+        H.call("mmvae_sigmoid_bwd", H.ptr(dy), H.ptr(y), H.ptr(dl), dy.numel(), H.stream())
         return dl
 
 
@@ -1145,10 +1141,10 @@ class LinearKN(Function):
         G = w.shape[2] * w.shape[3]
         N = C * G
         y = torch.empty(M, N, device=x.device)
-        _call("mmvae_gemm_f32", H.ptr(x), H.ptr(w), None, None, H.ptr(y), None, None, M, N, K, K, 1, N, 1, N, in_act,
-              H.ACT_NONE, H.EP_NONE, 0, 1, H.stream())
+        H.call("mmvae_gemm_f32", H.ptr(x), H.ptr(w), None, None, H.ptr(y), None, None, M, N, K, K, 1, N, 1, N, in_act,
+               H.ACT_NONE, H.EP_NONE, 0, 1, H.stream())
         if b is not None:
-            _call("mmvae_bias_group_add", H.ptr(y), H.ptr(b), M, C, G, H.stream())
+            H.call("mmvae_bias_group_add", H.ptr(y), H.ptr(b), M, C, G, H.stream())
         ctx.save_for_backward(x, w)
         ctx.cfg = (in_act, gw, gb, b is not None, C, G)
         return y
@@ -1165,8 +1161,8 @@ class LinearKN(Function):
         if ctx.needs_input_grad[0]:       # dx[m, k] = ep( sum_n dy[m, n] w[k, n] )
             dx = torch.empty_like(x)
             ep = _DACT[in_act]
-            _call("mmvae_gemm_f32", H.ptr(dy), H.ptr(w), None, H.ptr(x) if ep else None, H.ptr(dx), None, None, M, K, N,
-                  N, 1, 1, N, K, H.ACT_NONE, H.ACT_NONE, ep, 0, 1, H.stream())
+            H.call("mmvae_gemm_f32", H.ptr(dy), H.ptr(w), None, H.ptr(x) if ep else None, H.ptr(dx), None, None, M, K, N,
+                   N, 1, 1, N, K, H.ACT_NONE, H.ACT_NONE, ep, 0, 1, H.stream())
         # dw[k, n] (+)= sum_m act(x)[m, k] dy[m, n]: rows K, columns N, reduction over the M samples (split)
         dw, acc_w, ret_w = _new_like_param(w, gw)
         tiles = ((K + 31) // 32) * ((N + 31) // 32)
@@ -1181,8 +1177,8 @@ class LinearKN(Function):
             ws = GradReducer.alloc(nws, x.device) if defer else H.workspace(nws, x.device)
         if gw is not None and not defer:
             GradReducer.writes(x.device, gw)
-        _call("mmvae_gemm_f32", H.ptr(x), H.ptr(dy), None, None, H.ptr(dw), None, H.ptr(ws), K, N, M, 1, K, N, 1, N,
-              in_act, H.ACT_NONE, H.EP_NONE, H.ACC_DEFER if defer else acc_w, want, H.stream())
+        H.call("mmvae_gemm_f32", H.ptr(x), H.ptr(dy), None, None, H.ptr(dw), None, H.ptr(ws), K, N, M, 1, K, N, 1, N,
+               in_act, H.ACT_NONE, H.EP_NONE, H.ACC_DEFER if defer else acc_w, want, H.stream())
         if defer:
             GradReducer.add(ws.data_ptr(), dw, nz, K * N, K * N)
         ret_b = None
@@ -1190,16 +1186,16 @@ class LinearKN(Function):
             nbw = lib.mmvae_bias_group_ws_floats(M, C)
             if _defer(gb):
                 bws = GradReducer.alloc(nbw, x.device)
-                _call("mmvae_bias_group_grad", H.ptr(dy), H.ptr(gb), H.ptr(bws), M, C, G, H.ACC_DEFER, H.stream())
+                H.call("mmvae_bias_group_grad", H.ptr(dy), H.ptr(gb), H.ptr(bws), M, C, G, H.ACC_DEFER, H.stream())
                 GradReducer.add(bws.data_ptr(), gb, lib.mmvae_bias_group_parts(M), C, C)
             elif gb is not None:
                 bws = torch.empty(nbw, device=x.device)
                 GradReducer.writes(x.device, gb)
-                _call("mmvae_bias_group_grad", H.ptr(dy), H.ptr(gb), H.ptr(bws), M, C, G, 1, H.stream())
+                H.call("mmvae_bias_group_grad", H.ptr(dy), H.ptr(gb), H.ptr(bws), M, C, G, 1, H.stream())
             else:
                 ret_b = torch.empty(C, device=x.device)
                 bws = torch.empty(nbw, device=x.device)
-                _call("mmvae_bias_group_grad", H.ptr(dy), H.ptr(ret_b), H.ptr(bws), M, C, G, 0, H.stream())
+                H.call("mmvae_bias_group_grad", H.ptr(dy), H.ptr(ret_b), H.ptr(bws), M, C, G, 0, H.stream())
         return dx, ret_w, ret_b, None, None, None
 
 
@@ -1214,7 +1210,7 @@ class AvgPoolGlobal(Function):
         x = H.f32c(x)
         C = x.shape[-1]
         y = torch.empty(B, C, device=x.device)
-        _call("mmvae_avgpool_fwd", H.ptr(x), H.ptr(y), B, HW, C, in_act, H.stream())
+        H.call("mmvae_avgpool_fwd", H.ptr(x), H.ptr(y), B, HW, C, in_act, H.stream())
         ctx.save_for_backward(x)
         ctx.cfg = (B, HW, C, in_act)
         return y
@@ -1224,7 +1220,7 @@ class AvgPoolGlobal(Function):
         (x,) = ctx.saved_tensors
         B, HW, C, in_act = ctx.cfg
         dx = torch.empty_like(x)
-        _call("mmvae_avgpool_bwd", H.ptr(H.f32c(dy)), H.ptr(x), H.ptr(dx), B, HW, C, in_act, H.stream())
+        H.call("mmvae_avgpool_bwd", H.ptr(H.f32c(dy)), H.ptr(x), H.ptr(dx), B, HW, C, in_act, H.stream())
         return dx, None, None, None
 
 
@@ -1235,7 +1231,7 @@ class HeadSoftmax(Function):
     def forward(ctx, h):
         assert h.is_contiguous() and h.dtype == torch.float32
         B, D2 = h.shape
-        _call("mmvae_head_softmax_fwd", H.ptr(h), B, D2 // 2, H.stream())   # in place on the fresh linear output
+        H.call("mmvae_head_softmax_fwd", H.ptr(h), B, D2 // 2, H.stream())   # in place on the fresh linear output
         ctx.mark_dirty(h)
         ctx.save_for_backward(h)
         return h
@@ -1246,7 +1242,7 @@ class HeadSoftmax(Function):
         # h feeds nothing but this op, so the incoming gradient buffer is exclusively ours: transform it in place
         dh = H.f32c(dh)
         B, D2 = out.shape
-        _call("mmvae_head_softmax_bwd", H.ptr(out), H.ptr(dh), B, D2 // 2, H.stream())
+        H.call("mmvae_head_softmax_bwd", H.ptr(out), H.ptr(dh), B, D2 // 2, H.stream())
         return dh
 
 
@@ -1305,8 +1301,8 @@ class PoeReparamKL(Function):
         for i, t in enumerate(eps):
             a.eps[i] = t.data_ptr()
             a.z[i] = zs[i].data_ptr()
-        _call("mmvae_poe_reparam_kl_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(joint), H.ptr(kl), E, int(with_prior),
-              n_z, kl_mask, B, D, D2, int(bool(raw)), H.ptr(rng), H.stream())
+        H.call("mmvae_poe_reparam_kl_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(joint), H.ptr(kl), E, int(with_prior),
+               n_z, kl_mask, B, D, D2, int(bool(raw)), H.ptr(rng), H.stream())
         if cols is not None and not raw and GradReducer.share_packed_grads:
             for e, t in enumerate(packed):      # (backward: one gradient tensor per head output, handed over by its last reader)
                 if ctx.needs_input_grad[9 + e]:
@@ -1373,9 +1369,9 @@ class PoeReparamKL(Function):
             dth = ret = torch.empty_like(theta)
             acc = 0
         ws = H.workspace(H.lib().mmvae_poe_ws_floats(B, D), dev)
-        _call("mmvae_poe_reparam_kl_bwd_acc", ctypes.byref(a), H.ptr(theta), H.ptr(dkl), H.ptr(dth), H.ptr(ws),
-              _poe_ticket(dev), E,
-              int(with_prior), n_z if dz is not None else 0, kl_mask, B, D, 2 * Dtot, raw, acc, acc_packed, H.stream())
+        H.call("mmvae_poe_reparam_kl_bwd_acc", ctypes.byref(a), H.ptr(theta), H.ptr(dkl), H.ptr(dth), H.ptr(ws),
+               _poe_ticket(dev), E,
+               int(with_prior), n_z if dz is not None else 0, kl_mask, B, D, 2 * Dtot, raw, acc, acc_packed, H.stream())
         return (ret, None, None, None, None, None, None, None, None, *(dpacked if ret_packed is None else ret_packed),
                 *([None] * ctx.n_eps_in))
 
@@ -1401,8 +1397,8 @@ class TcFusion(Function):
         for e, p in enumerate(packed[:H.MAX_EXPERTS]):
             a.mu[e] = p.data_ptr()
             a.lv[e] = p.data_ptr() + 4 * D
-        _call("mmvae_tc_fusion_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(joint), H.ptr(kl), H.ptr(z), E, B, D,
-              D2, int(bool(raw)), H.stream())
+        H.call("mmvae_tc_fusion_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(joint), H.ptr(kl), H.ptr(z), E, B, D,
+               D2, int(bool(raw)), H.stream())
         ctx.save_for_backward(theta, eps, *packed)
         ctx.cfg = (gtheta, E, B, D, int(bool(raw)))
         ctx.mark_non_differentiable(joint)
@@ -1434,8 +1430,8 @@ class TcFusion(Function):
         else:
             dth, acc, ret = None, 0, None
         ws = H.workspace(H.lib().mmvae_tc_fusion_ws_floats(B, D), dev)
-        _call("mmvae_tc_fusion_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(dz), H.ptr(dkl), H.ptr(dth),
-              H.ptr(ws), E, B, D, 2 * D, raw, acc, H.stream())
+        H.call("mmvae_tc_fusion_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(dz), H.ptr(dkl), H.ptr(dth),
+               H.ptr(ws), E, B, D, 2 * D, raw, acc, H.stream())
         return (ret, None, None, None, *dpacked)
 
 
@@ -1477,7 +1473,7 @@ class RowsFan(Function):
                 t.width[k], t.ld_src[k], t.ld_dst[k] = w, w, W
                 k += 1
         t.n, t.B = k, B
-        _call("mmvae_rows_fan_fwd", ctypes.byref(t), H.stream())
+        H.call("mmvae_rows_fan_fwd", ctypes.byref(t), H.stream())
         ctx.plan, ctx.B, ctx.widths = plan, B, [t_.shape[1] for t_ in srcs]
         ctx.set_materialize_grads(False)
         return tuple(outs)
@@ -1504,7 +1500,7 @@ class RowsFan(Function):
                 t.n_g[s_] = j + 1
         t.n, t.B = n, B
         if n:
-            _call("mmvae_rows_fan_bwd", ctypes.byref(t), H.stream())
+            H.call("mmvae_rows_fan_bwd", ctypes.byref(t), H.stream())
         return (None, *outs)
 
 
@@ -1622,7 +1618,7 @@ class BceRowsum(Function):
         B = x_hat.shape[0]
         F = x_hat.numel() // B
         row = torch.empty(B, device=x_hat.device)
-        _call("mmvae_bce_rowsum_fwd", H.ptr(x_hat), H.ptr(target), H.ptr(row), B, F, B, H.stream())
+        H.call("mmvae_bce_rowsum_fwd", H.ptr(x_hat), H.ptr(target), H.ptr(row), B, F, B, H.stream())
         ctx.save_for_backward(x_hat, target)
         return row
 
@@ -1632,7 +1628,7 @@ class BceRowsum(Function):
         B = x_hat.shape[0]
         F = x_hat.numel() // B
         dx = torch.empty_like(x_hat)
-        _call("mmvae_bce_rowsum_bwd", H.ptr(x_hat), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(dx), B, F, H.stream())
+        H.call("mmvae_bce_rowsum_bwd", H.ptr(x_hat), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(dx), B, F, H.stream())
         return dx, None
 
 
@@ -1643,7 +1639,7 @@ class BceElem(Function):
     def forward(ctx, x_hat, target):
         x_hat, target = H.f32c(x_hat), H.f32c(target)
         out = torch.empty_like(x_hat)
-        _call("mmvae_bce_elem_fwd", H.ptr(x_hat), H.ptr(target), H.ptr(out), x_hat.numel(), H.stream())
+        H.call("mmvae_bce_elem_fwd", H.ptr(x_hat), H.ptr(target), H.ptr(out), x_hat.numel(), H.stream())
         ctx.save_for_backward(x_hat, target)
         return out
 
@@ -1672,8 +1668,8 @@ class LprobRowsum(Function):
         assert B * F_ == loc.numel() and B % trows == 0
         row = torch.empty(B, device=loc.device)
         sc = -1.0 if scale is None else float(scale)
-        _call("mmvae_lprob_rowsum_fwd", H.ptr(loc), H.ptr(target), H.ptr(row), B, F_, trows, sc, lap, lap_rows,
-              int(perm_c), H.stream())
+        H.call("mmvae_lprob_rowsum_fwd", H.ptr(loc), H.ptr(target), H.ptr(row), B, F_, trows, sc, lap, lap_rows,
+               int(perm_c), H.stream())
         ctx.save_for_backward(loc, target)
         ctx.cfg = (sc, lap, lap_rows, B, F_, trows, int(perm_c), int(bool(logit_grad)))
         return row
@@ -1683,8 +1679,8 @@ class LprobRowsum(Function):
         loc, target = ctx.saved_tensors
         sc, lap, lap_rows, B, F_, trows, perm_c, logit_grad = ctx.cfg
         d = torch.empty_like(loc)
-        _call("mmvae_lprob_rowsum_bwd", H.ptr(loc), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(d), B, F_, trows, sc, lap,
-              lap_rows, perm_c, logit_grad, H.stream())
+        H.call("mmvae_lprob_rowsum_bwd", H.ptr(loc), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(d), B, F_, trows, sc, lap,
+               lap_rows, perm_c, logit_grad, H.stream())
         return d, None, None, None, None, None
 
 
@@ -1699,8 +1695,8 @@ class OptimalSigmaRowsum(Function):
         row = torch.empty(B, device=loc.device)
         stats = torch.empty(4, device=loc.device)
         ws = torch.empty(H.lib().mmvae_optimal_sigma_ws_floats(B, F_), device=loc.device)
-        _call("mmvae_optimal_sigma_fwd", H.ptr(loc), H.ptr(target), H.ptr(row), H.ptr(stats), H.ptr(ws), B, F_,
-              H.stream())
+        H.call("mmvae_optimal_sigma_fwd", H.ptr(loc), H.ptr(target), H.ptr(row), H.ptr(stats), H.ptr(ws), B, F_,
+               H.stream())
         ctx.save_for_backward(loc, target, stats)
         return row
 
@@ -1709,8 +1705,8 @@ class OptimalSigmaRowsum(Function):
         loc, target, stats = ctx.saved_tensors
         B = loc.shape[0]
         d = torch.empty_like(loc)
-        _call("mmvae_optimal_sigma_bwd", H.ptr(loc), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(stats), H.ptr(d), B,
-              loc.numel() // B, H.stream())
+        H.call("mmvae_optimal_sigma_bwd", H.ptr(loc), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(stats), H.ptr(d), B,
+               loc.numel() // B, H.stream())
         return d, None
 
 
@@ -1723,8 +1719,8 @@ class LprobElem(Function):
         loc, target = H.f32c(loc), H.f32c(target)
         out = torch.empty(loc.shape, dtype=torch.float64, device=loc.device)
         sc = -1.0 if scale is None else float(scale)
-        _call("mmvae_lprob_elem_fwd", H.ptr(loc), H.ptr(target), H.ptr(out), loc.numel(), target.numel(), sc,
-              int(bool(laplace)), H.stream())
+        H.call("mmvae_lprob_elem_fwd", H.ptr(loc), H.ptr(target), H.ptr(out), loc.numel(), target.numel(), sc,
+               int(bool(laplace)), H.stream())
         ctx.save_for_backward(loc, target)
         ctx.cfg = (sc, int(bool(laplace)))
         return out
@@ -1734,8 +1730,8 @@ class LprobElem(Function):
         loc, target = ctx.saved_tensors
         g = g.to(torch.float64).contiguous()
         d = torch.empty_like(loc)
-        _call("mmvae_lprob_elem_bwd", H.ptr(loc), H.ptr(target), H.ptr(g), H.ptr(d), loc.numel(), target.numel(),
-              ctx.cfg[0], ctx.cfg[1], H.stream())
+        H.call("mmvae_lprob_elem_bwd", H.ptr(loc), H.ptr(target), H.ptr(g), H.ptr(d), loc.numel(), target.numel(),
+               ctx.cfg[0], ctx.cfg[1], H.stream())
         return d, None, None, None
 
 
@@ -1749,8 +1745,8 @@ class OptimalSigmaElem(Function):
         out = torch.empty_like(loc)
         stats = torch.empty(4, device=loc.device)
         ws = torch.empty(H.lib().mmvae_optimal_sigma_ws_floats(1, n), device=loc.device)
-        _call("mmvae_optimal_sigma_elem_fwd", H.ptr(loc), H.ptr(target), H.ptr(out), H.ptr(stats), H.ptr(ws), n,
-              H.stream())
+        H.call("mmvae_optimal_sigma_elem_fwd", H.ptr(loc), H.ptr(target), H.ptr(out), H.ptr(stats), H.ptr(ws), n,
+               H.stream())
         ctx.save_for_backward(loc, target, stats)
         return out
 
@@ -1760,8 +1756,8 @@ class OptimalSigmaElem(Function):
         n = loc.numel()
         d = torch.empty_like(loc)
         ws = torch.empty(H.lib().mmvae_optimal_sigma_ws_floats(1, n), device=loc.device)
-        _call("mmvae_optimal_sigma_elem_bwd", H.ptr(loc), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(stats), H.ptr(ws),
-              H.ptr(d), n, H.stream())
+        H.call("mmvae_optimal_sigma_elem_bwd", H.ptr(loc), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(stats), H.ptr(ws),
+               H.ptr(d), n, H.stream())
         return d, None
 
 
@@ -1780,7 +1776,7 @@ class PointwiseRowsum(Function):
         trows = target.numel() // F_
         assert trows * F_ == target.numel() and B % trows == 0
         row = torch.empty(B, device=x.device)
-        _call("mmvae_pointwise_rowsum_fwd", H.ptr(x), H.ptr(target), H.ptr(row), B, F_, trows, int(kind), H.stream())
+        H.call("mmvae_pointwise_rowsum_fwd", H.ptr(x), H.ptr(target), H.ptr(row), B, F_, trows, int(kind), H.stream())
         ctx.save_for_backward(x, target)
         ctx.cfg = (B, F_, trows, int(kind))
         return row
@@ -1790,8 +1786,8 @@ class PointwiseRowsum(Function):
         x, target = ctx.saved_tensors
         B, F_, trows, kind = ctx.cfg
         d = torch.empty_like(x)
-        _call("mmvae_pointwise_rowsum_bwd", H.ptr(x), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(d), B, F_, trows, kind,
-              H.stream())
+        H.call("mmvae_pointwise_rowsum_bwd", H.ptr(x), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(d), B, F_, trows, kind,
+               H.stream())
         return d, None, None
 
 
@@ -1802,7 +1798,7 @@ class PointwiseElem(Function):
     def forward(ctx, x, target, kind):
         x, target = H.f32c(x), H.f32c(target)
         out = torch.empty_like(x)
-        _call("mmvae_pointwise_elem", H.ptr(x), H.ptr(target), None, H.ptr(out), x.numel(), int(kind), H.stream())
+        H.call("mmvae_pointwise_elem", H.ptr(x), H.ptr(target), None, H.ptr(out), x.numel(), int(kind), H.stream())
         ctx.save_for_backward(x, target)
         ctx.kind = int(kind)
         return out
@@ -1811,8 +1807,8 @@ class PointwiseElem(Function):
     def backward(ctx, g):
         x, target = ctx.saved_tensors
         d = torch.empty_like(x)
-        _call("mmvae_pointwise_elem", H.ptr(x), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(d), x.numel(), ctx.kind,
-              H.stream())
+        H.call("mmvae_pointwise_elem", H.ptr(x), H.ptr(target), H.ptr(H.f32c(g)), H.ptr(d), x.numel(), ctx.kind,
+               H.stream())
         return d, None, None
 
 
@@ -1846,8 +1842,8 @@ class AddPEDropout(Function):
     @staticmethod
     def forward(ctx, x, pe, T, B, D, drop):
         y = torch.empty(T, B, D, device=pe.device)
-        _call("mmvae_add_pe_dropout_fwd", H.ptr(H.f32c(x)) if x is not None else None, H.ptr(pe), H.ptr(y), T, B, D,
-              _dp(drop, y.numel()), H.stream())
+        H.call("mmvae_add_pe_dropout_fwd", H.ptr(H.f32c(x)) if x is not None else None, H.ptr(pe), H.ptr(y), T, B, D,
+               _dp(drop, y.numel()), H.stream())
         ctx.drop = drop
         return y
 
@@ -1857,8 +1853,8 @@ class AddPEDropout(Function):
             return None, None, None, None, None, None
         dy = H.f32c(dy)
         dx = torch.empty_like(dy)
-        _call("mmvae_dropout_act_bwd", H.ptr(dy), H.ptr(dy), H.ptr(dx), dy.numel(), H.ACT_NONE,
-              ctx.drop.c() if ctx.drop is not None else None, H.stream())
+        H.call("mmvae_dropout_act_bwd", H.ptr(dy), H.ptr(dy), H.ptr(dx), dy.numel(), H.ACT_NONE,
+               ctx.drop.c() if ctx.drop is not None else None, H.stream())
         return dx, None, None, None, None, None
 
 
@@ -1889,12 +1885,12 @@ class CeOverTime(Function):
         ctx.trows = trows
         if cs is not None and not per_v and logits.requires_grad and T * V <= CE_TILE and V <= CE_TILE_V and trows == B:
             dl = torch.empty_like(logits)
-            _call("mmvae_ce_over_time_seeded", H.ptr(logits), H.ptr(target), H.ptr(row), cs.value, H.ptr(dl), B, T, V,
-                  H.stream())
+            H.call("mmvae_ce_over_time_seeded", H.ptr(logits), H.ptr(target), H.ptr(row), cs.value, H.ptr(dl), B, T, V,
+                   H.stream())
             ctx.seeded = (cs.seed.data_ptr(), dl)
         else:
-            _call("mmvae_ce_over_time_fwd", H.ptr(logits), H.ptr(target), H.ptr(loss), H.ptr(row), B, T, V, trows,
-                  H.stream())
+            H.call("mmvae_ce_over_time_fwd", H.ptr(logits), H.ptr(target), H.ptr(loss), H.ptr(row), B, T, V, trows,
+                   H.stream())
         ctx.save_for_backward(logits, target)
         ctx.per_v = per_v
         return loss if per_v else row
@@ -1907,8 +1903,8 @@ class CeOverTime(Function):
         B, T, V = logits.shape
         g = H.f32c(g)
         dl = torch.empty_like(logits)
-        _call("mmvae_ce_over_time_bwd", H.ptr(logits), H.ptr(target), H.ptr(g) if ctx.per_v else None,
-              None if ctx.per_v else H.ptr(g), H.ptr(dl), B, T, V, ctx.trows, H.stream())
+        H.call("mmvae_ce_over_time_bwd", H.ptr(logits), H.ptr(target), H.ptr(g) if ctx.per_v else None,
+               None if ctx.per_v else H.ptr(g), H.ptr(dl), B, T, V, ctx.trows, H.stream())
         return dl, None, None
 
 
@@ -1954,7 +1950,7 @@ class LincombRows(Function):
                     dp.p[i] = t.data_ptr() + 4 * j * B
                     i += 1
             du = ctypes.byref(dp)
-        _call("mmvae_lincomb_rowptrs_fwd", ctypes.byref(rp), flat, H.ptr(out), du, n, B, k, H.stream())
+        H.call("mmvae_lincomb_rowptrs_fwd", ctypes.byref(rp), flat, H.ptr(out), du, n, B, k, H.stream())
         ctx.cfg = (flat, n, B, k, rows, [tuple(t.shape) for t in blocks])
         ctx.keep = blocks
         ctx.set_materialize_grads(False)      # an unused output (kld is only logged) must not cost a zero-fill kernel
@@ -1981,7 +1977,7 @@ class LincombRows(Function):
             for j in range(r):
                 dp.p[i] = d.data_ptr() + 4 * j * B
                 i += 1
-        _call("mmvae_lincomb_rowptrs_bwd", ctypes.byref(gp), flat, ctypes.byref(dp), n, B, k, H.stream())
+        H.call("mmvae_lincomb_rowptrs_bwd", ctypes.byref(gp), flat, ctypes.byref(dp), n, B, k, H.stream())
         return (None, *outs)
 
 
@@ -2032,8 +2028,8 @@ class NormalLogRatio(Function):
         packed_r, packed_o, z = H.f32c(packed_r), H.f32c(packed_o), H.f32c(z)
         B, D2 = packed_r.shape
         lw = torch.empty(B, device=z.device)
-        _call("mmvae_normal_logratio_fwd", H.ptr(packed_r), H.ptr(packed_o), H.ptr(z), H.ptr(lw), B, D2 // 2,
-              H.stream())
+        H.call("mmvae_normal_logratio_fwd", H.ptr(packed_r), H.ptr(packed_o), H.ptr(z), H.ptr(lw), B, D2 // 2,
+               H.stream())
         ctx.save_for_backward(packed_r, z)
         return lw
 
@@ -2042,8 +2038,8 @@ class NormalLogRatio(Function):
         packed_r, z = ctx.saved_tensors
         B, D2 = packed_r.shape
         d = torch.empty_like(packed_r)
-        _call("mmvae_normal_logratio_bwd", H.ptr(packed_r), H.ptr(z), H.ptr(H.f32c(g)), H.ptr(d), B, D2 // 2,
-              H.stream())
+        H.call("mmvae_normal_logratio_bwd", H.ptr(packed_r), H.ptr(z), H.ptr(H.f32c(g)), H.ptr(d), B, D2 // 2,
+               H.stream())
         return d, None, None
 
 
@@ -2054,7 +2050,7 @@ class ExpMul(Function):
     def forward(ctx, lw, r):
         lw, r = H.f32c(lw), H.f32c(r)
         out = torch.empty_like(r)
-        _call("mmvae_expmul_fwd", H.ptr(lw), H.ptr(r), H.ptr(out), r.numel(), H.stream())
+        H.call("mmvae_expmul_fwd", H.ptr(lw), H.ptr(r), H.ptr(out), r.numel(), H.stream())
         ctx.save_for_backward(lw, r)
         return out
 
@@ -2062,7 +2058,7 @@ class ExpMul(Function):
     def backward(ctx, g):
         lw, r = ctx.saved_tensors
         dlw, dr = torch.empty_like(lw), torch.empty_like(r)
-        _call("mmvae_expmul_bwd", H.ptr(lw), H.ptr(r), H.ptr(H.f32c(g)), H.ptr(dlw), H.ptr(dr), r.numel(), H.stream())
+        H.call("mmvae_expmul_bwd", H.ptr(lw), H.ptr(r), H.ptr(H.f32c(g)), H.ptr(dlw), H.ptr(dr), r.numel(), H.stream())
         return dlw, dr
 
 
@@ -2079,7 +2075,7 @@ class MoeElbo(Function):
         kld = H.f32c(kld)
         flat = (H.c_f * n)(*[float(x) for x in W])
         out = torch.empty(2 + n, device=V.device)      # loss, n_nz, a keep flag per row
-        _call("mmvae_moe_elbo_fwd", H.ptr(V), flat, H.ptr(kld), H.ptr(out), n, M, B, float(beta), H.stream())
+        H.call("mmvae_moe_elbo_fwd", H.ptr(V), flat, H.ptr(kld), H.ptr(out), n, M, B, float(beta), H.stream())
         ctx.save_for_backward(out)
         ctx.cfg = (flat, n, M, B, float(beta), tuple(kld.shape))
         return out[0]
@@ -2090,8 +2086,8 @@ class MoeElbo(Function):
         flat, n, M, B, beta, kshape = ctx.cfg
         drows = torch.empty(n, B, device=out.device)
         dkld = torch.empty(kshape, device=out.device)
-        _call("mmvae_moe_elbo_bwd", H.ptr(H.f32c(g).reshape(1)), H.ptr(out), flat, H.ptr(drows), H.ptr(dkld), n, M, B,
-              beta, H.stream())
+        H.call("mmvae_moe_elbo_bwd", H.ptr(H.f32c(g).reshape(1)), H.ptr(out), flat, H.ptr(drows), H.ptr(dkld), n, M, B,
+               beta, H.stream())
         return (dkld, None, None, None, *[drows[i] for i in range(n)])
 
 
@@ -2103,8 +2099,8 @@ class LaplaceLogRatio(Function):
         packed_r, packed_o, z = H.f32c(packed_r), H.f32c(packed_o), H.f32c(z)
         B, D2 = packed_r.shape
         lw = torch.empty(B, device=z.device)
-        _call("mmvae_laplace_logratio_fwd", H.ptr(packed_r), H.ptr(packed_o), H.ptr(z), H.ptr(lw), B, D2 // 2,
-              H.stream())
+        H.call("mmvae_laplace_logratio_fwd", H.ptr(packed_r), H.ptr(packed_o), H.ptr(z), H.ptr(lw), B, D2 // 2,
+               H.stream())
         ctx.save_for_backward(packed_r, z)
         return lw
 
@@ -2113,8 +2109,8 @@ class LaplaceLogRatio(Function):
         packed_r, z = ctx.saved_tensors
         B, D2 = packed_r.shape
         d = torch.empty_like(packed_r)
-        _call("mmvae_laplace_logratio_bwd", H.ptr(packed_r), H.ptr(z), H.ptr(H.f32c(g)), H.ptr(d), B, D2 // 2,
-              H.stream())
+        H.call("mmvae_laplace_logratio_bwd", H.ptr(packed_r), H.ptr(z), H.ptr(H.f32c(g)), H.ptr(d), B, D2 // 2,
+               H.stream())
         return d, None, None
 
 
@@ -2126,7 +2122,7 @@ class KlLaplaceNormal(Function):
         packed = H.f32c(packed)
         B, D2 = packed.shape
         kl = torch.empty(B, device=packed.device)
-        _call("mmvae_kl_laplace_normal_fwd", H.ptr(packed), H.ptr(kl), B, D2 // 2, H.stream())
+        H.call("mmvae_kl_laplace_normal_fwd", H.ptr(packed), H.ptr(kl), B, D2 // 2, H.stream())
         ctx.save_for_backward(packed)
         return kl
 
@@ -2135,7 +2131,7 @@ class KlLaplaceNormal(Function):
         (packed,) = ctx.saved_tensors
         B, D2 = packed.shape
         d = torch.empty_like(packed)
-        _call("mmvae_kl_laplace_normal_bwd", H.ptr(packed), H.ptr(H.f32c(g)), H.ptr(d), B, D2 // 2, H.stream())
+        H.call("mmvae_kl_laplace_normal_bwd", H.ptr(packed), H.ptr(H.f32c(g)), H.ptr(d), B, D2 // 2, H.stream())
         return d
 
 
@@ -2160,8 +2156,8 @@ class MoeKSample(Function):
         for m in range(M):
             a.packed[m], a.eps[m], a.z[m], a.laplace[m] = packed[m].data_ptr(), eps[m].data_ptr(), zs[m].data_ptr(), \
                 int(laplace[m])
-        _call("mmvae_moe_ksample_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(lat), H.ptr(pi), M, K, B, D, float(beta),
-              H.stream())
+        H.call("mmvae_moe_ksample_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(lat), H.ptr(pi), M, K, B, D, float(beta),
+               H.stream())
         ctx.save_for_backward(theta, pi, z, *packed, *eps)
         ctx.cfg = (gtheta, tuple(int(x) for x in laplace), M, K, B, D, float(beta))
         ctx.set_materialize_grads(False)
@@ -2187,8 +2183,8 @@ class MoeKSample(Function):
         rows = None
         if ctx.needs_input_grad[0] or gtheta is not None:
             rows = GradReducer.alloc(B * D, dev) if _defer(gtheta) else torch.empty(B, D, device=dev)
-        _call("mmvae_moe_ksample_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(dlat), H.ptr(pi), H.ptr(rows), M, K, B, D,
-              beta, H.stream())
+        H.call("mmvae_moe_ksample_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(dlat), H.ptr(pi), H.ptr(rows), M, K, B, D,
+               beta, H.stream())
         if rows is not None:
             if _defer(gtheta):
                 GradReducer.add(rows.data_ptr(), gtheta, B, D, D)
@@ -2218,7 +2214,7 @@ class DregLoss(Function):
         t = H.DregRows()
         for r in range(M):
             t.own[r], t.cross[r], t.lam[r] = rows[2 * r].data_ptr(), rows[2 * r + 1].data_ptr(), float(lam[r])
-        _call("mmvae_dreg_loss_fwd", H.ptr(lat), ctypes.byref(t), H.ptr(out), M, K, B, H.stream())
+        H.call("mmvae_dreg_loss_fwd", H.ptr(lat), ctypes.byref(t), H.ptr(out), M, K, B, H.stream())
         ctx.save_for_backward(out)
         ctx.cfg = (tuple(float(x) for x in lam), M, K, B, [tuple(r.shape) for r in rows])
         rec = out[1 + 2 * M * K:].view(M, 2, K)
@@ -2236,7 +2232,7 @@ class DregLoss(Function):
         t = H.DregRows()
         for r in range(M):
             t.own[r], t.cross[r], t.lam[r] = drows[2 * r].data_ptr(), drows[2 * r + 1].data_ptr(), lam[r]
-        _call("mmvae_dreg_loss_bwd", H.ptr(out), H.ptr(g), ctypes.byref(t), H.ptr(dlat), M, K, B, H.stream())
+        H.call("mmvae_dreg_loss_bwd", H.ptr(out), H.ptr(g), ctypes.byref(t), H.ptr(dlat), M, K, B, H.stream())
         return (dlat, None, None, *drows)
 
 
@@ -2259,7 +2255,7 @@ class IwaeLoss(Function):
         t = H.DregRows()
         for r in range(M):
             t.own[r], t.cross[r], t.lam[r] = rows[2 * r].data_ptr(), rows[2 * r + 1].data_ptr(), float(lam[r])
-        _call("mmvae_iwae_loss_fwd", H.ptr(lat), ctypes.byref(t), H.ptr(out), M, K, B, H.stream())
+        H.call("mmvae_iwae_loss_fwd", H.ptr(lat), ctypes.byref(t), H.ptr(out), M, K, B, H.stream())
         ctx.save_for_backward(lat, out)
         ctx.cfg = (tuple(float(x) for x in lam), M, K, B)
         rec = out[1 + B:].view(M, 2, K * B)
@@ -2277,7 +2273,7 @@ class IwaeLoss(Function):
         t = H.DregRows()
         for r in range(M):
             t.own[r], t.cross[r], t.lam[r] = drows[2 * r].data_ptr(), drows[2 * r + 1].data_ptr(), lam[r]
-        _call("mmvae_iwae_loss_bwd", H.ptr(lat), H.ptr(out), H.ptr(g), ctypes.byref(t), H.ptr(dlat), M, K, B, H.stream())
+        H.call("mmvae_iwae_loss_bwd", H.ptr(lat), H.ptr(out), H.ptr(g), ctypes.byref(t), H.ptr(dlat), M, K, B, H.stream())
         return (dlat, None, None, *drows)
 
 
@@ -2336,8 +2332,8 @@ class EmbedPE(Function):
         B0, T, V = onehot.shape
         B = B0 * repeat
         x = torch.empty(T, B, 2 * V, device=onehot.device)
-        _call("mmvae_embed_pe_fwd", H.ptr(onehot), H.ptr(emb), H.ptr(pe), H.ptr(x), B, T, V, mode, B0, _dp(drop, x.numel()),
-              H.stream())
+        H.call("mmvae_embed_pe_fwd", H.ptr(onehot), H.ptr(emb), H.ptr(pe), H.ptr(x), B, T, V, mode, B0, _dp(drop, x.numel()),
+               H.stream())
         ctx.save_for_backward(onehot, emb)
         ctx.cfg = (mode, gemb, drop, repeat)
         return x
@@ -2354,13 +2350,13 @@ class EmbedPE(Function):
         nws = H.lib().mmvae_embed_ws_floats(B, T, V)
         if _defer(gemb):
             ws = GradReducer.alloc(nws, dx.device)
-            _call("mmvae_embed_pe_bwd", H.ptr(onehot), H.ptr(dx), None, H.ptr(ws), B, T, V, mode, B0, H.ACC_DEFER, dpc,
-                  H.stream())
+            H.call("mmvae_embed_pe_bwd", H.ptr(onehot), H.ptr(dx), None, H.ptr(ws), B, T, V, mode, B0, H.ACC_DEFER, dpc,
+                   H.stream())
             GradReducer.add(ws.data_ptr(), de, H.lib().mmvae_embed_bwd_rows(B, T, V), 4, 4)
         else:
             ws = H.workspace(nws, dx.device)
-            _call("mmvae_embed_pe_bwd", H.ptr(onehot), H.ptr(dx), H.ptr(de), H.ptr(ws), B, T, V, mode, B0, acc, dpc,
-                  H.stream())
+            H.call("mmvae_embed_pe_bwd", H.ptr(onehot), H.ptr(dx), H.ptr(de), H.ptr(ws), B, T, V, mode, B0, acc, dpc,
+                   H.stream())
         GradReducer.run_side_tail(dx.device)      # the text encoder's LAST backward launch: its stream idles from here on
         return None, ret, None, None, None, None, None
 
@@ -2377,8 +2373,8 @@ class Attention(Function):
         out = torch.empty(L, N, E, device=qkv.device)
         probs = torch.empty(N, nhead, L, L, device=qkv.device)
         p = qkv.data_ptr()
-        _call("mmvae_attn_fwd", p, p + 4 * E, p + 8 * E, H.ptr(kpm), H.ptr(out), H.ptr(probs), L, L, N, nhead, hd, E3,
-              E3, E3, int(mask_is_valid), _dp(drop, probs.numel()), H.stream())
+        H.call("mmvae_attn_fwd", p, p + 4 * E, p + 8 * E, H.ptr(kpm), H.ptr(out), H.ptr(probs), L, L, N, nhead, hd, E3,
+               E3, E3, int(mask_is_valid), _dp(drop, probs.numel()), H.stream())
         ctx.save_for_backward(qkv, probs)
         ctx.nhead = nhead
         ctx.drop = drop
@@ -2393,8 +2389,8 @@ class Attention(Function):
         dout = H.f32c(dout)
         dqkv = torch.empty_like(qkv)
         p, d = qkv.data_ptr(), dqkv.data_ptr()
-        _call("mmvae_attn_bwd", p, p + 4 * E, p + 8 * E, H.ptr(probs), H.ptr(dout), d, d + 4 * E, d + 8 * E, L, L, N,
-              nhead, E // nhead, E3, E3, E3, ctx.drop.c() if ctx.drop is not None else None, H.stream())
+        H.call("mmvae_attn_bwd", p, p + 4 * E, p + 8 * E, H.ptr(probs), H.ptr(dout), d, d + 4 * E, d + 8 * E, L, L, N,
+               nhead, E // nhead, E3, E3, E3, ctx.drop.c() if ctx.drop is not None else None, H.stream())
         return dqkv, None, None, None, None
 
 
@@ -2414,8 +2410,8 @@ def _linear_wgrad(dy2, x2, w, b, gw, gb, x_act=H.ACT_NONE):
         ws, acc = H.workspace(nws, dy2.device), acc_w
     if gw is not None and not (defer and nz > 1):
         GradReducer.writes(dy2.device, gw, gb)
-    _call("mmvae_linear_bwd_weight", H.ptr(dy2), H.ptr(x2), H.ptr(dw), H.ptr(db), H.ptr(ws), M, N, K, K, x_act, acc,
-          H.stream())
+    H.call("mmvae_linear_bwd_weight", H.ptr(dy2), H.ptr(x2), H.ptr(dw), H.ptr(db), H.ptr(ws), M, N, K, K, x_act, acc,
+           H.stream())
     if defer and nz > 1:
         GradReducer.add(ws.data_ptr(), dw, nz, N * K, N * K)
         if db is not None:
@@ -2450,7 +2446,7 @@ def _txt_wgrad(jobs):
         j.dy, j.x, j.ws, j.M, j.N, j.K = H.ptr(dy2), H.ptr(x2), H.ptr(ws), M, N, K
         segs.append((ws, nz, gw, gb, N, K, nws // nz))
     GradReducer.run_early_step(jobs[0][0].device)
-    _call("mmvae_txt_wgrad", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
+    H.call("mmvae_txt_wgrad", ctypes.cast(arr, ctypes.c_void_p), len(jobs), H.stream())
     for ws, nz, gw, gb, N, K, pitch in segs:      # (partial row z: [N * K weight sums | N bias sums] at ws + z * pitch)
         GradReducer.add(ws.data_ptr(), gw, nz, N * K, pitch)
         GradReducer.add(ws.data_ptr() + 4 * N * K, gb, nz, N, pitch)
@@ -2525,9 +2521,9 @@ class TxtLayer(Function):
             HN = hw.shape[0]
             hout = e(N, HN)
             S["z"] = y
-        _call("mmvae_txt_layer_fwd", H.ptr(x), H.ptr(mask_u8), H.ptr(mem) if dec else None, H.ptr(y), ctypes.byref(w),
-              ctypes.byref(sv), meta.c_drop(L, N), L, N, D, FF, NH, int(dec), int(meta.time_mean), H.ptr(hw), H.ptr(hb),
-              H.ptr(hout), HN, H.stream())
+        H.call("mmvae_txt_layer_fwd", H.ptr(x), H.ptr(mask_u8), H.ptr(mem) if dec else None, H.ptr(y), ctypes.byref(w),
+               ctypes.byref(sv), meta.c_drop(L, N), L, N, D, FF, NH, int(dec), int(meta.time_mean), H.ptr(hw), H.ptr(hb),
+               H.ptr(hout), HN, H.stream())
         ctx.meta, ctx.names, ctx.grads, ctx.S = meta, names, grads, S
         ctx.save_for_backward(x, mem if dec else None, mask_u8, *params)
         return y if hout is None else hout
@@ -2552,8 +2548,8 @@ class TxtLayer(Function):
             nz = lib.mmvae_linear_bwd_splits(N, HN, D)
             nws = lib.mmvae_linear_bwd_ws_floats(N, HN, D)
             ws = GradReducer.alloc(nws, dev) if nz > 1 else None
-            _call("mmvae_linear_bwd", H.ptr(dy), H.ptr(z), H.ptr(hw), None, H.ptr(dz), H.ptr(hgw), H.ptr(hgb),
-                  H.ptr(ws), N, HN, D, D, H.ACT_NONE, H.EP_NONE, H.ACC_DEFER, H.stream())
+            H.call("mmvae_linear_bwd", H.ptr(dy), H.ptr(z), H.ptr(hw), None, H.ptr(dz), H.ptr(hgw), H.ptr(hgb),
+                   H.ptr(ws), N, HN, D, D, H.ACT_NONE, H.EP_NONE, H.ACC_DEFER, H.stream())
             if nz > 1:
                 GradReducer.add(ws.data_ptr(), hgw, nz, HN * D, HN * D)
                 GradReducer.add(ws.data_ptr() + 4 * nz * HN * D, hgb, nz, HN, HN)
@@ -2590,8 +2586,8 @@ class TxtLayer(Function):
                 if d is not None:
                     setattr(t, k, H.Dropout(d.state.data_ptr(), d.slot, d.site, d.p))
             dstruct = ctypes.byref(t)
-        _call("mmvae_txt_layer_bwd", H.ptr(dy), H.ptr(mask_u8), H.ptr(dx), H.ptr(dmem), ctypes.byref(w),
-              ctypes.byref(sv), ctypes.byref(gr), dstruct, L, N, D, FF, NH, int(dec), int(meta.time_mean), H.stream())
+        H.call("mmvae_txt_layer_bwd", H.ptr(dy), H.ptr(mask_u8), H.ptr(dx), H.ptr(dmem), ctypes.byref(w),
+               ctypes.byref(sv), ctypes.byref(gr), dstruct, L, N, D, FF, NH, int(dec), int(meta.time_mean), H.stream())
         M = L * N
         ret = {}
 
@@ -2665,14 +2661,14 @@ class LayerNormResidual(Function):
             fused = (d == 32 and xin.shape[-1] == 32 and r is not None and r_rows == 0 and pb is not None and pw.is_contiguous()
                      and all(al(t) for t in (xin, pw, pb, r, gamma, beta, y, xhat)))
             if fused:
-                _call("mmvae_proj32_ln_fwd", H.ptr(xin), H.ptr(pw), H.ptr(pb), H.ptr(r), H.ptr(gamma), H.ptr(beta), H.ptr(y),
-                      H.ptr(xhat), H.ptr(rstd), rows, _dp(drop, x.numel()), H.stream())
+                H.call("mmvae_proj32_ln_fwd", H.ptr(xin), H.ptr(pw), H.ptr(pb), H.ptr(r), H.ptr(gamma), H.ptr(beta), H.ptr(y),
+                       H.ptr(xhat), H.ptr(rstd), rows, _dp(drop, x.numel()), H.stream())
             else:      # the Linear after all (its output was never computed), then the plain LayerNorm below
-                _call("mmvae_linear_fwd", H.ptr(xin), H.ptr(pw), H.ptr(pb), None, H.ptr(x), rows, d, xin.shape[-1],
-                      xin.shape[-1], H.ACT_NONE, H.EP_NONE, H.stream())
+                H.call("mmvae_linear_fwd", H.ptr(xin), H.ptr(pw), H.ptr(pb), None, H.ptr(x), rows, d, xin.shape[-1],
+                       xin.shape[-1], H.ACT_NONE, H.EP_NONE, H.stream())
         if not fused:
-            _call("mmvae_layernorm_residual_fwd", H.ptr(x), H.ptr(r), H.ptr(gamma), H.ptr(beta), H.ptr(y), H.ptr(xhat),
-                  H.ptr(rstd), rows, d, r_rows, _dp(drop, x.numel()), H.stream())
+            H.call("mmvae_layernorm_residual_fwd", H.ptr(x), H.ptr(r), H.ptr(gamma), H.ptr(beta), H.ptr(y), H.ptr(xhat),
+                   H.ptr(rstd), rows, d, r_rows, _dp(drop, x.numel()), H.stream())
         ctx.save_for_backward(xhat, rstd, gamma)
         ctx.cfg = (gg, gb, r is not None, r_rows, tuple(x.shape), tuple(r.shape) if r is not None else None, drop)
         ctx.res_sink = res_sink if (r is not None and r_rows == 0) else None
@@ -2697,20 +2693,20 @@ class LayerNormResidual(Function):
         nws = H.lib().mmvae_layernorm_ws_floats(rows, d)
         if _defer(gg, gb):
             ws = GradReducer.alloc(nws, dy.device)
-            _call("mmvae_layernorm_residual_bwd", H.ptr(dy), H.ptr(xhat), H.ptr(rstd), H.ptr(gamma), H.ptr(dsum),
-                  H.ptr(dxd), None, None, H.ptr(ws), rows, d, H.ACC_DEFER, dpc, H.stream())
+            H.call("mmvae_layernorm_residual_bwd", H.ptr(dy), H.ptr(xhat), H.ptr(rstd), H.ptr(gamma), H.ptr(dsum),
+                   H.ptr(dxd), None, None, H.ptr(ws), rows, d, H.ACC_DEFER, dpc, H.stream())
             nb = H.lib().mmvae_layernorm_bwd_rows(rows, d)
             GradReducer.add(ws.data_ptr(), dg, nb, d, 2 * d)
             GradReducer.add(ws.data_ptr() + 4 * d, dbt, nb, d, 2 * d)
         else:
             ws = H.workspace(nws, dy.device)
-            _call("mmvae_layernorm_residual_bwd", H.ptr(dy), H.ptr(xhat), H.ptr(rstd), H.ptr(gamma), H.ptr(dsum),
-                  H.ptr(dxd), dg.data_ptr(), dbt.data_ptr(), H.ptr(ws), rows, d, acc, dpc, H.stream())
+            H.call("mmvae_layernorm_residual_bwd", H.ptr(dy), H.ptr(xhat), H.ptr(rstd), H.ptr(gamma), H.ptr(dsum),
+                   H.ptr(dxd), dg.data_ptr(), dbt.data_ptr(), H.ptr(ws), rows, d, acc, dpc, H.stream())
         dr = None
         if has_r and ctx.needs_input_grad[1]:
             if r_rows:
                 dr = torch.empty(rshape, device=dy.device)
-                _call("mmvae_sum_over_time", H.ptr(dsum), H.ptr(dr), rows // r_rows, r_rows, d, H.stream())
+                H.call("mmvae_sum_over_time", H.ptr(dsum), H.ptr(dr), rows // r_rows, r_rows, d, H.stream())
             elif ctx.res_sink is not None:
                 ctx.res_sink.grad = dsum          # picked up by the sub-layer's first backward (ResidualGrad)
             else:
@@ -2725,7 +2721,7 @@ class MeanOverTime(Function):
         x = H.f32c(x)
         L, N, d = x.shape
         y = torch.empty(N, d, device=x.device)
-        _call("mmvae_mean_over_time_fwd", H.ptr(x), H.ptr(y), L, N, d, H.stream())
+        H.call("mmvae_mean_over_time_fwd", H.ptr(x), H.ptr(y), L, N, d, H.stream())
         ctx.shape = (L, N, d)
         return y
 
@@ -2734,7 +2730,7 @@ class MeanOverTime(Function):
         L, N, d = ctx.shape
         dy = H.f32c(dy)
         dx = torch.empty(L, N, d, device=dy.device)
-        _call("mmvae_mean_over_time_bwd", H.ptr(dy), H.ptr(dx), L, N, d, H.stream())
+        H.call("mmvae_mean_over_time_bwd", H.ptr(dy), H.ptr(dx), L, N, d, H.stream())
         return dx
 
 
@@ -2750,9 +2746,9 @@ class PermuteMask(Function):
         assert 0 < Tk <= T and tuple(mask_u8.shape) == (B, T)
         y = torch.empty(B, Tk, V, device=x.device)
         if Tk == T:
-            _call("mmvae_permute_mask_fwd", H.ptr(x), H.ptr(mask_u8), H.ptr(y), T, B, V, H.stream())
+            H.call("mmvae_permute_mask_fwd", H.ptr(x), H.ptr(mask_u8), H.ptr(y), T, B, V, H.stream())
         else:
-            _call("mmvae_permute_mask_head_fwd", H.ptr(x), H.ptr(mask_u8), H.ptr(y), T, B, V, Tk, H.stream())
+            H.call("mmvae_permute_mask_head_fwd", H.ptr(x), H.ptr(mask_u8), H.ptr(y), T, B, V, Tk, H.stream())
         ctx.save_for_backward(mask_u8)
         ctx.shape = (T, B, V, Tk)
         return y
@@ -2764,9 +2760,9 @@ class PermuteMask(Function):
         dy = H.f32c(dy)
         dx = torch.empty(T, B, V, device=dy.device)
         if Tk == T:
-            _call("mmvae_permute_mask_bwd", H.ptr(dy), H.ptr(mask_u8), H.ptr(dx), T, B, V, H.stream())
+            H.call("mmvae_permute_mask_bwd", H.ptr(dy), H.ptr(mask_u8), H.ptr(dx), T, B, V, H.stream())
         else:
-            _call("mmvae_permute_mask_head_bwd", H.ptr(dy), H.ptr(mask_u8), H.ptr(dx), T, B, V, Tk, H.stream())
+            H.call("mmvae_permute_mask_head_bwd", H.ptr(dy), H.ptr(mask_u8), H.ptr(dx), T, B, V, Tk, H.stream())
         return dx, None, None
 
 
@@ -2800,7 +2796,7 @@ class DropoutAct(Function):
     def forward(ctx, x, act, drop):
         x = H.f32c(x)
         y = torch.empty_like(x)
-        _call("mmvae_dropout_act_fwd", H.ptr(x), H.ptr(y), x.numel(), act, _dp(drop, x.numel()), H.stream())
+        H.call("mmvae_dropout_act_fwd", H.ptr(x), H.ptr(y), x.numel(), act, _dp(drop, x.numel()), H.stream())
         ctx.save_for_backward(x)
         ctx.cfg = (act, drop)
         return y
@@ -2811,8 +2807,8 @@ class DropoutAct(Function):
         act, drop = ctx.cfg
         dy = H.f32c(dy)
         dx = torch.empty_like(x)
-        _call("mmvae_dropout_act_bwd", H.ptr(dy), H.ptr(x), H.ptr(dx), x.numel(), act, drop.c() if drop else None,
-              H.stream())
+        H.call("mmvae_dropout_act_bwd", H.ptr(dy), H.ptr(x), H.ptr(dx), x.numel(), act, drop.c() if drop else None,
+               H.stream())
         return dx, None, None
 
 
@@ -2824,8 +2820,8 @@ class HeadBcastDropout(Function):
         v = H.f32c(v)
         N, E = v.shape
         out = torch.empty(L, N, E, device=v.device)
-        _call("mmvae_head_bcast_dropout_fwd", H.ptr(v), H.ptr(out), L, N, nhead, E // nhead, _dp(drop, N * nhead * L),
-              H.stream())
+        H.call("mmvae_head_bcast_dropout_fwd", H.ptr(v), H.ptr(out), L, N, nhead, E // nhead, _dp(drop, N * nhead * L),
+               H.stream())
         ctx.cfg = (L, N, E, nhead, drop)
         return out
 
@@ -2834,8 +2830,8 @@ class HeadBcastDropout(Function):
         L, N, E, nhead, drop = ctx.cfg
         dout = H.f32c(dout)
         dv = torch.empty(N, E, device=dout.device)
-        _call("mmvae_head_bcast_dropout_bwd", H.ptr(dout), H.ptr(dv), L, N, nhead, E // nhead,
-              drop.c() if drop else None, H.stream())
+        H.call("mmvae_head_bcast_dropout_bwd", H.ptr(dout), H.ptr(dv), L, N, nhead, E // nhead,
+               drop.c() if drop else None, H.stream())
         return dv, None, None, None
 
 
@@ -2862,21 +2858,21 @@ class Ffn32(Function):
             # for all layers of a tower: ffn32_prep_many), else made here
             if wsplit is None:
                 wsplit = torch.empty(H.lib().mmvae_ffn32_wsplit_bytes(FF), dtype=torch.uint8, device=x.device)
-                _call("mmvae_ffn32_prep_weights", H.ptr(w1), H.ptr(w2), H.ptr(wsplit), FF, H.stream())
+                H.call("mmvae_ffn32_prep_weights", H.ptr(w1), H.ptr(w2), H.ptr(wsplit), FF, H.stream())
             if ln is not None:
                 r_, gamma_, beta_, ln_drop = ln
                 r_ = H.f32c(r_)
                 yln, xhat, rstd = torch.empty_like(x), torch.empty_like(x), torch.empty(M, device=x.device)
-                _call("mmvae_ffn32_fwd_b16_ln", H.ptr(x), H.ptr(wsplit), H.ptr(b1), H.ptr(b2), H.ptr(r_), H.ptr(gamma_),
-                      H.ptr(beta_), H.ptr(yln), H.ptr(xhat), H.ptr(rstd), M, FF, _dp(drop, M * FF), _dp(ln_drop, M * 32),
-                      H.stream())
+                H.call("mmvae_ffn32_fwd_b16_ln", H.ptr(x), H.ptr(wsplit), H.ptr(b1), H.ptr(b2), H.ptr(r_), H.ptr(gamma_),
+                       H.ptr(beta_), H.ptr(yln), H.ptr(xhat), H.ptr(rstd), M, FF, _dp(drop, M * FF), _dp(ln_drop, M * 32),
+                       H.stream())
                 Ffn32.last_pre = (yln, xhat, rstd)
             else:
-                _call("mmvae_ffn32_fwd_b16", H.ptr(x), H.ptr(wsplit), H.ptr(b1), H.ptr(b2), H.ptr(y), M, FF,
-                      _dp(drop, M * FF), H.stream())
+                H.call("mmvae_ffn32_fwd_b16", H.ptr(x), H.ptr(wsplit), H.ptr(b1), H.ptr(b2), H.ptr(y), M, FF,
+                       _dp(drop, M * FF), H.stream())
         else:
-            _call("mmvae_ffn32_fwd", H.ptr(x), H.ptr(w1), H.ptr(b1), H.ptr(w2), H.ptr(b2), H.ptr(y), M, FF,
-                  _dp(drop, M * FF), H.stream())
+            H.call("mmvae_ffn32_fwd", H.ptr(x), H.ptr(w1), H.ptr(b1), H.ptr(w2), H.ptr(b2), H.ptr(y), M, FF,
+                   _dp(drop, M * FF), H.stream())
         ctx.save_for_backward(x, w1, b1, w2)
         ctx.wsplit = wsplit
         ctx.cfg = (drop, gw1, gb1, gw2, gb2)
@@ -2907,14 +2903,14 @@ class Ffn32(Function):
                 kadd, radd = radd, None
 
             def bwd(dx_, ws_):
-                _call("mmvae_ffn32_bwd_b16", H.ptr(x), H.ptr(dy), H.ptr(wsplit), H.ptr(b1), H.ptr(dx_), H.ptr(ws_), H.ptr(rsplit),
-                      H.ptr(kadd) if dx_ is not None else None, M, FF, dc, H.stream())
+                H.call("mmvae_ffn32_bwd_b16", H.ptr(x), H.ptr(dy), H.ptr(wsplit), H.ptr(b1), H.ptr(dx_), H.ptr(ws_), H.ptr(rsplit),
+                       H.ptr(kadd) if dx_ is not None else None, M, FF, dc, H.stream())
         else:
             rsplit = None
 
             def bwd(dx_, ws_):
-                _call("mmvae_ffn32_bwd", H.ptr(x), H.ptr(dy), H.ptr(w1), H.ptr(b1), H.ptr(w2),
-                      H.ptr(dx_) if dx_ is not None else None, H.ptr(ws_) if ws_ is not None else None, M, FF, dc, H.stream())
+                H.call("mmvae_ffn32_bwd", H.ptr(x), H.ptr(dy), H.ptr(w1), H.ptr(b1), H.ptr(w2),
+                       H.ptr(dx_) if dx_ is not None else None, H.ptr(ws_) if ws_ is not None else None, M, FF, dc, H.stream())
         if other is not None:
             # the weight-gradient launch (nothing but the end-of-backward fold reads it) goes to the step's OTHER stream,
             # which idles while a long tower's chain runs on this one; only dy and x have to exist, not the data gradient
@@ -2941,7 +2937,7 @@ class Ffn32(Function):
         else:
             for i, (o, ln, g, like) in enumerate(zip(offs, lens, (gw1, gb1, gw2, gb2), (w1, b1, w2, b1[:32]))):
                 dst, acc, ret = _new_like_param(like, g)
-                _call("mmvae_reduce_rows", H.ptr(ws) + 4 * o, H.ptr(dst), parts, ln, rowlen, acc, H.stream())
+                H.call("mmvae_reduce_rows", H.ptr(ws) + 4 * o, H.ptr(dst), parts, ln, rowlen, acc, H.stream())
                 rets[i] = ret
         if radd is not None and dx is not None:
             dx = dx + radd.view_as(dx)
@@ -2981,8 +2977,8 @@ def ffn32_prep_many(pairs):
     nb = H.lib().mmvae_ffn32_wsplit_bytes(FF)
     buf = torch.empty(n, nb, dtype=torch.uint8, device=dev)
     arr = ctypes.c_void_p * n
-    _call("mmvae_ffn32_prep_weights_many", arr(*[w1.data_ptr() for w1, _ in pairs]), arr(*[w2.data_ptr() for _, w2 in pairs]),
-          arr(*[buf[i].data_ptr() for i in range(n)]), n, FF, H.stream())
+    H.call("mmvae_ffn32_prep_weights_many", arr(*[w1.data_ptr() for w1, _ in pairs]), arr(*[w2.data_ptr() for _, w2 in pairs]),
+           arr(*[buf[i].data_ptr() for i in range(n)]), n, FF, H.stream())
     return [buf[i] for i in range(n)]
 
 
@@ -3014,7 +3010,7 @@ def gru_token_ids(onehot):
     B, T, V = onehot.shape
     ids = torch.empty(T, B, dtype=torch.int32, device=onehot.device)
     oh = torch.empty(T * B, V, device=onehot.device)
-    _call("mmvae_gru_token_ids", H.ptr(onehot), H.ptr(ids), H.ptr(oh), B, T, V, H.stream())
+    H.call("mmvae_gru_token_ids", H.ptr(onehot), H.ptr(ids), H.ptr(oh), B, T, V, H.stream())
     return ids, oh
 
 
@@ -3033,8 +3029,8 @@ class GruForward(Function):
         hs = torch.empty(T + 1, B, Hd, device=dev)
         fill(hs[0], 0.0)
         saved = torch.empty(4, T, B, Hd, device=dev)
-        _call("mmvae_gru_forward", H.ptr(pt), H.ptr(b_ih), H.ptr(w_hh), H.ptr(b_hh), H.ptr(ids), H.ptr(hs), H.ptr(saved),
-              T, B, Hd, V, H.stream())
+        H.call("mmvae_gru_forward", H.ptr(pt), H.ptr(b_ih), H.ptr(w_hh), H.ptr(b_hh), H.ptr(ids), H.ptr(hs), H.ptr(saved),
+               T, B, Hd, V, H.stream())
         ctx.save_for_backward(pt, b_ih, w_hh, b_hh, hs, saved, oh)
         ctx.cfg = (T, B, Hd, V, gw_hh, gb_hh)
         return hs[T]
@@ -3047,8 +3043,8 @@ class GruForward(Function):
         dh = H.f32c(dhT).clone()
         dgx = torch.empty(T, B, 3 * Hd, device=dev)
         dgh = torch.empty(T, B, 3 * Hd, device=dev)
-        _call("mmvae_gru_backward", H.ptr(dh), H.ptr(w_hh), H.ptr(hs), H.ptr(saved), H.ptr(dgx), H.ptr(dgh), T, B, Hd,
-              H.stream())
+        H.call("mmvae_gru_backward", H.ptr(dh), H.ptr(w_hh), H.ptr(hs), H.ptr(saved), H.ptr(dgx), H.ptr(dgh), T, B, Hd,
+               H.stream())
         # d W_hh (3H,H) = sum_t dGh_t^T h_{t-1}, d b_hh = column sums: reduction over the T*B rows
         ret_whh, ret_bhh = _linear_wgrad(dgh.view(T * B, 3 * Hd), hs[:T].reshape(T * B, Hd), w_hh, b_hh, gw_hh, gb_hh)
         # d pt (3H,V) = sum_t dGx_t^T onehot(id_t), d b_ih = column sums
@@ -3066,8 +3062,8 @@ class GruCell0(Function):
         V = pt.shape[1]
         out = torch.empty_like(h_fwd)
         saved = torch.empty(3, B, Hd, device=pt.device)
-        _call("mmvae_gru_cell0_fwd", H.ptr(pt), H.ptr(b_ih), H.ptr(b_hh), H.ptr(ids_last), H.ptr(h_fwd), H.ptr(out),
-              H.ptr(saved), B, Hd, V, H.stream())
+        H.call("mmvae_gru_cell0_fwd", H.ptr(pt), H.ptr(b_ih), H.ptr(b_hh), H.ptr(ids_last), H.ptr(h_fwd), H.ptr(out),
+               H.ptr(saved), B, Hd, V, H.stream())
         ctx.save_for_backward(pt, b_ih, b_hh, saved, oh_last)
         ctx.cfg = (B, Hd, V)
         return out
@@ -3079,7 +3075,7 @@ class GruCell0(Function):
         dout = H.f32c(dout)
         dgx = torch.empty(B, 3 * Hd, device=pt.device)
         dgh = torch.empty(B, 3 * Hd, device=pt.device)
-        _call("mmvae_gru_cell0_bwd", H.ptr(dout), H.ptr(saved), H.ptr(b_hh), H.ptr(dgx), H.ptr(dgh), B, Hd, H.stream())
+        H.call("mmvae_gru_cell0_bwd", H.ptr(dout), H.ptr(saved), H.ptr(b_hh), H.ptr(dgx), H.ptr(dgh), B, Hd, H.stream())
         d_pt, d_bih = _linear_wgrad(dgx, oh_last, pt, b_ih, None, None)
         _, d_bhh = _linear_wgrad(dgh, oh_last, pt, b_hh, None, None)      # column sums of dGh (the dW half is unused)
         return d_pt, d_bih, d_bhh, None, None, dout, None
@@ -3098,14 +3094,14 @@ WEIGHT_GEN = [0]      # bumped by every optimiser launch: caches derived from th
 
 def adam_amsgrad_flat(p, g, m, v, vmax, lr, beta1, beta2, eps, step, step_dev=None, grad_scale=1.0, zero_grad=True):
     WEIGHT_GEN[0] += 1
-    _call("mmvae_adam_amsgrad_flat", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), lr, beta1, beta2,
-          eps, int(step), H.ptr(step_dev), grad_scale, int(zero_grad), H.stream())
+    H.call("mmvae_adam_amsgrad_flat", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), lr, beta1, beta2,
+           eps, int(step), H.ptr(step_dev), grad_scale, int(zero_grad), H.stream())
 
 
 def adabelief_flat(p, g, m, s, lr, beta1, beta2, eps, step, step_dev=None, grad_scale=1.0, zero_grad=True):
     WEIGHT_GEN[0] += 1
-    _call("mmvae_adabelief_flat", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(s), p.numel(), lr, beta1, beta2, eps, int(step),
-          H.ptr(step_dev), grad_scale, int(zero_grad), H.stream())
+    H.call("mmvae_adabelief_flat", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(s), p.numel(), lr, beta1, beta2, eps, int(step),
+           H.ptr(step_dev), grad_scale, int(zero_grad), H.stream())
 
 
 def _tail_args(tail):
@@ -3119,22 +3115,22 @@ def _tail_args(tail):
 def adam_fold_flat(p, g, m, v, vmax, lr, beta1, beta2, eps, step_dev, grad_scale, zero_grad, deferred):
     """GradReducer.deferred + Adam(amsgrad) in one launch (mmvae_adam_fold_flat)"""
     WEIGHT_GEN[0] += 1
-    _call("mmvae_adam_fold_flat", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), lr, beta1, beta2, eps,
-          H.ptr(step_dev), grad_scale, int(zero_grad), ctypes.byref(deferred["table"]), *_tail_args(deferred["tail"]),
-          H.stream())
+    H.call("mmvae_adam_fold_flat", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), lr, beta1, beta2, eps,
+           H.ptr(step_dev), grad_scale, int(zero_grad), ctypes.byref(deferred["table"]), *_tail_args(deferred["tail"]),
+           H.stream())
 
 
 def adam_fold_range(p, g, m, v, vmax, lo, hi, advance, lr, beta1, beta2, eps, step_dev, grad_scale, zero_grad, table, tail=None):
     """the same over elements [lo, hi) only, with the segments of `table` (H.ReduceSegments or None) that lie inside
     (mmvae_adam_fold_range); advance: this is the launch that closes the step"""
     WEIGHT_GEN[0] += 1
-    _call("mmvae_adam_fold_range", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), int(lo), int(hi),
-          int(advance), lr, beta1, beta2, eps, H.ptr(step_dev), grad_scale, int(zero_grad),
-          ctypes.byref(table) if table is not None else None, *_tail_args(tail), H.stream())
+    H.call("mmvae_adam_fold_range", H.ptr(p), H.ptr(g), H.ptr(m), H.ptr(v), H.ptr(vmax), p.numel(), int(lo), int(hi),
+           int(advance), lr, beta1, beta2, eps, H.ptr(step_dev), grad_scale, int(zero_grad),
+           ctypes.byref(table) if table is not None else None, *_tail_args(tail), H.stream())
 
 
 def step_inc(step_dev):
-    _call("mmvae_step_inc", H.ptr(step_dev), H.stream())
+    H.call("mmvae_step_inc", H.ptr(step_dev), H.stream())
 
 
 class Sigmoid(Function):
@@ -3142,7 +3138,7 @@ class Sigmoid(Function):
     def forward(ctx, x):
         x = H.f32c(x)
         y = torch.empty_like(x)
-        _call("mmvae_sigmoid_fwd", H.ptr(x), H.ptr(y), x.numel(), H.stream())
+        H.call("mmvae_sigmoid_fwd", H.ptr(x), H.ptr(y), x.numel(), H.stream())
         ctx.save_for_backward(y)
         return y
 
@@ -3150,7 +3146,7 @@ class Sigmoid(Function):
     def backward(ctx, dy):
         (y,) = ctx.saved_tensors
         dx = torch.empty_like(y)
-        _call("mmvae_sigmoid_bwd", H.ptr(H.f32c(dy)), H.ptr(y), H.ptr(dx), y.numel(), H.stream())
+        H.call("mmvae_sigmoid_bwd", H.ptr(H.f32c(dy)), H.ptr(y), H.ptr(dx), y.numel(), H.stream())
         return dx
 
 
@@ -3161,14 +3157,14 @@ def sigmoid(x):
 def randn(shape, state):
     """standard-normal tensor from the counter-based device generator (`state`: int32[3] = seed, counter, ticket)"""
     out = torch.empty(shape, device=state.device)
-    _call("mmvae_randn", H.ptr(out), out.numel(), H.ptr(state), H.stream())
+    H.call("mmvae_randn", H.ptr(out), out.numel(), H.ptr(state), H.stream())
     return out
 
 
 def rand_laplace(shape, state):
     """standard-Laplace variates (Laplace.rsample: z = loc + scale * e) from the counter-based device generator"""
     out = torch.empty(shape, device=state.device)
-    _call("mmvae_rand_laplace", H.ptr(out), out.numel(), H.ptr(state), H.stream())
+    H.call("mmvae_rand_laplace", H.ptr(out), out.numel(), H.ptr(state), H.stream())
     return out
 
 
@@ -3176,7 +3172,7 @@ def expand_image_u8(src_u8, dst):
     """dst (fp32, same numel) = src_u8 / 255, bit-identical to torch's true division of the converted bytes"""
     assert src_u8.dtype == torch.uint8 and dst.dtype == torch.float32 and src_u8.numel() == dst.numel()
     assert src_u8.is_contiguous() and dst.is_contiguous()
-    _call("mmvae_expand_image_u8", H.ptr(src_u8), H.ptr(dst), dst.numel(), H.stream())
+    H.call("mmvae_expand_image_u8", H.ptr(src_u8), H.ptr(dst), dst.numel(), H.stream())
     return dst
 
 
@@ -3185,2306 +3181,27 @@ def expand_text_tokens(tokens, lengths, onehot, mask_u8=None):
     assert tokens.dtype == torch.int32 and lengths.dtype == torch.int32 and onehot.dtype == torch.float32
     B, T, V = onehot.shape
     assert tokens.shape == (B, T) and lengths.shape == (B,) and tokens.is_contiguous() and onehot.is_contiguous()
-    _call("mmvae_expand_text_tokens", H.ptr(tokens), H.ptr(lengths), H.ptr(onehot), H.ptr(mask_u8), B, T, V, H.stream())
+    H.call("mmvae_expand_text_tokens", H.ptr(tokens), H.ptr(lengths), H.ptr(onehot), H.ptr(mask_u8), B, T, V, H.stream())
     return onehot
 
 
 def fill(t, value):
-    _call("mmvae_fill", H.ptr(t), t.numel(), float(value), H.stream())
-
-
-# ---- held-out log-likelihood estimation (csrc/loglik.hip): forward only, no autograd ------------------------------------
-def mix_ksample_logw(comps, laplace, theta, Kc, k0=0, eps=None, rng=None, advance=True, prior_loc=None,
-                     prior_laplace=False):
-    """Stratified draws from the mixture q = (1/C) sum_c q_c and the latent part of their importance weights.
-    comps (C,B,2D) = [loc | scale], laplace: C flags, theta (1,D): the prior's scale is softmax(theta) D.
-    Draw k0 + k (k < Kc) comes from component (k0 + k) % C; its noise is eps[k] (eps (Kc,B,D)) or, with `rng` (the
-    generator state), element (k0 + k) B D + b D + d of the current draw -- `advance` bumps the state's call counter and
-    belongs to the last chunk of a draw.  -> z (Kc,B,D), lw0 (Kc,B) = log p(z) - log q(z)."""
-    comps = H.f32c(comps)
-    C, B, D2 = comps.shape
-    D = D2 // 2
-    assert len(laplace) == C and (eps is None) != (rng is None), "either eps or the generator state"
-    if eps is not None:
-        eps = H.f32c(eps)
-        assert tuple(eps.shape) == (Kc, B, D), (tuple(eps.shape), (Kc, B, D))
-    if prior_loc is not None:
-        prior_loc = H.f32c(prior_loc)
-        assert prior_loc.numel() == D
-    theta = H.f32c(theta)
-    assert theta.numel() == D
-    z = torch.empty(Kc, B, D, device=comps.device)
-    lw0 = torch.empty(Kc, B, device=comps.device)
-    mask = sum(1 << c for c, f in enumerate(laplace) if f)
-    _call("mmvae_mix_ksample_logw_fwd", H.ptr(comps), mask, H.ptr(theta), H.ptr(prior_loc), int(bool(prior_laplace)),
-          H.ptr(eps), H.ptr(rng), int(bool(advance)), H.ptr(z), H.ptr(lw0), C, int(Kc), int(k0), B, D, H.stream())
-    return z, lw0
-
-
-def lme_state(n_rows, B, device):
-    """empty streaming log-sum-exp state (1 + n_rows, 3, B) fp64: running maximum -inf, both sums 0"""
-    st = torch.zeros(1 + n_rows, 3, B, dtype=torch.float64, device=device)
-    st[:, 0] = float("-inf")
-    return st
-
-
-def lme_update(state, lw0, rows, joint_mask=None):
-    """fold one chunk into the state: row 0 takes lw0 + sum of the rows in `joint_mask` (default: all), row 1 + m takes
-    rows[m].  lw0 and every row: (Kc,B) fp32."""
-    lw0 = H.f32c(lw0)
-    Kc, B = lw0.shape
-    rows = [H.f32c(r).reshape(-1) for r in rows]
-    assert state.dtype == torch.float64 and tuple(state.shape) == (1 + len(rows), 3, B) and state.is_contiguous()
-    assert all(r.numel() == Kc * B for r in rows)
-    t = H.LmeRows()
-    for m, r in enumerate(rows):
-        t.ll[m] = r.data_ptr()
-    mask = (1 << len(rows)) - 1 if joint_mask is None else int(joint_mask)
-    _call("mmvae_lme_update", H.ptr(state), H.ptr(lw0), ctypes.byref(t), len(rows), mask, Kc, B, H.stream())
-    return state
-
-
-def lme_finish(state, K):
-    """-> (log-mean-exp over the K folded samples (1 + n_rows, B), effective sample size of row 0 (B,)), fp64"""
-    R, _, B = state.shape
-    out = torch.empty(R, B, dtype=torch.float64, device=state.device)
-    ess = torch.empty(B, dtype=torch.float64, device=state.device)
-    _call("mmvae_lme_finish", H.ptr(state), H.ptr(out), H.ptr(ess), R - 1, int(K), B, H.stream())
-    return out, ess
-
-
-# ---- host helpers of the evaluation metrics: labels, and the minibatch `order` of probe_train / digit_train -------------------
-def label_matrix(batches, what, who):
-    """labels of an iterable of (batch, labels) -> (A, N) int64 on the host; `who` names the caller in the errors"""
-    cols = []
-    for _, y in batches:
-        y = torch.as_tensor(y).detach().cpu()
-        if y.is_floating_point() or y.dim() not in (1, 2):
-            raise ValueError(f"{who}: {what} labels must be an integer (B,) or (B, A) array")
-        cols.append(y.long().reshape(y.shape[0], -1))
-    if not cols:
-        raise ValueError(f"{who}: the {what} set is empty")
-    return torch.cat(cols, 0).t().contiguous()
-
-
-def epoch_orders(N, epochs, seed, device, shuffle=True):
-    """the `order` argument of probe_train / digit_train: (epochs, N) int32 on `device`, one permutation of the N rows per
-    epoch drawn from torch.Generator(seed); None -- sequential minibatches -- when not shuffling"""
-    if not shuffle:
-        return None
-    g = torch.Generator().manual_seed(int(seed))
-    return torch.stack([torch.randperm(N, generator=g) for _ in range(int(epochs))]).to(device=device, dtype=torch.int32)
-
-
-def _check_order(who, order, N, batch, step0, n_steps, validate, check_labels):
-    """`order` of probe_train / digit_train: (E,N) contiguous int32, E epochs enough for the steps [step0, step0 + n_steps);
-    under `validate` the caller's `check_labels()`, then every entry a row in [0, N).  -> E (0: sequential, no `order`)"""
-    E = 0
-    if order is not None:
-        assert order.dim() == 2 and order.dtype == torch.int32 and order.is_contiguous() and order.shape[1] == N
-        E = order.shape[0]
-        spe = (N + batch - 1) // batch
-        if (step0 + n_steps - 1) // spe >= E:
-            raise ValueError(f"{who}: steps up to {step0 + n_steps} need more than the {E} epochs of `order`")
-    if validate:
-        check_labels()
-        if order is not None and (int(order.min()) < 0 or int(order.max()) >= N):
-            raise ValueError(f"{who}: `order` holds rows outside [0, N)")
-    return E
-
-
-# ---- latent classification (csrc/probe.hip): linear probes trained on chip, forward only, no autograd ---------------------
-def _probe_table(probes, Cmax):
-    """[(s, a, C)] -> the host (P,3) int table of the C ABI.  The class counts are checked here (ValueError names them);
-    the kernels refuse the same shapes with MMVAE_ERR_UNSUPPORTED."""
-    probes = [tuple(int(x) for x in pr) for pr in probes]
-    if not probes or len(probes) > H.PROBE_MAX_PROBES:
-        raise ValueError(f"probe table: {len(probes)} probes (1 .. {H.PROBE_MAX_PROBES} per launch)")
-    for s, a, C in probes:
-        if not 2 <= C <= min(Cmax, H.PROBE_MAX_CLASSES):
-            raise ValueError(f"probe table: {C} classes (2 .. {min(Cmax, H.PROBE_MAX_CLASSES)} are on the MI355X path)")
-    flat = [x for pr in probes for x in pr]
-    return probes, (ctypes.c_int * len(flat))(*flat)
-
-
-def _probe_dims(state, z, probes):
-    """shape contract shared by probe_train / probe_eval -> (P, S, N, D, Cmax)"""
-    assert z.dim() == 3 and z.dtype == torch.float32 and z.is_contiguous(), "z: contiguous fp32 (S,N,D)"
-    S, N, D = z.shape
-    if D > 256:
-        raise ValueError(f"probe: D = {D} latent dimensions (up to 256 are on the MI355X path)")
-    assert state.dim() == 4 and state.shape[1] == 3 and state.dtype == torch.float32 and state.is_contiguous()
-    P, Cmax = state.shape[0], state.shape[2]
-    assert state.shape[3] == D + 1 and P == len(probes), "state: (P, 3, Cmax, D + 1), one row per probe"
-    return P, S, N, D, Cmax
-
-
-def probe_check_labels(labels, probes):
-    """ValueError if a probe's label row holds a label outside [0, C) (one host synchronisation)"""
-    lo, hi = labels.amin(1).tolist(), labels.amax(1).tolist()
-    for s, a, C in probes:
-        if not 0 <= int(a) < labels.shape[0]:
-            raise ValueError(f"probe table: label row {a} of {labels.shape[0]}")
-        if lo[a] < 0 or hi[a] >= C:
-            raise ValueError(f"probe labels: row {a} holds labels in [{lo[a]}, {hi[a]}], outside [0, {C})")
-
-
-def probe_state(P, D, Cmax, device, init=None, seed=0):
-    """(P, 3, Cmax, D + 1) fp32: [parameters | exp_avg | exp_avg_sq] per probe, each a (Cmax, D + 1) matrix [W | b].
-    nn.Linear's default init -- W and b ~ U(-1/sqrt(D), 1/sqrt(D)) -- drawn on the host from torch.Generator(seed), or
-    the (W (C,D), b (C,)) pairs of `init` (rows beyond C stay 0).  The moments start at 0."""
-    P, D, Cmax = int(P), int(D), int(Cmax)
-    if D < 1 or D > 256:
-        raise ValueError(f"probe: D = {D} latent dimensions (1 .. 256 are on the MI355X path)")
-    if not 2 <= Cmax <= H.PROBE_MAX_CLASSES:
-        raise ValueError(f"probe: {Cmax} classes (2 .. {H.PROBE_MAX_CLASSES} are on the MI355X path)")
-    par = torch.zeros(P, Cmax, D + 1)
-    if init is None:
-        bound = 1.0 / D ** 0.5
-        g = torch.Generator().manual_seed(int(seed))
-        par.copy_((torch.rand(P, Cmax, D + 1, generator=g) * 2.0 - 1.0) * bound)
-    else:
-        assert len(init) == P, "init: one (W, b) pair per probe"
-        for p, (W, b) in enumerate(init):
-            C = W.shape[0]
-            assert W.shape == (C, D) and b.shape == (C,) and C <= Cmax, (tuple(W.shape), tuple(b.shape), Cmax, D)
-            par[p, :C, :D] = W.detach().float().cpu()
-            par[p, :C, D] = b.detach().float().cpu()
-    state = torch.zeros(P, 3, Cmax, D + 1)
-    state[:, 0] = par
-    return state.to(device)
-
-
-def probe_weights(state, p, C):
-    """-> (W (C,D), b (C,)) of probe p (copies)"""
-    par = state[p, 0, :C]
-    return par[:, :-1].clone(), par[:, -1].clone()
-
-
-def probe_train(state, z, labels, probes, batch, step0, n_steps, lr=1e-3, order=None, validate=True):
-    """Adam steps [step0, step0 + n_steps) of every probe in ONE launch (one workgroup per probe), in place on `state`.
-    z (S,N,D) fp32, labels (A,N) int32, probes [(s, a, C)]; step t covers positions [i batch, (i + 1) batch) of epoch
-    t // ceil(N / batch); `order` (E,N) int32 maps position -> row per epoch (None: sequential).
-    -> loss (P, n_steps): the mean cross-entropy of every step.  `validate`: check labels / order on the host first."""
-    P, S, N, D, Cmax = _probe_dims(state, z, probes)
-    probes, table = _probe_table(probes, Cmax)
-    assert labels.dim() == 2 and labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape[1] == N
-    if int(batch) < 1 or int(n_steps) < 1 or int(step0) < 0:
-        raise ValueError(f"probe_train: batch = {batch}, step0 = {step0}, n_steps = {n_steps}")
-    E = _check_order("probe_train", order, N, int(batch), int(step0), int(n_steps), validate,
-                     lambda: probe_check_labels(labels, probes))
-    for s, a, C in probes:
-        if not (0 <= s < S and 0 <= a < labels.shape[0]):
-            raise ValueError(f"probe table: probe ({s}, {a}, {C}) outside {S} latent matrices / {labels.shape[0]} label rows")
-    loss = torch.empty(P, int(n_steps), device=z.device)
-    _call("mmvae_probe_train", H.ptr(state), H.ptr(z), H.ptr(labels), H.ptr(order), E, table, H.ptr(loss), P, S,
-          labels.shape[0], N, D, Cmax, int(batch), int(step0), int(n_steps), float(lr), H.stream())
-    return loss
-
-
-def probe_eval(state, z, labels, probes):
-    """-> (pred (P,N) int32: argmax of the logits, the first maximum; nll (P,N) fp32: the row's cross-entropy against its
-    probe's label row, 0 when `labels` is None)"""
-    P, S, N, D, Cmax = _probe_dims(state, z, probes)
-    probes, table = _probe_table(probes, Cmax)
-    A = 0
-    if labels is not None:
-        assert labels.dim() == 2 and labels.dtype == torch.int32 and labels.is_contiguous() and labels.shape[1] == N
-        A = labels.shape[0]
-    for s, a, C in probes:
-        if not (0 <= s < S and (labels is None or 0 <= a < A)):
-            raise ValueError(f"probe table: probe ({s}, {a}, {C}) outside {S} latent matrices / {A} label rows")
-    pred = torch.empty(P, N, dtype=torch.int32, device=z.device)
-    nll = torch.empty(P, N, device=z.device)
-    _call("mmvae_probe_eval", H.ptr(state), H.ptr(z), H.ptr(labels), table, H.ptr(pred), H.ptr(nll), P, S, A, N, D, Cmax,
-          H.stream())
-    return pred, nll
-
-
-# ---- generation coherence (csrc/coherence.hip): scoring kernels, forward only, no autograd -------------------------------
-def text_decode_score(logits, target_ids=None, lengths=None):
-    """logits (N,T,V) fp32 -> pred (N,T) int32: the first maximum over V of every step (an all-zero row gives 0).
-    With target_ids (N,T) int32 and lengths (N,) int32 also letters (N,) int32: the steps t < min(lengths[n], T) at which
-    pred equals the target (None without targets)."""
-    assert logits.dim() == 3 and logits.dtype == torch.float32, "logits: fp32 (N,T,V)"
-    logits = logits.contiguous()
-    N, T, V = logits.shape
-    if not (1 <= T <= H.COH_MAX_STEPS and 2 <= V <= H.COH_MAX_VOCAB):
-        raise ValueError(f"text_decode_score: T = {T}, V = {V} (1 .. {H.COH_MAX_STEPS} steps, 2 .. {H.COH_MAX_VOCAB} "
-                         f"symbols are on the MI355X path)")
-    if (target_ids is None) != (lengths is None):
-        raise ValueError("text_decode_score: target_ids and lengths come together")
-    pred = torch.empty(N, T, dtype=torch.int32, device=logits.device)
-    letters = None
-    if N == 0:
-        return pred, (None if target_ids is None else torch.empty(0, dtype=torch.int32, device=logits.device))
-    if target_ids is not None:
-        assert target_ids.shape == (N, T) and target_ids.dtype == torch.int32 and target_ids.is_contiguous()
-        assert lengths.shape == (N,) and lengths.dtype == torch.int32 and lengths.is_contiguous()
-        letters = torch.empty(N, dtype=torch.int32, device=logits.device)
-    _call("mmvae_text_decode_score", H.ptr(logits), H.ptr(target_ids), H.ptr(lengths), H.ptr(pred), H.ptr(letters), N, T,
-          V, H.stream())
-    return pred, letters
-
-
-def cls_head(feats, W1, b1, W2, b2, n_classes, labels=None, want_logits=False):
-    """The heads of A attribute classifiers in one launch.  feats (A,N,512): the trunks' last conv output before its
-    ReLU; W1 (A,256,512), b1 (A,256), W2 (A,Cmax,256), b2 (A,Cmax); n_classes: A ints; labels (A,N) int32 or None
-    (-1: never correct).  -> {"pred" (A,N) int32, "logits" (A,N,Cmax) or None, "correct" (A,N) uint8 and "n_correct"
-    (N,) int32 (None without labels)}."""
-    assert feats.dim() == 3 and feats.dtype == torch.float32 and feats.is_contiguous(), "feats: contiguous fp32 (A,N,512)"
-    A, N, F_ = feats.shape
-    n_classes = [int(c) for c in n_classes]
-    Cmax = W2.shape[1]
-    if not 1 <= A <= H.COH_MAX_CLASSIFIERS or len(n_classes) != A:
-        raise ValueError(f"cls_head: {A} classifiers, {len(n_classes)} class counts (1 .. {H.COH_MAX_CLASSIFIERS} per "
-                         f"launch)")
-    if not 2 <= Cmax <= H.COH_MAX_CLASSES or any(not 2 <= c <= Cmax for c in n_classes):
-        raise ValueError(f"cls_head: class counts {n_classes} under Cmax = {Cmax} (2 .. {H.COH_MAX_CLASSES} are on the "
-                         f"MI355X path)")
-    assert F_ == H.COH_FEATS and W1.shape == (A, H.COH_HIDDEN, H.COH_FEATS) and b1.shape == (A, H.COH_HIDDEN)
-    assert W2.shape == (A, Cmax, H.COH_HIDDEN) and b2.shape == (A, Cmax)
-    for t in (W1, b1, W2, b2):
-        assert t.dtype == torch.float32 and t.is_contiguous(), "cls_head: contiguous fp32 parameters"
-    dev = feats.device
-    pred = torch.empty(A, N, dtype=torch.int32, device=dev)
-    logits = torch.empty(A, N, Cmax, device=dev) if want_logits else None
-    correct = n_correct = None
-    if labels is not None:
-        assert labels.shape == (A, N) and labels.dtype == torch.int32 and labels.is_contiguous(), "labels: int32 (A,N)"
-        correct = torch.empty(A, N, dtype=torch.uint8, device=dev)
-        n_correct = torch.empty(N, dtype=torch.int32, device=dev)
-    if N > 0:
-        _call("mmvae_cls_head", H.ptr(feats), H.ptr(W1), H.ptr(b1), H.ptr(W2), H.ptr(b2), (ctypes.c_int * A)(*n_classes),
-              H.ptr(labels), H.ptr(pred), H.ptr(logits), H.ptr(correct), H.ptr(n_correct), A, N, Cmax, H.stream())
-    return {"pred": pred, "logits": logits, "correct": correct, "n_correct": n_correct}
-
-
-# ---- MNIST-SVHN digit classifiers (csrc/digits.hip): evaluated and trained on chip, no autograd ---------------------------
-DIGIT_KINDS = {"mnist": H.DIGIT_MNIST, "svhn": H.DIGIT_SVHN}
-DIGIT_INPUT = {"mnist": (1, 28, 28), "svhn": (3, 32, 32)}
-DIGIT_N_PARAMS = {"mnist": 21840, "svhn": 31340}
-
-
-def digit_param_shapes(kind):
-    """[(state-dict key, shape)] of a digit classifier in the packed order of the C ABI (the reference's module names)"""
-    C, flat = DIGIT_INPUT[kind][0], (320 if kind == "mnist" else 500)
-    return [("conv1.weight", (10, C, 5, 5)), ("conv1.bias", (10,)), ("conv2.weight", (20, 10, 5, 5)), ("conv2.bias", (20,)),
-            ("fc1.weight", (50, flat)), ("fc1.bias", (50,)), ("fc2.weight", (10, 50)), ("fc2.bias", (10,))]
-
-
-def _digit_kinds(kinds):
-    kinds = [kinds] if isinstance(kinds, str) else list(kinds)
-    if not 1 <= len(kinds) <= H.DIGIT_MAX_NETS or any(k not in DIGIT_KINDS for k in kinds):
-        raise ValueError(f"digit classifiers: kinds = {kinds} (1 .. {H.DIGIT_MAX_NETS} of 'mnist' / 'svhn')")
-    return kinds
-
-
-def digit_default_init(kind, generator):
-    """nn.Conv2d's / nn.Linear's default init -- weight and bias ~ U(-1/sqrt(fan_in), 1/sqrt(fan_in)) -- drawn on the
-    host from `generator`, in the packed order -> {key: tensor}"""
-    out = {}
-    shapes = digit_param_shapes(kind)
-    for (kw, sw), (kb, sb) in zip(shapes[0::2], shapes[1::2]):
-        fan_in = 1
-        for s in sw[1:]:
-            fan_in *= s
-        bound = 1.0 / fan_in ** 0.5
-        out[kw] = (torch.rand(*sw, generator=generator) * 2.0 - 1.0) * bound
-        out[kb] = (torch.rand(*sb, generator=generator) * 2.0 - 1.0) * bound
-    return out
-
-
-def digit_pack(kind, params):
-    """{key: tensor} -> the packed (n_params,) fp32 host vector"""
-    parts = []
-    for k, s in digit_param_shapes(kind):
-        t = params[k].detach().float().cpu()
-        assert tuple(t.shape) == s, (k, tuple(t.shape), s)
-        parts.append(t.reshape(-1))
-    return torch.cat(parts)
-
-
-def digit_unpack(kind, vec):
-    """a packed (>= n_params,) vector -> {key: tensor} (copies, on vec's device)"""
-    out, o = {}, 0
-    for k, s in digit_param_shapes(kind):
-        n = 1
-        for d in s:
-            n *= d
-        out[k] = vec[o:o + n].reshape(s).clone()
-        o += n
-    return out
-
-
-def digit_state(kinds, device, init=None, seed=0):
-    """(nets, 3, n_params_max) fp32: [parameters | exp_avg | exp_avg_sq] per network in the packed order conv1.w, conv1.b,
-    conv2.w, conv2.b, fc1.w, fc1.b, fc2.w, fc2.b.  The init is nn.Conv2d's / nn.Linear's default, drawn on the host from
-    torch.Generator(seed) network after network, or `init`: one {state-dict key: tensor} per network.  Moments start at 0."""
-    kinds = _digit_kinds(kinds)
-    stride = max(DIGIT_N_PARAMS[k] for k in kinds)
-    state = torch.zeros(len(kinds), 3, stride)
-    g = torch.Generator().manual_seed(int(seed))
-    if init is not None:
-        assert len(init) == len(kinds), "init: one parameter dict per network"
-    for i, k in enumerate(kinds):
-        par = digit_default_init(k, g) if init is None else init[i]
-        state[i, 0, :DIGIT_N_PARAMS[k]] = digit_pack(k, par)
-    return state.to(device)
-
-
-def _digit_args(state, kinds, images, labels=None):
-    """shape contract of the digit entry points -> (kinds, host kind table, image pointer table, label pointer table, N)"""
-    kinds = _digit_kinds(kinds)
-    nets = len(kinds)
-    assert state.dim() == 3 and state.shape[:2] == (nets, 3) and state.dtype == torch.float32 and state.is_contiguous(), \
-        "state: contiguous fp32 (nets, 3, n_params_max)"
-    assert state.shape[2] >= max(DIGIT_N_PARAMS[k] for k in kinds), "state: narrower than the largest network"
-    assert len(images) == nets, "images: one (N,C,H,W) tensor per network"
-    N = images[0].shape[0]
-    for k, x in zip(kinds, images):
-        assert x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (N,) + DIGIT_INPUT[k], \
-            f"{k} images: contiguous fp32 (N,{','.join(map(str, DIGIT_INPUT[k]))}), got {tuple(x.shape)}"
-    lab = None
-    if labels is not None:
-        assert len(labels) == nets, "labels: one (N,) int32 tensor per network"
-        for y in labels:
-            assert y.dtype == torch.int32 and y.is_contiguous() and tuple(y.shape) == (N,), "labels: contiguous int32 (N,)"
-        lab = (H.c_p * nets)(*[H.ptr(y) for y in labels])
-    return kinds, (ctypes.c_int * nets)(*[DIGIT_KINDS[k] for k in kinds]), (H.c_p * nets)(*[H.ptr(x) for x in images]), lab, N
-
-
-def digit_check_labels(labels):
-    """ValueError if a label lies outside [0, 10) (one host synchronisation per tensor)"""
-    for y in labels:
-        lo, hi = int(y.min()), int(y.max())
-        if lo < 0 or hi >= 10:
-            raise ValueError(f"digit classifiers: labels in [{lo}, {hi}], outside [0, 10)")
-
-
-def _digit_p(p):
-    p = float(p)
-    if not 0.0 <= p < 1.0:
-        raise ValueError(f"digit classifiers: dropout p = {p} (0 <= p < 1)")
-    return p
-
-
-def digit_eval(state, kinds, images):
-    """-> (logp (nets,N,10) fp32 log-probabilities, pred (nets,N) int32: their first maximum); dropout off"""
-    kinds, ktab, xtab, _, N = _digit_args(state, kinds, images)
-    dev = state.device
-    logp = torch.empty(len(kinds), N, 10, device=dev)
-    pred = torch.empty(len(kinds), N, dtype=torch.int32, device=dev)
-    if N > 0:
-        _call("mmvae_digit_eval", H.ptr(state), ktab, xtab, H.ptr(logp), H.ptr(pred), len(kinds), state.shape[2], N,
-              H.stream())
-    return logp, pred
-
-
-def digit_grad(state, kinds, images, labels, seed=0, step=0, p=0.0, validate=True):
-    """The first half of a training step on one minibatch (all N rows of `images`): -> (grad (nets, n_params_max): the
-    gradient of the mean loss with the dropout masks of (seed, step), rowloss (nets,N) = -logp[label])"""
-    kinds, ktab, xtab, ltab, N = _digit_args(state, kinds, images, labels)
-    if not 1 <= N <= 65535:
-        raise ValueError(f"digit_grad: a minibatch of {N} rows (1 .. 65535)")
-    if validate:
-        digit_check_labels(labels)
-    nets, stride, dev = len(kinds), state.shape[2], state.device
-    ws = H.workspace(H.lib().mmvae_digit_ws_floats(nets, N, stride), dev)
-    grad = torch.zeros(nets, stride, device=dev)
-    rowloss = torch.empty(nets, N, device=dev)
-    _call("mmvae_digit_grad", H.ptr(state), ktab, xtab, ltab, H.ptr(ws), H.ptr(grad), H.ptr(rowloss), nets, stride, N,
-          int(seed) & 0xFFFFFFFF, int(step), _digit_p(p), H.stream())
-    return grad, rowloss
-
-
-def digit_train(state, kinds, images, labels, batch, step0, n_steps, lr=1e-3, seed=0, p=0.5, order=None, validate=True):
-    """Adam steps [step0, step0 + n_steps) of every network, in place on `state`: forward with dropout, backward, Adam;
-    two launches per step.  images: per network (N,C,H,W) fp32 on the device, labels: per network (N,) int32; the
-    minibatch schedule and `order` (E,N) int32 are ops.probe_train's.  -> loss (nets, n_steps)."""
-    kinds, ktab, xtab, ltab, N = _digit_args(state, kinds, images, labels)
-    batch, step0, n_steps = int(batch), int(step0), int(n_steps)
-    if not 1 <= batch <= 65535 or n_steps < 1 or step0 < 0 or N < 1:
-        raise ValueError(f"digit_train: batch = {batch}, step0 = {step0}, n_steps = {n_steps}, N = {N}")
-    E = _check_order("digit_train", order, N, batch, step0, n_steps, validate, lambda: digit_check_labels(labels))
-    nets, stride, dev = len(kinds), state.shape[2], state.device
-    ws = H.workspace(H.lib().mmvae_digit_ws_floats(nets, batch, stride), dev)
-    loss = torch.empty(nets, n_steps, device=dev)
-    _call("mmvae_digit_train", H.ptr(state), ktab, xtab, ltab, H.ptr(order), E, H.ptr(ws), H.ptr(loss), nets, stride, N,
-          batch, step0, n_steps, float(lr), int(seed) & 0xFFFFFFFF, _digit_p(p), H.stream())
-    return loss
-
-
-def digit_masks(kind, batch, step0, n_steps, seed=0, p=0.5, device="cuda"):
-    """The masks digit_train / digit_grad use for the steps [step0, step0 + n_steps) of a network kind, as 0 or 1/(1-p)
-    floats -> (Dropout2d mask (n_steps, batch, 20), dropout mask (n_steps, batch, 50))"""
-    (kind,) = _digit_kinds(kind)
-    batch, n_steps = int(batch), int(n_steps)
-    if not 1 <= batch <= 65535 or n_steps < 1 or int(step0) < 0:
-        raise ValueError(f"digit_masks: batch = {batch}, step0 = {step0}, n_steps = {n_steps}")
-    m2d = torch.empty(n_steps, batch, 20, device=device)
-    m1 = torch.empty(n_steps, batch, 50, device=device)
-    _call("mmvae_digit_masks", H.ptr(m2d), H.ptr(m1), DIGIT_KINDS[kind], int(seed) & 0xFFFFFFFF, int(step0), n_steps,
-          batch, _digit_p(p), H.stream())
-    return m2d, m1
-
-
-# ---- latent analysis (csrc/tsne.hip): exact t-SNE, forward only, no autograd ------------------------------------------------
-TSNE_SWITCH_IT = 250      # iterations with early exaggeration 12 and momentum 0.5 (scikit-learn's _EXPLORATION_MAX_ITER)
-TSNE_CHECK_EVERY = 50     # iterations per enqueued call and between two looks at the log (its _N_ITER_CHECK)
-
-
-def _tsne_points(who, X):
-    assert X.dim() == 2 and X.dtype == torch.float32, f"{who}: fp32 (N, D)"
-    N, D = X.shape
-    if not H.TSNE_MIN_POINTS <= N <= H.TSNE_MAX_POINTS or not 1 <= D <= H.TSNE_MAX_DIM:
-        raise ValueError(f"{who}: N = {N} points of D = {D} dimensions ({H.TSNE_MIN_POINTS} .. {H.TSNE_MAX_POINTS} points "
-                         f"of 1 .. {H.TSNE_MAX_DIM} dimensions are on the MI355X path)")
-    return N, D
-
-
-def tsne_sqdist(X):
-    """X (N,D) fp32 -> D2 (N,N) fp32: the squared Euclidean distances, every one summed directly in double and rounded
-    (no Gram trick: near-duplicates do not cancel); zero diagonal, symmetric bit for bit."""
-    N, D = _tsne_points("tsne_sqdist", X)
-    X = X.contiguous()
-    D2 = torch.empty(N, N, device=X.device)
-    _call("mmvae_tsne_sqdist", H.ptr(X), H.ptr(D2), N, D, H.stream())
-    return D2
-
-
-def tsne_default_init(N, seed=123):
-    """scikit-learn's init="random": 1e-4 * RandomState(seed).standard_normal((N, 2)) as float32 (a host tensor)"""
-    return torch.from_numpy((1e-4 * np.random.RandomState(int(seed)).standard_normal((int(N), 2))).astype(np.float32))
-
-
-def tsne_check_perplexity(perplexity, N):
-    if not float(perplexity) > 0.0:
-        raise ValueError(f"perplexity must be positive, got {perplexity}")
-    if float(perplexity) >= N:
-        raise ValueError("perplexity must be less than n_samples")
-
-
-def tsne_joint_probabilities(X, perplexity, sqdist=None, details=False):
-    """-> (P (N,N) fp32, beta (N,) float64): scikit-learn's _joint_probabilities of the squared distances of X (or of
-    `sqdist` (N,N) fp32 as given) -- per row the binary search for the precision beta that gives the conditional
-    distribution the entropy log(perplexity), in double; P = max((C + C^T) / sum, eps) off the diagonal, 0 on it,
-    symmetric bit for bit.  P is a view of rows padded to a multiple of 4 columns, the layout the iteration kernels read.
-    `details`: also {"s", "rowsum", "steps"} of the search, (N,) float64 each."""
-    D2 = tsne_sqdist(X) if sqdist is None else sqdist.contiguous()
-    assert D2.dim() == 2 and D2.shape[0] == D2.shape[1] and D2.dtype == torch.float32, "sqdist: fp32 (N,N)"
-    N = D2.shape[0]
-    if not H.TSNE_MIN_POINTS <= N <= H.TSNE_MAX_POINTS:
-        raise ValueError(f"tsne_joint_probabilities: N = {N} points ({H.TSNE_MIN_POINTS} .. {H.TSNE_MAX_POINTS} are on the "
-                         f"MI355X path)")
-    tsne_check_perplexity(perplexity, N)
-    ld = H.lib().mmvae_tsne_ld(N)
-    store = torch.empty(N, ld, device=D2.device)
-    info = torch.empty(N, 4, dtype=torch.float64, device=D2.device)
-    total = torch.empty(1, dtype=torch.float64, device=D2.device)
-    _call("mmvae_tsne_joint_p", H.ptr(D2), float(perplexity), H.ptr(store), ld, H.ptr(info), H.ptr(total), N, H.stream())
-    P = store[:, :N]
-    if details:
-        return P, info[:, 0].clone(), {"s": info[:, 1].clone(), "rowsum": info[:, 2].clone(), "steps": info[:, 3].clone()}
-    return P, info[:, 0].clone()
-
-
-def _tsne_padded(P):
-    """P (N,N) fp32 as the kernels read it: unit column stride, a row stride of N rounded up to 4 (16-byte rows) -- the
-    view tsne_joint_probabilities returns as it is, anything else copied into that layout"""
-    assert P.dim() == 2 and P.shape[0] == P.shape[1] and P.dtype == torch.float32, "P: fp32 (N,N)"
-    N = P.shape[0]
-    ld = (N + 3) & ~3
-    if P.stride(1) == 1 and P.stride(0) == ld and P.data_ptr() % 16 == 0:
-        return P, ld
-    store = torch.zeros(N, ld, device=P.device)
-    store[:, :N] = P
-    return store[:, :N], ld
-
-
-def tsne_state(Y0):
-    """Y0 (N,2) -> the iteration's state (3,N,2) fp32 on the device Y0 is on: Y | upd = 0 | gains = 1"""
-    assert Y0.dim() == 2 and Y0.shape[1] == 2, "Y0: (N,2)"
-    Y0 = Y0.detach().float()
-    return torch.stack([Y0, torch.zeros_like(Y0), torch.ones_like(Y0)]).contiguous()
-
-
-def _tsne_args(who, state, P):
-    assert state.dim() == 3 and state.shape[0] == 3 and state.shape[2] == 2 and state.dtype == torch.float32 \
-        and state.is_contiguous(), "state: contiguous fp32 (3,N,2) from tsne_state"
-    N = state.shape[1]
-    if not H.TSNE_MIN_POINTS <= N <= H.TSNE_MAX_POINTS:
-        raise ValueError(f"{who}: N = {N} points ({H.TSNE_MIN_POINTS} .. {H.TSNE_MAX_POINTS} are on the MI355X path)")
-    assert P.shape[0] == N, f"{who}: P is {tuple(P.shape)}, the state holds {N} points"
-    P, ld = _tsne_padded(P)
-    ws = torch.empty(H.lib().mmvae_tsne_ws_doubles(N), dtype=torch.float64, device=state.device)
-    return N, P, ld, ws
-
-
-def tsne_forces(state, P, it, switch_it=TSNE_SWITCH_IT):
-    """The first half of iteration `it` (exaggeration 12 for it < switch_it, then 1), the state untouched
-    -> (g (N,2) fp32: the gradient of the objective, KL, Z: 0-d float64 tensors on the device)."""
-    N, P, ld, ws = _tsne_args("tsne_forces", state, P)
-    g = torch.empty(N, 2, device=state.device)
-    kz = torch.empty(2, dtype=torch.float64, device=state.device)
-    _call("mmvae_tsne_forces", H.ptr(state), H.ptr(P), ld, H.ptr(ws), H.ptr(g), H.ptr(kz), N, int(it), int(switch_it),
-          H.stream())
-    return g, kz[0], kz[1]
-
-
-def tsne_default_lr(N):
-    """scikit-learn's learning_rate="auto": max(N / early_exaggeration / 4, 50)"""
-    return max(N / 12.0 / 4.0, 50.0)
-
-
-def tsne_run(state, P, it0, n_iter, lr, switch_it=TSNE_SWITCH_IT, kl_every=1):
-    """The iterations [it0, it0 + n_iter) in place on `state`, enqueued in one call (two launches per iteration, no host
-    synchronisation) -> log (n_iter,2) float64 on the device: (KL with the iteration's exaggeration, |g|_2) at the
-    embedding each iteration started from.  `kl_every`: KL is computed in the iterations with (it + 1) % kl_every == 0,
-    NaN elsewhere (scikit-learn computes it every 50th; its double logarithms are most of a pair's arithmetic).
-    Bit-identical from run to run and however the iterations are split over calls."""
-    N, P, ld, ws = _tsne_args("tsne_run", state, P)
-    if int(n_iter) < 1 or int(it0) < 0 or not float(lr) > 0.0 or int(kl_every) < 1:
-        raise ValueError(f"tsne_run: it0 = {it0}, n_iter = {n_iter}, lr = {lr}, kl_every = {kl_every}")
-    log = torch.empty(int(n_iter), 2, dtype=torch.float64, device=state.device)
-    _call("mmvae_tsne_run", H.ptr(state), H.ptr(P), ld, H.ptr(ws), H.ptr(log), N, int(it0), int(n_iter), int(switch_it),
-          float(lr), int(kl_every), H.stream())
-    return log
-
-
-def tsne_embed(X, perplexity=30.0, max_iter=1000, seed=123, init=None, lr="auto", n_iter_without_progress=300,
-               min_grad_norm=1e-7, kl_every=TSNE_CHECK_EVERY):
-    """Exact t-SNE of X (N,D) fp32 into two dimensions: sklearn.manifold.TSNE(n_components=2, method="exact",
-    init="random", random_state=seed, learning_rate="auto") -- 250 iterations with early exaggeration 12 and momentum 0.5,
-    then momentum 0.8 up to `max_iter`, with scikit-learn's stopping rule: every 50th iteration a stage ends when the
-    objective has had no new best for more than `n_iter_without_progress` iterations (250 in the first stage) or when
-    |g|_2 <= min_grad_norm.  (scikit-learn takes the norm of the gradient scaled by the gains; here it is the gradient's.)
-    `init`: (N,2) instead of the seeded draw.  The host enqueues 50 iterations per call and reads the log back once per
-    call: at most max_iter / 50 synchronisations.
-    -> {"embedding": (N,2) fp32, "kl_divergence": float, the objective at the returned embedding without exaggeration,
-        "n_iter": iterations run, "log": (n_iter,2) float64 (KL, |g|) per iteration (KL every `kl_every`-th, NaN between),
-        "beta": (N,) float64 precisions of the perplexity search}."""
-    N, _ = _tsne_points("tsne_embed", X)
-    tsne_check_perplexity(perplexity, N)
-    max_iter = int(max_iter)
-    if max_iter < TSNE_SWITCH_IT:
-        raise ValueError(f"tsne_embed: max_iter = {max_iter} (at least the {TSNE_SWITCH_IT} iterations of the first stage)")
-    if TSNE_CHECK_EVERY % int(kl_every) != 0:
-        raise ValueError(f"tsne_embed: kl_every = {kl_every} must divide the check cadence {TSNE_CHECK_EVERY}")
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError("tsne_embed: X holds values that are not finite")
-    lr = tsne_default_lr(N) if isinstance(lr, str) else float(lr)
-    P, beta = tsne_joint_probabilities(X, perplexity)
-    Y0 = tsne_default_init(N, seed) if init is None else torch.as_tensor(init)
-    if tuple(Y0.shape) != (N, 2):
-        raise ValueError(f"tsne_embed: init is {tuple(Y0.shape)}, not ({N}, 2)")
-    state = tsne_state(Y0.to(X.device))
-    logs, it, switch_it = [], 0, TSNE_SWITCH_IT
-    for stage_end, patience in ((TSNE_SWITCH_IT, TSNE_SWITCH_IT), (max_iter, int(n_iter_without_progress))):
-        best, best_it, stop = float("inf"), it, False
-        while it < stage_end and not stop:
-            n = min(TSNE_CHECK_EVERY - it % TSNE_CHECK_EVERY, stage_end - it)
-            log = tsne_run(state, P, it, n, lr, switch_it=switch_it, kl_every=kl_every)
-            logs.append(log)
-            it += n
-            if it % TSNE_CHECK_EVERY == 0:
-                kl, gnorm = log[-1].tolist()      # (the synchronisation of this call)
-                if kl < best:
-                    best, best_it = kl, it - 1
-                elif it - 1 - best_it > patience:
-                    stop = True
-                if gnorm <= float(min_grad_norm):
-                    stop = True
-        switch_it = min(switch_it, it)
-    _, kl, _ = tsne_forces(state, P, max(it, switch_it), switch_it=switch_it)
-    return {"embedding": state[0].clone(), "kl_divergence": float(kl), "n_iter": it, "log": torch.cat(logs),
-            "beta": beta}
-
-
-# ---- checks shared by the feature-set metrics (Frechet, manifold, KID) and the chunked kernels --------------------------------
-def _feature_rows(who, what, X, least=1, most=None, why="", finite=True):
-    """contiguous fp32 (rows, F) or ValueError: shape, dtype, the limit on F, `least` .. `most` rows (`why`: the caller's
-    clause on that limit), finite values (`finite` False: the caller checks them after its own comparisons)"""
-    if not torch.is_tensor(X) or X.dim() != 2 or not X.is_floating_point():
-        said = f"{tuple(X.shape)}, {X.dtype}" if torch.is_tensor(X) else type(X).__name__
-        raise ValueError(f"{who}: {what} is {said}; floating (rows, F) features")
-    rows, F = X.shape
-    if not 1 <= F <= H.FRECHET_MAX_F:
-        raise ValueError(f"{who}: {what} has F = {F} features (1 .. {H.FRECHET_MAX_F} are on the MI355X path)")
-    if rows < least or (most is not None and rows > most):
-        raise ValueError(f"{who}: {what} has {rows} rows ({why})")
-    X = H.f32c(X.detach())
-    if finite:
-        _finite(who, what, X)
-    return X
-
-
-def _finite(who, what, X):
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError(f"{who}: {what} holds values that are not finite")
-
-
-def _chunks(who, chunks, what="column chunks"):
-    chunks = int(chunks)
-    if chunks < 0:
-        raise ValueError(f"{who}: chunks = {chunks} (0: the default plan, or a positive number of {what})")
-    return chunks
-
-
-# ---- Frechet distance of feature sets (csrc/frechet.hip): float64, forward only, no autograd --------------------------------
-def _frechet_f(who, F):
-    F = int(F)
-    if not 1 <= F <= H.FRECHET_MAX_F:
-        raise ValueError(f"{who}: F = {F} features (1 .. {H.FRECHET_MAX_F} are on the MI355X path)")
-    return F
-
-
-def _frechet_state_f(who, state):
-    """F of a moment state, or ValueError: the contiguous float64 vector (1 + F + F F,) that frechet_state returns"""
-    ok = torch.is_tensor(state) and state.dim() == 1 and state.dtype == torch.float64 and state.is_contiguous()
-    F = (math.isqrt(max(4 * state.numel() - 3, 0)) - 1) // 2 if ok else 0
-    if not ok or 1 + F + F * F != state.numel() or not 1 <= F <= H.FRECHET_MAX_F:
-        what = f"{tuple(state.shape)}, {state.dtype}" if torch.is_tensor(state) else type(state).__name__
-        raise ValueError(f"{who}: the state is {what}; frechet_state gives a contiguous float64 vector (1 + F + F F,), "
-                         f"1 <= F <= {H.FRECHET_MAX_F} on the MI355X path")
-    return F
-
-
-def frechet_state(F, device):
-    """empty streaming moment state, float64 (1 + F + F F,): n | mean (F) | M2 (F,F), all 0"""
-    F = _frechet_f("frechet_state", F)
-    return torch.zeros(1 + F + F * F, dtype=torch.float64, device=device)
-
-
-def frechet_update(state, feats):
-    """fold the rows of feats (n_b, F) into the state: batch mean and centred scatter in double (one tiled SYRK on the
-    fp64 MFMA), merged by Chan's rule.  Memory does not grow with the number of rows folded."""
-    F = _frechet_state_f("frechet_update", state)
-    feats = _feature_rows("frechet_update", "feats", feats, least=0, finite=False)
-    if feats.shape[1] != F:
-        raise ValueError(f"frechet_update: feats has F = {feats.shape[1]} features; the state holds floating (rows, {F})")
-    if feats.shape[0] == 0:
-        return state
-    _finite("frechet_update", "feats", feats)
-    ws = torch.empty(F, dtype=torch.float64, device=state.device)
-    _call("mmvae_frechet_update", H.ptr(state), H.ptr(feats), H.ptr(ws), feats.shape[0], F, H.stream())
-    return state
-
-
-def frechet_moments(state):
-    """-> (n, mu (F,) float64, sigma (F,F) float64 = M2 / (n - 1): np.cov's normalisation, n >= 2)"""
-    F = _frechet_state_f("frechet_moments", state)
-    n = int(state[0])
-    if n < 2:
-        raise ValueError(f"frechet_moments: n = {n} rows folded (a covariance needs n >= 2)")
-    mu = torch.empty(F, dtype=torch.float64, device=state.device)
-    sigma = torch.empty(F, F, dtype=torch.float64, device=state.device)
-    _call("mmvae_frechet_finish", H.ptr(state), H.ptr(mu), H.ptr(sigma), n, F, H.stream())
-    return n, mu, sigma
-
-
-def _f64_square(who, what, M):
-    if M.dim() != 2 or M.shape[0] != M.shape[1] or M.dtype != torch.float64:
-        raise ValueError(f"{who}: {what} of shape {tuple(M.shape)}, {M.dtype}; float64 (F,F), 1 <= F <= {H.FRECHET_MAX_F} on "
-                         f"the MI355X path")
-    _frechet_f(who, M.shape[0])
-    return M.contiguous()
-
-
-def f64_gemm(A, B, trans_b=False):
-    """C = A B (or A B^T) of row-major float64 (F,F) matrices on the fp64 MFMA tile routine"""
-    A, B = _f64_square("f64_gemm", "A", A), _f64_square("f64_gemm", "B", B)
-    if A.shape != B.shape:
-        raise ValueError(f"f64_gemm: A {tuple(A.shape)} and B {tuple(B.shape)} differ")
-    C = torch.empty_like(A)
-    _call("mmvae_f64_gemm", H.ptr(A), H.ptr(B), H.ptr(C), A.shape[0], int(bool(trans_b)), H.stream())
-    return C
-
-
-def sym_eig(S, vectors=True, max_sweeps=H.EIG_MAX_SWEEPS):
-    """One-sided Jacobi of the symmetric float64 S (F,F) in round-robin order, one launch per step (include/mmvae_hip.h:
-    mmvae_sym_eig) -> {"values": (F,) = |A_j|, the eigenvalues of a positive semi-definite S, unsorted, "vectors": (F,F)
-    with column j the eigenvector of values[j] (None for vectors=False: the same values bit for bit), "sweeps": int,
-    "rotations": [counted rotations per sweep]}.  The host reads one integer per sweep.  RuntimeError when the sweeps reach
-    `max_sweeps` (at most 30) without converging."""
-    S = _f64_square("sym_eig", "S", S)
-    F, max_sweeps = S.shape[0], int(max_sweeps)
-    if not 1 <= max_sweeps <= H.EIG_MAX_SWEEPS:
-        raise ValueError(f"sym_eig: max_sweeps = {max_sweeps} (1 .. {H.EIG_MAX_SWEEPS})")
-    if not bool(torch.isfinite(S).all()):
-        raise ValueError("sym_eig: S holds values that are not finite")
-    dev = S.device
-    ws = torch.empty(H.lib().mmvae_sym_eig_ws_doubles(F), dtype=torch.float64, device=dev)
-    Vc = torch.empty(F, F, dtype=torch.float64, device=dev) if vectors else None
-    values = torch.empty(F, dtype=torch.float64, device=dev)
-    sweeps, rot = ctypes.c_int(0), (ctypes.c_int * max_sweeps)()
-    _call("mmvae_sym_eig", H.ptr(S), H.ptr(ws), H.ptr(Vc), H.ptr(values), ctypes.byref(sweeps), rot, F, max_sweeps,
-          H.stream())
-    return {"values": values, "vectors": None if Vc is None else Vc.t(), "sweeps": sweeps.value,
-            "rotations": list(rot[:sweeps.value])}
-
-
-def frechet_distance(mu1, sigma1, mu2, sigma2):
-    """d^2 = |mu1 - mu2|^2 + tr S1 + tr S2 - 2 tr (S1 S2)^1/2 of float64 moments on the device, the square root through two
-    symmetric eigendecompositions: (lambda, V) of S1, R = diag(sqrt(lambda)) V^T, G = R S2 R^T, tr (S1 S2)^1/2 = sum_j
-    sqrt(sigma_j(G)).  -> {"distance": float64 0-d tensor, "tr_covmean": float64 0-d tensor, "sweeps": (s1, s2)}."""
-    sigma1, sigma2 = _f64_square("frechet_distance", "sigma1", sigma1), _f64_square("frechet_distance", "sigma2", sigma2)
-    F = sigma1.shape[0]
-    for what, t, shape in (("mu1", mu1, (F,)), ("mu2", mu2, (F,)), ("sigma2", sigma2, (F, F))):
-        if tuple(t.shape) != shape or t.dtype != torch.float64:
-            raise ValueError(f"frechet_distance: {what} of shape {tuple(t.shape)}, {t.dtype}; float64 {shape} beside sigma1 "
-                             f"(1 .. {H.FRECHET_MAX_F} features are on the MI355X path)")
-    mu1, mu2 = mu1.contiguous(), mu2.contiguous()
-    if not all(bool(torch.isfinite(t).all()) for t in (mu1, mu2, sigma1, sigma2)):
-        raise ValueError("frechet_distance: the moments hold values that are not finite")
-    dev = sigma1.device
-    ws = torch.empty(H.lib().mmvae_frechet_ws_doubles(F), dtype=torch.float64, device=dev)
-    out = torch.empty(5, dtype=torch.float64, device=dev)
-    sweeps = (ctypes.c_int * 2)()
-    _call("mmvae_frechet_distance", H.ptr(mu1), H.ptr(sigma1), H.ptr(mu2), H.ptr(sigma2), H.ptr(ws), H.ptr(out), sweeps, F,
-          H.stream())
-    return {"distance": out[0], "tr_covmean": out[1], "sweeps": (sweeps[0], sweeps[1])}
-
-
-# ---- k-nearest-neighbour manifold estimates of feature sets (csrc/manifold.hip): float64 distances, forward only ------------
-def _manifold_k(who, k):
-    k = int(k)
-    if not 1 <= k <= H.MANIFOLD_MAX_K:
-        raise ValueError(f"{who}: k = {k} neighbours (1 .. {H.MANIFOLD_MAX_K} are on the MI355X path)")
-    return k
-
-
-def _manifold_rows(who, what, X, least=1):
-    return _feature_rows(who, what, X, least, H.MANIFOLD_MAX_ROWS, f"{least} .. {H.MANIFOLD_MAX_ROWS} are on the MI355X "
-                                                                     f"path; the k-th neighbour needs k + 1 rows")
-
-
-def _manifold_sqnorms(X):
-    n2 = torch.empty(X.shape[0], dtype=torch.float64, device=X.device)
-    _call("mmvae_manifold_sqnorms", H.ptr(X), H.ptr(n2), X.shape[0], X.shape[1], H.stream())
-    return n2
-
-
-def _manifold_radii(X, n2, k, chunks):
-    N, F = X.shape
-    ws = torch.empty(H.lib().mmvae_manifold_ws_doubles(N, N, k, chunks), dtype=torch.float64, device=X.device)
-    rad2 = torch.empty(N, dtype=torch.float64, device=X.device)
-    _call("mmvae_manifold_radii", H.ptr(X), H.ptr(n2), H.ptr(ws), H.ptr(rad2), N, F, k, chunks, H.stream())
-    return rad2
-
-
-def _manifold_cross(B, nb, A, na, rad2, chunks):
-    (Nb, F), Na = B.shape, A.shape[0]
-    ws = torch.empty(H.lib().mmvae_manifold_ws_doubles(Nb, Na, 1, chunks), dtype=torch.float64, device=B.device)
-    count = torch.empty(Nb, dtype=torch.int32, device=B.device)
-    mind2 = torch.empty(Nb, dtype=torch.float64, device=B.device)
-    _call("mmvae_manifold_cross", H.ptr(B), H.ptr(nb), H.ptr(A), H.ptr(na), H.ptr(rad2), H.ptr(ws), H.ptr(count),
-          H.ptr(mind2), Nb, Na, F, chunks, H.stream())
-    return count, mind2
-
-
-def manifold_sqnorms(X):
-    """-> (N,) float64: |x_i|^2 of the fp32 rows, summed in double in feature order"""
-    return _manifold_sqnorms(_manifold_rows("manifold_sqnorms", "X", X))
-
-
-def manifold_radii(X, k, chunks=0):
-    """-> (N,) float64: rad^2[i] = the k-th smallest squared distance from row i of X (N,F) to the other rows, the row itself
-    left out by index (a duplicate row is a neighbour at distance 0).  d^2 = max(0, (|x|^2 + |y|^2) - 2 x . y) in double, the
-    Gram product on the fp64 MFMA; the N x N matrix is never written.  `chunks`: how many workgroups share a row's columns
-    (0: the default plan); the result does not depend on it, bit for bit."""
-    k, chunks = _manifold_k("manifold_radii", k), _chunks("manifold_radii", chunks)
-    X = _manifold_rows("manifold_radii", "X", X, least=k + 1)
-    return _manifold_radii(X, _manifold_sqnorms(X), k, chunks)
-
-
-def _manifold_rad2(who, rad2, A):
-    if not torch.is_tensor(rad2) or tuple(rad2.shape) != (A.shape[0],) or rad2.dtype != torch.float64:
-        said = f"{tuple(rad2.shape)}, {rad2.dtype}" if torch.is_tensor(rad2) else type(rad2).__name__
-        raise ValueError(f"{who}: rad2 is {said}; float64 ({A.shape[0]},), one squared radius per manifold row")
-    if rad2.device != A.device:
-        raise ValueError(f"{who}: rad2 is on {rad2.device}, the manifold rows on {A.device}")
-    rad2 = rad2.detach().contiguous()
-    if bool(torch.isnan(rad2).any()):
-        raise ValueError(f"{who}: rad2 holds NaN")
-    return rad2
-
-
-def manifold_cross(queries, manifold, rad2, chunks=0):
-    """query rows (Nq,F) against manifold rows (Na,F) with their squared radii rad2 (Na,) float64
-    -> (count (Nq,) int32 = the number of manifold rows whose sphere holds the query, d^2 <= rad^2: a point on a sphere is
-        inside; mind2 (Nq,) float64 = the query's smallest squared distance to the manifold rows)."""
-    chunks = _chunks("manifold_cross", chunks)
-    B = _manifold_rows("manifold_cross", "queries", queries)
-    A = _manifold_rows("manifold_cross", "manifold", manifold)
-    if A.shape[1] != B.shape[1]:
-        raise ValueError(f"manifold_cross: queries have F = {B.shape[1]} features, the manifold F = {A.shape[1]}")
-    if A.device != B.device:
-        raise ValueError(f"manifold_cross: the queries are on {B.device}, the manifold rows on {A.device}")
-    rad2 = _manifold_rad2("manifold_cross", rad2, A)
-    return _manifold_cross(B, _manifold_sqnorms(B), A, _manifold_sqnorms(A), rad2, chunks)
-
-
-def manifold_prdc(real, fake, k=5, chunks=0):
-    """Improved precision and recall (Kynkaanniemi et al. 2019), density and coverage (Naeem et al. 2020) of generated
-    feature rows `fake` (M,F) against `real` (N,F), k-nearest-neighbour spheres, `<=` throughout:
-      rad2_real, rad2_fake   manifold_radii of each set;
-      hit_real[j]  = #{i : d^2(fake_j, real_i) <= rad2_real[i]},  hit_fake[i] = #{j : d^2(real_i, fake_j) <= rad2_fake[j]},
-      near_real[i] = min_j d^2(real_i, fake_j);
-      precision = mean_j [hit_real[j] > 0], recall = mean_i [hit_fake[i] > 0], density = sum_j hit_real[j] / (k M),
-      coverage = mean_i [near_real[i] <= rad2_real[i]].
-    -> the four as floats (quotients of integer sums: exact counts) and the five per-row tensors on the device."""
-    k, chunks = _manifold_k("manifold_prdc", k), _chunks("manifold_prdc", chunks)
-    R = _manifold_rows("manifold_prdc", "real", real, least=k + 1)
-    G = _manifold_rows("manifold_prdc", "fake", fake, least=k + 1)
-    if R.shape[1] != G.shape[1]:
-        raise ValueError(f"manifold_prdc: real has F = {R.shape[1]} features, fake F = {G.shape[1]}")
-    if R.device != G.device:
-        raise ValueError(f"manifold_prdc: real is on {R.device}, fake on {G.device}")
-    nr, ng = _manifold_sqnorms(R), _manifold_sqnorms(G)
-    rad_r, rad_g = _manifold_radii(R, nr, k, chunks), _manifold_radii(G, ng, k, chunks)
-    hit_r, _ = _manifold_cross(G, ng, R, nr, rad_r, chunks)
-    hit_g, near_r = _manifold_cross(R, nr, G, ng, rad_g, chunks)
-    N, M = R.shape[0], G.shape[0]
-    return {"precision": int((hit_r > 0).sum()) / M, "recall": int((hit_g > 0).sum()) / N,
-            "density": int(hit_r.sum(dtype=torch.int64)) / (k * M), "coverage": int((near_r <= rad_r).sum()) / N,
-            "hit_real": hit_r, "hit_fake": hit_g, "near_real": near_r, "rad2_real": rad_r, "rad2_fake": rad_g}
-
-
-# ---- kernel inception distance of feature sets (csrc/kid.hip): float64 sums of polynomial kernel values, forward only -------
-def _kid_index(who, what, idx, rows, device):
-    """contiguous int32 (S, m) on `device` or ValueError: an integer (S, m) tensor inside the limits, every entry in
-    [0, rows) -- one min/max read on the device, before any C call: the kernel does not check"""
-    if not torch.is_tensor(idx) or idx.dim() != 2 or idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
-        said = f"{tuple(idx.shape)}, {idx.dtype}" if torch.is_tensor(idx) else type(idx).__name__
-        raise ValueError(f"{who}: {what} is {said}; an integer (S, m) tensor, one row of row numbers per subset")
-    S, m = idx.shape
-    if not 1 <= S <= H.KID_MAX_SUBSETS or not 2 <= m <= H.KID_MAX_SUBSET:
-        raise ValueError(f"{who}: {what} is {S} subsets of m = {m} rows (1 .. {H.KID_MAX_SUBSETS} subsets of 2 .. "
-                         f"{H.KID_MAX_SUBSET} rows are on the MI355X path)")
-    if idx.device != device:
-        raise ValueError(f"{who}: {what} is on {idx.device}, the features on {device}")
-    idx = idx.detach()
-    lo, hi = (int(v) for v in torch.aminmax(idx))
-    if lo < 0 or hi >= rows:
-        raise ValueError(f"{who}: {what} holds row numbers from {lo} to {hi}; the set has the rows 0 .. {rows - 1}")
-    return idx.to(torch.int32).contiguous()
-
-
-def _kid_kernel(who, F, degree, gamma, coef0, chunks):
-    degree = int(degree)
-    if not 1 <= degree <= H.KID_MAX_DEGREE:
-        raise ValueError(f"{who}: degree = {degree} (1 .. {H.KID_MAX_DEGREE} are on the MI355X path)")
-    chunks = _chunks(who, chunks)
-    gamma, coef0 = 1.0 / F if gamma is None else float(gamma), float(coef0)
-    if not math.isfinite(gamma) or not math.isfinite(coef0):
-        raise ValueError(f"{who}: gamma = {gamma}, coef0 = {coef0} (finite numbers)")
-    return degree, gamma, coef0, chunks
-
-
-def _kid_sums(who, names, X, Y, idx_x, idx_y, degree, gamma, coef0, chunks):
-    """every check of kid_sums, then the C call -> (sums, the int32 index lists handed to it)"""
-    (nx, ny), (nix, niy) = names
-    X, Y = (_feature_rows(who, what, t, 1, 2 ** 31 - 1, "1 .. 2^31 - 1: the index lists are int32", finite=False)
-            for what, t in ((nx, X), (ny, Y)))      # (finite values: after the comparisons of the two sets)
-    if X.shape[1] != Y.shape[1]:
-        raise ValueError(f"{who}: {nx} has F = {X.shape[1]} features, {ny} F = {Y.shape[1]}")
-    if X.device != Y.device:
-        raise ValueError(f"{who}: {nx} is on {X.device}, {ny} on {Y.device}")
-    _finite(who, nx, X)
-    _finite(who, ny, Y)
-    F = X.shape[1]
-    degree, gamma, coef0, chunks = _kid_kernel(who, F, degree, gamma, coef0, chunks)
-    if torch.is_tensor(idx_x) and torch.is_tensor(idx_y) and idx_x.shape != idx_y.shape:
-        raise ValueError(f"{who}: {nix} is {tuple(idx_x.shape)}, {niy} {tuple(idx_y.shape)}; both (S, m)")
-    idx_x = _kid_index(who, nix, idx_x, X.shape[0], X.device)
-    idx_y = _kid_index(who, niy, idx_y, Y.shape[0], X.device)
-    if X.device.type != "cuda":
-        raise ValueError(f"{who}: {nx} is on {X.device}; the kernel runs on the MI355X (there is no host path)")
-    S, m = idx_x.shape
-    ws = torch.empty(H.lib().mmvae_kid_ws_doubles(S, m, chunks), dtype=torch.float64, device=X.device)
-    sums = torch.empty(S, 3, dtype=torch.float64, device=X.device)
-    _call("mmvae_kid_sums", H.ptr(X), H.ptr(Y), H.ptr(idx_x), H.ptr(idx_y), H.ptr(ws), H.ptr(sums), X.shape[0], Y.shape[0],
-          F, S, m, degree, gamma, coef0, chunks, H.stream())
-    return sums, idx_x, idx_y
-
-
-def kid_sums(X, Y, idx_x, idx_y, degree=3, gamma=None, coef0=1.0, chunks=0):
-    """The sums behind the kernel inception distance: feature rows X (rows_x,F), Y (rows_y,F); idx_x, idx_y integer (S,m),
-    per subset the rows taken from X and from Y.  With k(x, y) = (gamma x . y + coef0)^degree (gamma None: 1 / F),
-    x_i = X[idx_x[s,i]], y_j = Y[idx_y[s,j]] -> (S,3) float64 = [sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j),
-    sum_{i,j} k(x_i, y_j)], the diagonal of the first two left out by position in the list.  Dot products in double on the
-    fp64 MFMA, the rows gathered through the lists as they are loaded; neither a gathered copy nor an m x m block is
-    written.  `chunks`: how many workgroups share a row's columns (0: the default plan); two plans regroup fp64 sums
-    (agreement to rounding, not bit for bit), two runs with one plan give the same bits.  Every index is checked to lie
-    inside its set (one min/max read per list) before the kernel runs."""
-    return _kid_sums("kid_sums", (("X", "Y"), ("idx_x", "idx_y")), X, Y, idx_x, idx_y, degree, gamma, coef0, chunks)[0]
-
-
-def kid_draw(n_real, n_fake, subsets, m, seed):
-    """the subsets of a kernel inception distance, drawn on the host: rs = numpy.random.RandomState(seed); for s in order
-    rs.choice(n_real, m, replace=False), then rs.choice(n_fake, m, replace=False) -> two (subsets, m) int64 arrays"""
-    rs = np.random.RandomState(seed)
-    idx_real, idx_fake = np.empty((subsets, m), dtype=np.int64), np.empty((subsets, m), dtype=np.int64)
-    for s in range(subsets):
-        idx_real[s] = rs.choice(n_real, m, replace=False)
-        idx_fake[s] = rs.choice(n_fake, m, replace=False)
-    return idx_real, idx_fake
-
-
-def kernel_inception_distance(real, fake, subsets=100, subset_size=1000, seed=0, idx=None, degree=3, gamma=None, coef0=1.0,
-                              chunks=0):
-    """Kernel inception distance (Binkowski et al. 2018) of generated feature rows `fake` (M,F) against `real` (N,F): the
-    unbiased estimate of the squared maximum mean discrepancy under k(x, y) = (gamma x . y + coef0)^degree (gamma None:
-    1 / F), over `subsets` random subsets of m = min(subset_size, N, M) rows of each set, drawn without replacement
-    (kid_draw(N, M, subsets, m, seed)) or given as idx = (idx_real, idx_fake), integer (S, m):
-      mmd2[s] = sxx / (m (m - 1)) + syy / (m (m - 1)) - 2 sxy / m^2,   (sxx, syy, sxy) = kid_sums(...)[s]
-    -> {"kid": mean_s mmd2, "std": the standard deviation of mmd2 over the subsets (divisor S), both float64 0-d tensors
-        on the device, "mmd2": (S,), "sums": (S,3), "idx_real", "idx_fake": (S,m) int32 on the device, "m": m}.
-    The estimator is unbiased: a negative mmd2 (and kid) is a legitimate value and is not clamped."""
-    who = "kernel_inception_distance"
-    if idx is None:
-        if not all(torch.is_tensor(t) and t.dim() == 2 for t in (real, fake)):
-            raise ValueError(f"{who}: real and fake are floating (rows, F) features")
-        subsets, m = int(subsets), min(int(subset_size), real.shape[0], fake.shape[0])
-        if m < 2:
-            raise ValueError(f"{who}: m = min(subset_size = {subset_size}, {real.shape[0]} real rows, {fake.shape[0]} "
-                             f"generated rows) = {m} (the unbiased estimate needs two rows of each set)")
-        if not 1 <= subsets <= H.KID_MAX_SUBSETS or m > H.KID_MAX_SUBSET:
-            raise ValueError(f"{who}: {subsets} subsets of m = {m} rows (1 .. {H.KID_MAX_SUBSETS} subsets of 2 .. "
-                             f"{H.KID_MAX_SUBSET} rows are on the MI355X path)")
-        idx = tuple(torch.from_numpy(i).to(device=real.device, dtype=torch.int32)
-                    for i in kid_draw(real.shape[0], fake.shape[0], subsets, m, seed))
-    elif not isinstance(idx, (tuple, list)) or len(idx) != 2:
-        raise ValueError(f"{who}: idx is (idx_real, idx_fake), two integer (S, m) tensors")
-    sums, idx_real, idx_fake = _kid_sums(who, (("real", "fake"), ("idx_real", "idx_fake")), real, fake, idx[0], idx[1],
-                                         degree, gamma, coef0, chunks)
-    m = idx_real.shape[1]
-    mmd2 = sums[:, 0] / (m * (m - 1)) + sums[:, 1] / (m * (m - 1)) - 2.0 * sums[:, 2] / (m * m)
-    return {"kid": mmd2.mean(), "std": mmd2.std(unbiased=False), "mmd2": mmd2, "sums": sums, "idx_real": idx_real,
-            "idx_fake": idx_fake, "m": m}
-
-
-# ---- latent cluster analysis (csrc/cluster.hip): k-means, partition statistics, silhouette; float64, forward only -----------
-KMEANS_CHECK_EVERY = 8      # iterations per enqueued call and between two looks at the restarts' states
-
-
-def _cluster_rows(who, X):
-    return _feature_rows(who, "X", X, 1, H.MANIFOLD_MAX_ROWS, f"1 .. {H.MANIFOLD_MAX_ROWS} are on the MI355X path")
-
-
-def _cluster_count(who, C, N):
-    C = int(C)
-    if not 1 <= C <= H.CLUSTER_MAX_K:
-        raise ValueError(f"{who}: {C} clusters (1 .. {H.CLUSTER_MAX_K} are on the MI355X path)")
-    if C > N:
-        raise ValueError(f"{who}: {C} clusters for {N} rows (at most one cluster per row on the MI355X path)")
-    return C
-
-
-def _cluster_labels(who, what, labels, N, device=None):
-    """an integer (N,) tensor (N None: of any length >= 1) of ids >= 0 (on `device`, where one is given) or ValueError
-    -> (labels, the largest id)"""
-    if isinstance(labels, (np.ndarray, list, tuple)):
-        labels = torch.from_numpy(np.ascontiguousarray(labels))
-    if not torch.is_tensor(labels) or labels.dim() != 1 or labels.numel() == 0 or labels.is_floating_point() or labels.is_complex() or \
-            labels.dtype == torch.bool:
-        said = f"{tuple(labels.shape)}, {labels.dtype}" if torch.is_tensor(labels) else type(labels).__name__
-        raise ValueError(f"{who}: {what} is {said}; an integer (N,) tensor, one cluster id per row")
-    if N is not None and labels.shape[0] != N:
-        raise ValueError(f"{who}: {what} has {labels.shape[0]} entries for {N} rows")
-    if device is not None and labels.device != device:
-        raise ValueError(f"{who}: {what} is on {labels.device}, the rows on {device}")
-    labels = labels.detach()
-    lo, hi = (int(v) for v in torch.aminmax(labels))
-    if lo < 0:
-        raise ValueError(f"{who}: {what} holds negative ids (clusters are numbered from 0)")
-    return labels, hi
-
-
-def _cluster_partition(who, X, labels, n_clusters):
-    """the checks shared by cluster_stats and silhouette -> (X fp32, labels int32 on its device, C)"""
-    X = _cluster_rows(who, X)
-    labels, hi = _cluster_labels(who, "labels", labels, X.shape[0], X.device)
-    C = hi + 1 if n_clusters is None else int(n_clusters)
-    if not 1 <= C <= H.CLUSTER_MAX_K:
-        raise ValueError(f"{who}: {C} clusters (1 .. {H.CLUSTER_MAX_K} are on the MI355X path)")
-    if hi >= C:
-        raise ValueError(f"{who}: labels holds the id {hi}; n_clusters = {C} has the ids 0 .. {C - 1}")
-    return X, labels.to(torch.int32).contiguous(), C
-
-
-def _need_device(who, X):
-    if X.device.type != "cuda":
-        raise ValueError(f"{who}: X is on {X.device}; the kernels run on the MI355X (there is no host path)")
-
-
-def kmeans_draw(N, C, n_init, seed):
-    """the start centres of a k-means fit, drawn on the host: rs = numpy.random.RandomState(seed); per restart, in order,
-    rs.permutation(N)[:C] -> (n_init, C) int32 row numbers, no row twice within a restart"""
-    rs = np.random.RandomState(seed)
-    return np.stack([rs.permutation(N)[:C] for _ in range(n_init)]).astype(np.int32)
-
-
-def _cluster_spread(labels, d2, C):
-    R, N = labels.shape
-    counts = torch.empty(R, C, dtype=torch.int32, device=labels.device)
-    within, wdist = (torch.empty(R, C, dtype=torch.float64, device=labels.device) for _ in range(2))
-    inertia = torch.empty(R, dtype=torch.float64, device=labels.device)
-    _call("mmvae_cluster_spread", H.ptr(labels), H.ptr(d2), H.ptr(counts), H.ptr(within), H.ptr(wdist), H.ptr(inertia), N, C,
-          R, H.stream())
-    return counts, within, wdist, inertia
-
-
-def kmeans_check_init(who, init, N, F, C=None):
-    """the start centres of a k-means fit on (N, F) rows or ValueError: integer (R, C) row numbers inside [0, N), none twice
-    within a restart, or finite float64 (R, C, F) centres; R, C inside the limits, C <= N (and equal to `C`, where given)
-    -> (init as a tensor, whether it holds row numbers)"""
-    if isinstance(init, np.ndarray):
-        init = torch.from_numpy(np.ascontiguousarray(init))
-    rows = torch.is_tensor(init) and init.dim() == 2 and not init.is_floating_point() and not init.is_complex() and \
-        init.dtype != torch.bool
-    if not rows and not (torch.is_tensor(init) and init.dim() == 3 and init.dtype == torch.float64):
-        said = f"{tuple(init.shape)}, {init.dtype}" if torch.is_tensor(init) else type(init).__name__
-        raise ValueError(f"{who}: init is {said}; integer (R, C) row numbers or float64 (R, C, F) centres")
-    if not 1 <= init.shape[0] <= H.CLUSTER_MAX_INIT:
-        raise ValueError(f"{who}: {init.shape[0]} restarts (1 .. {H.CLUSTER_MAX_INIT} are on the MI355X path)")
-    if _cluster_count(who, init.shape[1], N) != (init.shape[1] if C is None else C):
-        raise ValueError(f"{who}: init holds {init.shape[1]} centres per restart, n_clusters = {C}")
-    init = init.detach()
-    if rows:
-        lo, hi = (int(v) for v in torch.aminmax(init))
-        if lo < 0 or hi >= N:
-            raise ValueError(f"{who}: init holds row numbers from {lo} to {hi}; X has the rows 0 .. {N - 1}")
-        ordered = torch.sort(init.long(), dim=1).values
-        if bool((ordered[:, 1:] == ordered[:, :-1]).any()):
-            raise ValueError(f"{who}: init names a row twice within one restart (two equal start centres)")
-    else:
-        if init.shape[2] != F:
-            raise ValueError(f"{who}: init has centres of {init.shape[2]} features, X F = {F}")
-        _finite(who, "init", init)
-    return init, rows
-
-
-def kmeans_fit(X, init, max_iter=300):
-    """k-means (Lloyd) on the rows of X (N,F), read as double, from given start centres, R restarts side by side.
-    `init`: integer (R,C) row numbers (centre c of restart r starts as row init[r, c]; kmeans_draw) or float64 (R,C,F)
-    centres.  Per restart, iteration t = 1, 2, ...: labels = the nearest centre by d^2 = sum_f (x_f - mu_f)^2 (a tie goes
-    to the lowest index); t > 1 and no label changed: converged, n_iter = t; else every centre becomes the mean of its rows
-    (summed in index order; a cluster without rows keeps its centre and counts in `empty`); after `max_iter` updates
-    without convergence one more assignment gives the labels of the returned centres.  This is scikit-learn's
-    KMeans(init=<array>, n_init=1, tol=0, algorithm="lloyd") on float64 input, except that it relocates empty clusters.
-    Two launches per iteration for all restarts; the host reads the restarts' states every KMEANS_CHECK_EVERY iterations.
-    -> {"centres" (R,C,F) float64, "labels" (R,N) int32, "inertia" (R,) float64 = sum_i d^2[i, label_i], "n_iter" (R,) int32,
-        "converged" (R,) bool, "empty" (R,) int32, "counts" (R,C) int32, "best": the restart of the smallest inertia (the
-        lowest of equals)}.  Two runs, and a restart alone or beside others, give the same bits."""
-    who = "kmeans_fit"
-    X = _cluster_rows(who, X)
-    N, F = X.shape
-    max_iter = int(max_iter)
-    if not 1 <= max_iter <= H.CLUSTER_MAX_ITER:
-        raise ValueError(f"{who}: max_iter = {max_iter} (1 .. {H.CLUSTER_MAX_ITER} are on the MI355X path)")
-    init, rows = kmeans_check_init(who, init, N, F)
-    R, C = init.shape[:2]
-    init = init.to(X.device)
-    _need_device(who, X)
-    centres = (X.double()[init.long()] if rows else init.clone()).contiguous()
-    labels = torch.zeros(R, N, dtype=torch.int32, device=X.device)
-    ws = torch.zeros(H.lib().mmvae_cluster_lloyd_ws_ints(N, R), dtype=torch.int32, device=X.device)
-    state = ws[:4 * R].view(R, 4)
-    for it0 in range(1, max_iter + 1, KMEANS_CHECK_EVERY):
-        _call("mmvae_cluster_lloyd", H.ptr(X), H.ptr(centres), H.ptr(labels), H.ptr(ws), N, F, C, R, it0,
-              min(KMEANS_CHECK_EVERY, max_iter - it0 + 1), max_iter, H.stream())
-        if bool((state[:, 0] != 0).all()):
-            break
-    d2 = torch.empty(R, N, dtype=torch.float64, device=X.device)
-    _call("mmvae_cluster_assign", H.ptr(X), H.ptr(centres), H.ptr(labels), H.ptr(d2), N, F, C, R, 0, H.stream())
-    counts, _, _, inertia = _cluster_spread(labels, d2, C)
-    state = state.clone()
-    finished = state[:, 0] != 0
-    empties = ws[ws.numel() - R * H.CLUSTER_MAX_K:].view(R, H.CLUSTER_MAX_K)      # (per cluster: the updates it had no rows at)
-    return {"centres": centres, "labels": labels, "inertia": inertia,
-            "n_iter": torch.where(finished, state[:, 1], torch.full_like(state[:, 1], max_iter)),
-            "converged": finished & (state[:, 2] != 0), "empty": empties.sum(1).to(torch.int32), "counts": counts,
-            "best": int(np.argmin(inertia.cpu().numpy()))}
-
-
-def cluster_stats(X, labels, n_clusters):
-    """The statistics of the partition `labels` (N,) of the rows of X (N,F) into the ids 0 .. n_clusters - 1, in double:
-    -> {"counts" (C,) int32, "means" (C,F) float64 (the rows summed in index order; 0 for an id without rows), "within" (C,)
-        = sum_{i in c} |x_i - m_c|^2, "wdist" (C,) = sum_{i in c} |x_i - m_c|, rows in index order}."""
-    who = "cluster_stats"
-    if n_clusters is None:
-        raise ValueError(f"{who}: n_clusters is None (1 .. {H.CLUSTER_MAX_K} are on the MI355X path)")
-    X, labels, C = _cluster_partition(who, X, labels, n_clusters)
-    _need_device(who, X)
-    N, F = X.shape
-    labels = labels.view(1, N)
-    means = torch.zeros(1, C, F, dtype=torch.float64, device=X.device)
-    counts = torch.empty(1, C, dtype=torch.int32, device=X.device)
-    d2 = torch.empty(1, N, dtype=torch.float64, device=X.device)
-    _call("mmvae_cluster_means", H.ptr(X), H.ptr(labels), H.ptr(means), H.ptr(counts), N, F, C, 1, H.stream())
-    _call("mmvae_cluster_assign", H.ptr(X), H.ptr(means), H.ptr(labels), H.ptr(d2), N, F, C, 1, 1, H.stream())
-    counts, within, wdist, _ = _cluster_spread(labels, d2, C)
-    return {"counts": counts[0], "means": means[0], "within": within[0], "wdist": wdist[0]}
-
-
-def cluster_indices(stats):
-    """Calinski-Harabasz and Davies-Bouldin indices from cluster_stats' result, on the host in float64 as scikit-learn's
-    calinski_harabasz_score and davies_bouldin_score compute them, over the C' clusters that have rows:
-      CH = [sum_c n_c |m_c - m|^2 / (C' - 1)] / [sum_c within_c / (N - C')], m the mean of all rows (1 where the clusters
-      have no spread); DB = mean_c max_{c' != c} (wdist_c / n_c + wdist_c' / n_c') / |m_c - m_c'| (0 where every spread or
-      every distance between means vanishes).  -> {"calinski_harabasz": float, "davies_bouldin": float}"""
-    who = "cluster_indices"
-    if not isinstance(stats, dict) or any(k not in stats for k in ("counts", "means", "within", "wdist")):
-        raise ValueError(f"{who}: stats is what cluster_stats returns (counts, means, within, wdist)")
-    n_all, m, within, wdist = (np.asarray(torch.as_tensor(stats[k]).detach().cpu().numpy())
-                               for k in ("counts", "means", "within", "wdist"))
-    if m.ndim != 2 or any(v.shape != (m.shape[0],) for v in (n_all, within, wdist)):
-        raise ValueError(f"{who}: stats holds counts, within, wdist (C,) and means (C, F)")
-    on = n_all > 0
-    n, m, within, wdist = n_all[on].astype(np.float64), m[on].astype(np.float64), within[on], wdist[on]
-    N, C = n.sum(), len(n)
-    if not 2 <= C < N:
-        raise ValueError(f"{who}: {C} clusters with rows for {int(N)} rows (the indices need 2 .. N - 1)")
-    mean = (n[:, None] * m).sum(0) / N
-    extra, intra = float((n * ((m - mean) ** 2).sum(1)).sum()), float(within.sum())
-    ch = 1.0 if intra == 0.0 else extra * (N - C) / (intra * (C - 1.0))
-    spread = wdist / n
-    between = np.sqrt(((m[:, None, :] - m[None, :, :]) ** 2).sum(2))
-    if np.allclose(spread, 0) or np.allclose(between, 0):
-        db = 0.0
-    else:
-        between[between == 0] = np.inf
-        db = float(np.mean(np.max((spread[:, None] + spread[None, :]) / between, axis=1)))
-    return {"calinski_harabasz": float(ch), "davies_bouldin": db}
-
-
-def _silhouette_plan(counts, N, chunks):
-    """the padded column list's layout and the chunk table from the clusters' sizes (host) -> (tile offset per cluster,
-    padded length, table (chunks, 3) int32 = (cluster, first tile, tile past the last), first (C + 1,) int32)"""
-    tiles = (counts + 63) // 64
-    offset = np.concatenate(([0], np.cumsum(tiles)))
-    per = H.lib().mmvae_cluster_sil_tiles_per_chunk(N, int(offset[-1]), chunks)
-    table, first = [], [0]
-    for c, t in enumerate(tiles):
-        table += [(c, int(offset[c]) + t0, int(offset[c]) + min(t0 + per, int(t))) for t0 in range(0, int(t), per)]
-        first.append(len(table))
-    return offset, 64 * int(offset[-1]), np.array(table, dtype=np.int32).reshape(-1, 3), np.array(first, dtype=np.int32)
-
-
-def silhouette(X, labels, n_clusters=None, chunks=0):
-    """Silhouette of the partition `labels` (N,) of the rows of X (N,F); ids 0 .. n_clusters - 1 (None: the largest id + 1),
-    ids without rows allowed.  d(i, j) = sqrt(max(0, (|x_i|^2 + |x_j|^2) - 2 x_i . x_j)) in double, the product on the fp64
-    MFMA; S[i, c] = sum_{j in c, j != i} d(i, j), the row itself left out by INDEX (a duplicate row is an ordinary member
-    at distance 0); a = S[i, l_i] / (n_l - 1), b = min over the other clusters with rows of S[i, c] / n_c,
-    s_i = (b - a) / max(a, b), 0 in a cluster of one row and where max(a, b) = 0.  Neither the N x N matrix nor an N x n_c
-    block is written: the columns are walked through a list of row numbers sorted by cluster.  `chunks`: 0 = the default
-    plan, or the number of chunks the column list is cut into before the cuts at the cluster borders; two plans regroup
-    fp64 sums (agreement to rounding), two runs with one plan give the same bits.
-    -> {"samples" (N,) float64, "score": float = mean_i s_i, "sums" S (N,C) float64, "counts" (C,) int64}."""
-    who = "silhouette"
-    X, labels, C = _cluster_partition(who, X, labels, n_clusters)
-    chunks = _chunks(who, chunks)
-    N, F = X.shape
-    lab = labels.long()
-    cnt = torch.bincount(lab, minlength=C)
-    counts = cnt.cpu().numpy()
-    if int((counts > 0).sum()) < 2:
-        raise ValueError(f"{who}: labels puts every row into one cluster (the silhouette needs two clusters with rows)")
-    _need_device(who, X)
-    dev = X.device
-    offset, padded, table, first = _silhouette_plan(counts, N, chunks)
-    order = torch.argsort(lab, stable=True)
-    of = lab[order]
-    start = torch.from_numpy(np.concatenate(([0], np.cumsum(counts)[:-1]))).to(dev)
-    place = 64 * torch.from_numpy(offset[:-1]).to(dev)[of] + (torch.arange(N, device=dev) - start[of])
-    column_list = torch.full((padded,), -1, dtype=torch.int32, device=dev)
-    column_list[place] = order.to(torch.int32)
-    n_chunks = len(table)
-    ws = torch.empty(H.lib().mmvae_cluster_sil_ws_doubles(N, n_chunks), dtype=torch.float64, device=dev)
-    S = torch.empty(N, C, dtype=torch.float64, device=dev)
-    n2, table, first = _manifold_sqnorms(X), torch.from_numpy(table).to(dev), torch.from_numpy(first).to(dev)
-    _call("mmvae_cluster_sil_sums", H.ptr(X), H.ptr(n2), H.ptr(column_list), H.ptr(table), H.ptr(first), H.ptr(ws), H.ptr(S),
-          N, F, C, padded, n_chunks, H.stream())
-    own = cnt[lab]
-    a = S.gather(1, lab[:, None])[:, 0] / (own - 1).clamp(min=1)
-    others = (cnt[None, :] > 0) & (torch.arange(C, device=dev)[None, :] != lab[:, None])
-    b = torch.where(others, S / cnt.clamp(min=1)[None, :], torch.full_like(S, float("inf"))).min(1).values
-    top = torch.maximum(a, b)
-    s = torch.where((own > 1) & (top > 0), (b - a) / top, torch.zeros_like(top))
-    return {"samples": s, "score": float(s.mean()), "sums": S, "counts": cnt}
-
-
-def cluster_agreement(a, b):
-    """Agreement of two labelings of the same rows, a the classes and b the clusters, from their integer contingency table
-    T[class, cluster] on the host in float64, as scikit-learn defines them: adjusted Rand index, normalised mutual
-    information (arithmetic mean of the entropies, natural logarithm), homogeneity, completeness, and purity = sum over
-    the clusters of max_class T / N.  -> {"ari", "nmi", "homogeneity", "completeness", "purity"}: floats"""
-    who = "cluster_agreement"
-    sides = []
-    for what, t in (("a", a), ("b", b)):
-        sides.append(_cluster_labels(who, what, t, None)[0].cpu().numpy())
-    if len(sides[0]) != len(sides[1]):
-        raise ValueError(f"{who}: a has {len(sides[0])} entries, b {len(sides[1])} (one pair of ids per row)")
-    ia, ib = (np.unique(t, return_inverse=True)[1] for t in sides)
-    T = np.zeros((int(ia.max()) + 1, int(ib.max()) + 1), dtype=np.int64)
-    np.add.at(T, (ia, ib), 1)
-    N, ra, rb = int(T.sum()), T.sum(1), T.sum(0)
-    sq = int((T * T).sum())
-    tp, fp, fn = sq - N, int((T @ rb).sum()) - sq, int((T.T @ ra).sum()) - sq
-    tn = N * N - fp - fn - sq
-    ari = 1.0 if fn == 0 and fp == 0 else 2.0 * (tp * tn - fn * fp) / ((tp + fn) * (fn + tn) + (tp + fp) * (fp + tn))
-    i, j = np.nonzero(T)
-    v = T[i, j].astype(np.float64)
-    mi = float(max(np.sum(v / N * (np.log(v) - math.log(N)) + v / N * (-np.log(ra[i] * rb[j].astype(np.float64))
-                                                                       + 2.0 * math.log(N))), 0.0))
-
-    def entropy(n):
-        n = n[n > 0].astype(np.float64)
-        return float(-np.sum((n / n.sum()) * (np.log(n) - math.log(n.sum()))))
-    ha, hb, tiny = entropy(ra), entropy(rb), float(np.finfo(np.float64).eps)
-    if len(ra) == 1 and len(rb) == 1:
-        nmi = 1.0
-    else:
-        nmi = 0.0 if mi <= tiny else mi / max(0.5 * (ha + hb), tiny)
-    return {"ari": float(ari), "nmi": float(nmi), "homogeneity": mi / ha if ha else 1.0,
-            "completeness": mi / hb if hb else 1.0, "purity": float(T.max(0).sum()) / N}
-
-
-# ---- latent density estimation (csrc/gmm.hip): Gaussian-mixture EM, scoring, draws; float64, forward only --------------------
-GMM_SLICE_BYTES = 256 << 20      # restarts run in slices whose responsibilities and workspace stay under this
-
-
-def _gmm_rows(who, X, D=None):
-    """contiguous fp32 (N, D) rows inside the limits (and of `D` dimensions, where given) or ValueError"""
-    X = _feature_rows(who, "X", X, 1, H.MANIFOLD_MAX_ROWS, f"1 .. {H.MANIFOLD_MAX_ROWS} are on the MI355X path", finite=False)
-    if not 1 <= X.shape[1] <= H.GMM_MAX_D:
-        raise ValueError(f"{who}: X has D = {X.shape[1]} dimensions (1 .. {H.GMM_MAX_D} are on the MI355X path)")
-    if D is not None and X.shape[1] != D:
-        raise ValueError(f"{who}: X has D = {X.shape[1]} dimensions, the mixture {D}")
-    _finite(who, "X", X)
-    return X
-
-
-def _gmm_covariance(who, covariance_type):
-    if covariance_type not in H.GMM_COVARIANCES:
-        raise ValueError(f"{who}: covariance_type = {covariance_type!r} ({', '.join(map(repr, H.GMM_COVARIANCES))} are on "
-                         f"the MI355X path)")
-    return H.GMM_COVARIANCES[covariance_type]
-
-
-def gmm_check_init(who, init, N, n_components=None):
-    """the start of a mixture fit on N rows or ValueError: integer (R, N) labels, one per row and restart, inside
-    [0, n_components) (None: the largest id + 1 components); R and the components inside the limits
-    -> (init as an int32 tensor, C)"""
-    if isinstance(init, np.ndarray):
-        init = torch.from_numpy(np.ascontiguousarray(init))
-    if not torch.is_tensor(init) or init.dim() != 2 or init.is_floating_point() or init.is_complex() or init.dtype == torch.bool:
-        said = f"{tuple(init.shape)}, {init.dtype}" if torch.is_tensor(init) else type(init).__name__
-        raise ValueError(f"{who}: init is {said}; integer (R, N) labels, one component id per restart and row")
-    if not 1 <= init.shape[0] <= H.CLUSTER_MAX_INIT:
-        raise ValueError(f"{who}: {init.shape[0]} restarts (1 .. {H.CLUSTER_MAX_INIT} are on the MI355X path)")
-    if init.shape[1] != N:
-        raise ValueError(f"{who}: init has {init.shape[1]} labels per restart for {N} rows")
-    init = init.detach()
-    lo, hi = (int(v) for v in torch.aminmax(init))
-    C = hi + 1 if n_components is None else int(n_components)
-    if not 1 <= C <= H.CLUSTER_MAX_K:
-        raise ValueError(f"{who}: {C} components (1 .. {H.CLUSTER_MAX_K} are on the MI355X path)")
-    if lo < 0 or hi >= C:
-        raise ValueError(f"{who}: init holds the ids {lo} .. {hi}; n_components = {C} has the ids 0 .. {C - 1}")
-    return init.to(torch.int32).contiguous(), C
-
-
-def _gmm_fit_args(who, reg_covar, tol, max_iter):
-    reg_covar, tol, max_iter = float(reg_covar), float(tol), int(max_iter)
-    if not (reg_covar >= 0.0 and math.isfinite(reg_covar)):
-        raise ValueError(f"{who}: reg_covar = {reg_covar} (a finite value >= 0)")
-    if not (tol >= 0.0 and math.isfinite(tol)):
-        raise ValueError(f"{who}: tol = {tol} (a finite value >= 0)")
-    if not 1 <= max_iter <= H.CLUSTER_MAX_ITER:
-        raise ValueError(f"{who}: max_iter = {max_iter} (1 .. {H.CLUSTER_MAX_ITER} are on the MI355X path)")
-    return reg_covar, tol, max_iter
-
-
-def gmm_fit(X, init, covariance_type="full", reg_covar=1e-6, tol=1e-3, max_iter=100, sync_every=10, n_components=None,
-            slice_bytes=None):
-    """EM for a mixture of C Gaussians on the rows of X (N,D), read as double, R restarts side by side, with the arithmetic of
-    scikit-learn's GaussianMixture (covariance_type "full" or "diag").  `init`: integer (R,N) labels; restart r starts from
-    their one-hot as responsibilities and one M-step (C = `n_components`, or the largest id + 1; a component without rows
-    starts as N(0, reg_covar I) with weight ~0).  Iteration t = 1, 2, ...: E-step, M-step; the restart has converged when the
-    E-step's lower bound (the mean log-density) moved by less than `tol`; n_iter = t.  A restart one of whose covariances
-    has no Cholesky factor is `degenerate` (bound -inf, never `best`); when every restart is, ValueError.  Three launches
-    per iteration for all restarts; the host reads the restarts' records every `sync_every` iterations.  Restarts run in
-    slices of `slice_bytes` (GMM_SLICE_BYTES) of responsibilities and workspace.
-    -> {"weights" (R,C), "means" (R,C,D), "covariances" (R,C,D,D) | (R,C,D), "cholesky" (lower factors; diag: square roots),
-        "precisions_cholesky", "log_det" (R,C), "lower_bound" (R,), "n_iter" (R,) int32, "converged", "degenerate" (R,) bool,
-        "best": the restart of the largest bound (the lowest of equals), "labels" (R,N) int32, "resp" (R,N,C), "log_density"
-        (R,N) of the final parameters, "covariance_type"}, float64.  Two runs, a restart alone or beside others, any
-        `sync_every` and any slicing give the same bits."""
-    who = "gmm_fit"
-    X = _gmm_rows(who, X)
-    N, D = X.shape
-    diag = _gmm_covariance(who, covariance_type)
-    reg_covar, tol, max_iter = _gmm_fit_args(who, reg_covar, tol, max_iter)
-    sync_every = int(sync_every)
-    if sync_every < 1:
-        raise ValueError(f"{who}: sync_every = {sync_every} (at least one iteration between two looks at the records)")
-    init, C = gmm_check_init(who, init, N, n_components)
-    R = init.shape[0]
-    slice_bytes = GMM_SLICE_BYTES if slice_bytes is None else int(slice_bytes)
-    if slice_bytes < 1:
-        raise ValueError(f"{who}: slice_bytes = {slice_bytes} (a positive number of bytes; one restart runs in any case)")
-    _need_device(who, X)
-    dev = X.device
-    init = init.to(dev)
-    per = 8 * (N * C + H.lib().mmvae_gmm_ws_doubles(N, D, C, 1, diag))
-    step = max(1, min(R, slice_bytes // per))
-    shape = (D,) if diag else (D, D)
-    parts = []
-    for r0 in range(0, R, step):
-        Rs = min(step, R - r0)
-        f64 = dict(dtype=torch.float64, device=dev)
-        weights, logdet = torch.empty(Rs, C, **f64), torch.empty(Rs, C, **f64)
-        means = torch.empty(Rs, C, D, **f64)
-        cov, chol, prec = (torch.empty(Rs, C, *shape, **f64) for _ in range(3))
-        resp = torch.empty(Rs, N, C, **f64)
-        ws = torch.zeros(H.lib().mmvae_gmm_ws_doubles(N, D, C, Rs, diag), **f64)
-        state = ws[:4 * Rs].view(Rs, 4)
-        bad = ws[4 * Rs:(4 + H.CLUSTER_MAX_K) * Rs].view(Rs, H.CLUSTER_MAX_K)
-        start = init[r0:r0 + Rs].contiguous()
-        for it0 in range(1, max_iter + 1, sync_every):
-            _call("mmvae_gmm_em", H.ptr(X), H.ptr(start), H.ptr(weights), H.ptr(means), H.ptr(cov), H.ptr(chol), H.ptr(prec),
-                  H.ptr(logdet), H.ptr(resp), H.ptr(ws), N, D, C, Rs, diag, reg_covar, tol, it0,
-                  min(sync_every, max_iter - it0 + 1), max_iter, H.stream())
-            if bool(((state[:, 3] != 0) | (bad != 0).any(1)).all()):
-                break
-        logdens = torch.empty(Rs, N, **f64)
-        labels = torch.empty(Rs, N, dtype=torch.int32, device=dev)
-        _call("mmvae_gmm_score", H.ptr(X), H.ptr(weights), H.ptr(means), H.ptr(prec), H.ptr(logdet), H.ptr(logdens),
-              H.ptr(resp), H.ptr(labels), N, D, C, Rs, diag, H.stream())
-        degenerate = (bad != 0).any(1)
-        parts.append({"weights": weights, "means": means, "covariances": cov, "cholesky": chol, "precisions_cholesky": prec,
-                      "log_det": logdet,
-                      "lower_bound": torch.where(degenerate, torch.full_like(state[:, 0], -math.inf), state[:, 0]),
-                      "n_iter": state[:, 1].to(torch.int32), "converged": (state[:, 2] != 0) & ~degenerate,
-                      "degenerate": degenerate, "labels": labels, "resp": resp, "log_density": logdens})
-    out = {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
-    bound = out["lower_bound"].cpu().numpy()
-    if bool(out["degenerate"].all()):
-        raise ValueError(f"{who}: every restart met a covariance without a Cholesky factor (a component of a single row or of "
-                         f"equal rows); reg_covar = {reg_covar}: increase it, or ask for fewer components")
-    out["best"] = int(np.argmax(bound))      # (degenerate restarts hold -inf; the first of equals)
-    out["covariance_type"] = covariance_type
-    return out
-
-
-def _gmm_mixture(who, fit, restart):
-    """one mixture out of what gmm_fit returns (`restart`, None: its best) or of a single mixture's entry (weights (C,), as
-    TorchMMVAE.fit_latent_density returns per subset; `restart` must be None) or ValueError
-    -> ({"weights" (C,), "means" (C,D), "cholesky", "precisions_cholesky", "log_det" (C,)}: contiguous float64, diag, restart)"""
-    keys = ("weights", "means", "cholesky", "precisions_cholesky", "log_det")
-    if not isinstance(fit, dict) or any(not torch.is_tensor(fit.get(k)) or fit[k].dtype != torch.float64 for k in keys) or \
-            "covariance_type" not in fit:
-        raise ValueError(f"{who}: fit is what gmm_fit returns (float64 {', '.join(keys)}; covariance_type)")
-    diag = _gmm_covariance(who, fit["covariance_type"])
-    many = fit["weights"].dim() == 2
-    if many:
-        R = fit["weights"].shape[0]
-        restart = fit.get("best") if restart is None else restart
-        if not isinstance(restart, (int, np.integer)) or not 0 <= restart < R:
-            raise ValueError(f"{who}: restart = {restart!r} (the fit holds the restarts 0 .. {R - 1})")
-        if "degenerate" in fit and bool(fit["degenerate"][restart]):
-            raise ValueError(f"{who}: restart {restart} is degenerate (a covariance without a Cholesky factor)")
-        restart = int(restart)
-    elif restart is not None:
-        raise ValueError(f"{who}: restart = {restart!r} for a single mixture (None)")
-    m = {k: (fit[k][restart] if many else fit[k]).detach().contiguous() for k in keys}
-    C = m["weights"].shape[0] if m["weights"].dim() == 1 else 0
-    D = m["means"].shape[1] if m["means"].dim() == 2 else 0
-    shape = (C, D) if diag else (C, D, D)
-    if not 1 <= C <= H.CLUSTER_MAX_K or not 1 <= D <= H.GMM_MAX_D or m["means"].shape != (C, D) or m["log_det"].shape != (C,) or \
-            m["cholesky"].shape != shape or m["precisions_cholesky"].shape != shape:
-        raise ValueError(f"{who}: fit holds weights {tuple(m['weights'].shape)}, means {tuple(m['means'].shape)}, factors "
-                         f"{tuple(m['cholesky'].shape)}; (C), (C, D) and {'(C, D)' if diag else '(C, D, D)'} with C <= "
-                         f"{H.CLUSTER_MAX_K}, D <= {H.GMM_MAX_D} are on the MI355X path")
-    return m, diag, restart
-
-
-def gmm_score(X, fit, restart=None):
-    """The log-density of the rows of X (N,D) under one mixture of `fit` (gmm_fit's result and a restart, None: its best; or a
-    single mixture's entry), by the E-step's kernel: on the fitted rows it returns the fit's own bits.
-    -> {"log_density" (N,) float64, "labels" (N,) int32 (the first most probable component), "resp" (N,C), "score": the mean}"""
-    who = "gmm_score"
-    m, diag, _ = _gmm_mixture(who, fit, restart)
-    C, D = m["means"].shape
-    X = _gmm_rows(who, X, D)
-    N = X.shape[0]
-    _need_device(who, X)
-    m = {k: v.to(X.device) for k, v in m.items()}
-    logdens = torch.empty(N, dtype=torch.float64, device=X.device)
-    resp = torch.empty(N, C, dtype=torch.float64, device=X.device)
-    labels = torch.empty(N, dtype=torch.int32, device=X.device)
-    _call("mmvae_gmm_score", H.ptr(X), H.ptr(m["weights"]), H.ptr(m["means"]), H.ptr(m["precisions_cholesky"]),
-          H.ptr(m["log_det"]), H.ptr(logdens), H.ptr(resp), H.ptr(labels), N, D, C, 1, diag, H.stream())
-    return {"log_density": logdens, "labels": labels, "resp": resp, "score": float(logdens.cpu().numpy().mean())}
-
-
-def gmm_sample(fit, n, u=None, eps=None, state=None, restart=None):
-    """n draws from one mixture of `fit` (as in gmm_score): draw i takes the first component k with u[i] < w_0 + .. + w_k (the
-    last one takes the rest) and z = mu_k + L_k eps[i] in double, rounded to fp32 once.  `u` (n,) float64 in [0, 1) (None:
-    numpy.random.RandomState(0).random_sample(n)); `eps` (n,D) floats (None: ops.randn on `state`, the int32[3] state of the
-    device generator).  -> (z (n,D) fp32, components (n,) int32)"""
-    who = "gmm_sample"
-    m, diag, _ = _gmm_mixture(who, fit, restart)
-    C, D = m["means"].shape
-    n = int(n)
-    if not 1 <= n <= H.GMM_MAX_DRAWS:
-        raise ValueError(f"{who}: n = {n} draws (1 .. {H.GMM_MAX_DRAWS} per call are on the MI355X path)")
-    if u is None:
-        u = torch.from_numpy(np.random.RandomState(0).random_sample(n))
-    if isinstance(u, np.ndarray):
-        u = torch.from_numpy(np.ascontiguousarray(u))
-    if not torch.is_tensor(u) or u.dtype != torch.float64 or u.shape != (n,):
-        said = f"{tuple(u.shape)}, {u.dtype}" if torch.is_tensor(u) else type(u).__name__
-        raise ValueError(f"{who}: u is {said}; float64 ({n},) values in [0, 1)")
-    if not bool(((u >= 0) & (u < 1)).all()):
-        raise ValueError(f"{who}: u holds values outside [0, 1)")
-    if eps is None:
-        if not torch.is_tensor(state) or state.dtype != torch.int32 or state.numel() != 3:
-            raise ValueError(f"{who}: without eps the draws need `state`, the int32[3] state of the device generator")
-        eps = randn((n, D), state)
-    if not torch.is_tensor(eps) or not eps.is_floating_point() or eps.shape != (n, D):
-        said = f"{tuple(eps.shape)}, {eps.dtype}" if torch.is_tensor(eps) else type(eps).__name__
-        raise ValueError(f"{who}: eps is {said}; floating ({n}, {D}) standard-normal values")
-    _finite(who, "eps", eps)
-    dev = m["weights"].device
-    if dev.type != "cuda":
-        raise ValueError(f"{who}: the mixture is on {dev}; the kernels run on the MI355X (there is no host path)")
-    u, eps = u.detach().to(dev).contiguous(), H.f32c(eps.detach().to(dev))
-    z = torch.empty(n, D, dtype=torch.float32, device=dev)
-    comp = torch.empty(n, dtype=torch.int32, device=dev)
-    _call("mmvae_gmm_sample", H.ptr(m["weights"]), H.ptr(m["means"]), H.ptr(m["cholesky"]), H.ptr(u), H.ptr(eps), H.ptr(z),
-          H.ptr(comp), n, D, C, diag, H.stream())
-    return z, comp
-
-
-def gmm_information(fit, n_rows, restart=None):
-    """BIC and AIC of one mixture of `fit` on the n_rows rows it was fitted to, on the host, as scikit-learn's
-    GaussianMixture.bic / .aic: n_parameters = C D (D + 1) / 2 + C D + C - 1 (full) or 2 C D + C - 1 (diag); with score = the
-    mean log-density of those rows (`fit["log_density"]` of the restart, or a single mixture's `fit["score"]`):
-    bic = -2 N score + n_parameters ln N, aic = -2 N score + 2 n_parameters.  -> {"n_parameters", "bic", "aic"}"""
-    who = "gmm_information"
-    if not isinstance(fit, dict) or not torch.is_tensor(fit.get("means")) or "covariance_type" not in fit:
-        raise ValueError(f"{who}: fit is what gmm_fit returns (means, covariance_type, log_density)")
-    diag = _gmm_covariance(who, fit["covariance_type"])
-    n_rows = int(n_rows)
-    if n_rows < 1:
-        raise ValueError(f"{who}: n_rows = {n_rows}")
-    C, D = fit["means"].shape[-2:]
-    if fit["means"].dim() == 3:
-        R = fit["means"].shape[0]
-        restart = fit.get("best") if restart is None else restart
-        if not isinstance(restart, (int, np.integer)) or not 0 <= restart < R:
-            raise ValueError(f"{who}: restart = {restart!r} (the fit holds the restarts 0 .. {R - 1})")
-        rows = fit["log_density"][restart]
-        if rows.shape[0] != n_rows:
-            raise ValueError(f"{who}: n_rows = {n_rows}, the fit holds the log-density of {rows.shape[0]} rows")
-        score = float(rows.detach().cpu().numpy().mean())
-    else:
-        if restart is not None:
-            raise ValueError(f"{who}: restart = {restart!r} for a single mixture (None)")
-        score = float(fit["score"])
-    n_par = (2 * C * D if diag else C * D * (D + 1) // 2 + C * D) + C - 1
-    return {"n_parameters": n_par, "bic": -2.0 * score * n_rows + n_par * math.log(n_rows),
-            "aic": -2.0 * score * n_rows + 2 * n_par}
-
-
-# ---- canonical correlation of feature pairs and sentence features (csrc/cca.hip): float64, forward only, no autograd ---------
-def _f64_block(who, what, M):
-    """a float64 (rows, cols) tensor or view whose rows are contiguous (a sub-block of a row-major matrix), or ValueError"""
-    if not torch.is_tensor(M) or M.dim() != 2 or M.dtype != torch.float64 or M.stride(1) != 1 or \
-            M.stride(0) < M.shape[1] or not all(1 <= n <= H.FRECHET_MAX_F for n in M.shape):
-        said = f"{tuple(M.shape)}, {M.dtype}, strides {M.stride()}" if torch.is_tensor(M) else type(M).__name__
-        raise ValueError(f"{who}: {what} is {said}; a float64 block (rows, cols) with contiguous rows, 1 .. "
-                         f"{H.FRECHET_MAX_F} each way on the MI355X path")
-    return M
-
-
-def f64_gemm_ld(A, B, out, trans_b=False, scale=None):
-    """out (M,N) <- (A diag(scale)) B, or (A diag(scale)) B^T for trans_b: A (M,K), B (K,N) or (N,K), `out` float64 blocks
-    with contiguous rows -- slices of larger row-major matrices are read and written in place, nothing else of `out`'s
-    matrix is touched.  `scale` (K,) float64 multiplies the columns of A as they are loaded (None: the plain product).  The
-    fp64 MFMA tile routine of f64_gemm; M, N, K need be no multiples of its tile.  `out` must not share memory with A or
-    B.  -> out"""
-    who = "f64_gemm_ld"
-    A, B, out = _f64_block(who, "A", A), _f64_block(who, "B", B), _f64_block(who, "out", out)
-    (M, K), (N, Kb) = A.shape, (B.shape if trans_b else B.shape[::-1])
-    if Kb != K or tuple(out.shape) != (M, N):
-        raise ValueError(f"{who}: A {tuple(A.shape)}, B {tuple(B.shape)} (trans_b = {bool(trans_b)}), out "
-                         f"{tuple(out.shape)} do not form a product")
-    if scale is not None:
-        if not torch.is_tensor(scale) or tuple(scale.shape) != (K,) or scale.dtype != torch.float64:
-            raise ValueError(f"{who}: scale must be float64 ({K},), one factor per column of A")
-        scale = scale.contiguous()
-    store = out.untyped_storage().data_ptr()
-    if store in (A.untyped_storage().data_ptr(), B.untyped_storage().data_ptr()):
-        raise ValueError(f"{who}: out shares its memory with an operand")
-    if not (A.is_cuda and B.is_cuda and out.is_cuda):
-        raise ValueError(f"{who}: the blocks are on {A.device}, {B.device}, {out.device}; the kernel runs on the MI355X "
-                         f"(there is no host path)")
-    _call("mmvae_f64_gemm_ld", H.ptr(A), A.stride(0), H.ptr(B), B.stride(0), H.ptr(out), out.stride(0), H.ptr(scale), M, N, K,
-          int(bool(trans_b)), H.stream())
-    return out
-
-
-def _cca_widths(who, widths, O):
-    try:
-        widths = [int(w) for w in widths]
-    except TypeError:
-        raise ValueError(f"{who}: widths = {widths!r} (the feature width of every view, in order)") from None
-    if not 2 <= len(widths) <= H.CCA_MAX_VIEWS or min(widths) < 1:
-        raise ValueError(f"{who}: widths = {widths} (2 .. {H.CCA_MAX_VIEWS} views of at least one feature each)")
-    if sum(widths) != O:
-        raise ValueError(f"{who}: widths = {widths} sum to {sum(widths)}, the moments hold O = {O} features")
-    if O > H.FRECHET_MAX_F:
-        raise ValueError(f"{who}: the views hold O = {O} features side by side; the eigensolver takes at most "
-                         f"{H.FRECHET_MAX_F} in all (MMVAE_FRECHET_MAX_F) on the MI355X path: reduce a view's features first")
-    return widths
-
-
-def cca_fit(mu, sigma, widths, k, ridge=1e-12):
-    """Multi-view canonical correlation analysis from the moments of the stacked views: the arithmetic of the reference's
-    cca (eval/mnistsvhn_helper.py:26-78) in float64 on the device.  `mu` (O,), `sigma` (O,O): frechet_moments of rows that
-    hold the views' features side by side, view i `widths[i]` wide, O = sum(widths).  The reference solves A v = lambda B v,
-    B = the block diagonal of the views' covariances + ridge I, A = the off-diagonal blocks + ridge I (its quirk, kept).
-    Here, with W = B^-1/2 built per view from sym_eig (B_i = Q L Q^T, W_i = Q L^-1/2 Q^T), the symmetric positive
-    semi-definite N = W (sigma + 2 ridge I) W has the eigenvalues 1 + lambda and the eigenvectors u, v = W u: sym_eig(N),
-    a stable descending sort (ties keep solver order), the k largest.  Every product is f64_gemm_ld on sub-blocks of
-    (O,O) matrices; no block-diagonal W is multiplied out.
-    -> {"correlations": (k,) float64 = value - 1, "projections": [(o_i, k) float64 per view], the columns of the stacked
-        (O, k) matrix scaled to unit Euclidean norm (what scipy.linalg.eig returns; the sign of a column is the solver's),
-        "means": [the slices of mu], "sweeps": {"views": [per view], "joint": of N}, "condition": [lambda_min / lambda_max
-        of B_i per view], "widths", "k"}.
-    2 .. 8 views, O <= 2048, 1 <= k <= min(min(widths), 64), ridge > 0.  A view whose covariance is rank-deficient is
-    ill-posed at the default ridge (float64 eig(A, B) itself is): the remedy is the caller's, a ridge near 1e-3 of the
-    feature variance.
-    Deviations from the reference: k is required (its k=None picks k by an Otsu threshold of scikit-image, not restated);
-    the covariances are float64 from the float32 features, where the reference forms them in float32 torch.mm."""
-    who = "cca_fit"
-    if not torch.is_tensor(sigma) or sigma.dim() != 2 or sigma.shape[0] != sigma.shape[1] or sigma.dtype != torch.float64 \
-            or not torch.is_tensor(mu) or tuple(mu.shape) != (sigma.shape[0],) or mu.dtype != torch.float64:
-        raise ValueError(f"{who}: mu (O,) and sigma (O,O) are the float64 moments frechet_moments returns")
-    O = sigma.shape[0]
-    widths = _cca_widths(who, widths, O)
-    k, ridge = int(k), float(ridge)
-    if not 1 <= k <= min(min(widths), H.CCA_MAX_K):
-        raise ValueError(f"{who}: k = {k} (1 .. min(narrowest view = {min(widths)}, {H.CCA_MAX_K}) on the MI355X path)")
-    if not (ridge > 0.0 and math.isfinite(ridge)):
-        raise ValueError(f"{who}: ridge = {ridge} (a positive number: B must be positive definite)")
-    if not bool(torch.isfinite(sigma).all()) or not bool(torch.isfinite(mu).all()):
-        raise ValueError(f"{who}: the moments hold values that are not finite")
-    if sigma.device.type != "cuda":
-        raise ValueError(f"{who}: the moments are on {sigma.device}; the kernels run on the MI355X (there is no host path)")
-    dev, mu = sigma.device, mu.contiguous()
-    S = sigma.clone(memory_format=torch.contiguous_format)
-    S.diagonal().add_(2.0 * ridge)
-    offs = [0] + list(itertools.accumulate(widths))
-    W = torch.zeros(O, O, dtype=torch.float64, device=dev)
-    lows, highs, view_sweeps = [], [], []
-    for lo, hi in zip(offs, offs[1:]):
-        Bi = sigma[lo:hi, lo:hi].clone(memory_format=torch.contiguous_format)
-        Bi.diagonal().add_(ridge)
-        e = sym_eig(Bi)
-        lam, Q = e["values"], e["vectors"].contiguous()
-        lows.append(lam.min())
-        highs.append(lam.max())
-        view_sweeps.append(e["sweeps"])
-        f64_gemm_ld(Q, Q, W[lo:hi, lo:hi], trans_b=True, scale=lam.rsqrt())
-    lows, highs = torch.stack(lows).tolist(), torch.stack(highs).tolist()
-    if not all(l > 0.0 for l in lows) or not bool(torch.isfinite(W).all()):
-        raise ValueError(f"{who}: a view's covariance + ridge I is singular in float64 (smallest eigenvalues {lows}); "
-                         f"raise `ridge`")
-    T, N = torch.empty_like(W), torch.empty_like(W)
-    for lo, hi in zip(offs, offs[1:]):
-        f64_gemm_ld(W[lo:hi, lo:hi], S[lo:hi, :], T[lo:hi, :])          # T = W S, a row of blocks per launch
-    for lo, hi in zip(offs, offs[1:]):
-        f64_gemm_ld(T[:, lo:hi], W[lo:hi, lo:hi], N[:, lo:hi])          # N = T W, a column of blocks per launch
-    N = (N + N.t()) * 0.5      # W is symmetric to rounding only; the solver wants the two halves equal
-    e = sym_eig(N)
-    order = torch.sort(e["values"], descending=True, stable=True).indices[:k]
-    U = e["vectors"][:, order].contiguous()
-    P = torch.empty(O, k, dtype=torch.float64, device=dev)
-    for lo, hi in zip(offs, offs[1:]):
-        f64_gemm_ld(W[lo:hi, lo:hi], U[lo:hi, :], P[lo:hi, :])
-    P = P / torch.linalg.vector_norm(P, dim=0, keepdim=True)
-    return {"correlations": e["values"][order] - 1.0, "projections": [P[lo:hi].contiguous() for lo, hi in zip(offs, offs[1:])],
-            "means": [mu[lo:hi].contiguous() for lo, hi in zip(offs, offs[1:])],
-            "sweeps": {"views": view_sweeps, "joint": e["sweeps"]}, "condition": [l / h for l, h in zip(lows, highs)],
-            "widths": widths, "k": k}
-
-
-def _cca_side(who, name, x, mean, proj):
-    if not torch.is_tensor(x) or x.dim() != 2 or not x.is_floating_point():
-        said = f"{tuple(x.shape)}, {x.dtype}" if torch.is_tensor(x) else type(x).__name__
-        raise ValueError(f"{who}: {name} is {said}; floating (rows, o) features")
-    o = x.shape[1]
-    if not 1 <= o <= H.FRECHET_MAX_F:
-        raise ValueError(f"{who}: {name} has o = {o} features (1 .. {H.FRECHET_MAX_F} are on the MI355X path)")
-    for what, t, dims in ((f"mean_{name}", mean, 1), (f"proj_{name}", proj, 2)):
-        if not torch.is_tensor(t) or t.dim() != dims or t.shape[0] != o or t.dtype != torch.float64:
-            said = f"{tuple(t.shape)}, {t.dtype}" if torch.is_tensor(t) else type(t).__name__
-            raise ValueError(f"{who}: {what} is {said}; float64 ({o},{'' if dims == 1 else ' k'}) beside {name}")
-    return x.detach(), mean.contiguous(), proj.contiguous()
-
-
-def cca_score(a, b, mean_a, mean_b, proj_a, proj_b):
-    """The cross-modal correlation of paired feature rows a (rows, o_a), b (rows, o_b) under a fit (cca_fit's means and
-    projections, float64 (o,) and (o, k)): per row r, p = (a_r - mean_a) proj_a, q = (b_r - mean_b) proj_b and
-    cos_r = p . q / (max(|p|, 1e-8) max(|q|, 1e-8)), F.cosine_similarity's clamp.  One kernel: the rows are converted and
-    centred in double as they are loaded, both products run on the fp64 MFMA, the projections are never written.
-    -> (cos (rows,) float64, their sum, a float64 0-d tensor added in a fixed order: two runs give the same bits)."""
-    who = "cca_score"
-    a, mean_a, proj_a = _cca_side(who, "a", a, mean_a, proj_a)
-    b, mean_b, proj_b = _cca_side(who, "b", b, mean_b, proj_b)
-    rows, k = a.shape[0], proj_a.shape[1]
-    if b.shape[0] != rows or not 1 <= rows <= H.CCA_MAX_ROWS:
-        raise ValueError(f"{who}: a has {rows} rows, b {b.shape[0]} (the same rows of both views, at least one)")
-    if proj_b.shape[1] != k or not 1 <= k <= H.CCA_MAX_K:
-        raise ValueError(f"{who}: proj_a has k = {k} columns, proj_b {proj_b.shape[1]} (the same 1 .. {H.CCA_MAX_K} on the "
-                         f"MI355X path)")
-    if a.device.type != "cuda":
-        raise ValueError(f"{who}: a is on {a.device}; the kernel runs on the MI355X (there is no host path)")
-    a, b = H.f32c(a), H.f32c(b)
-    if not bool(torch.isfinite(a).all() & torch.isfinite(b).all()):      # (one read for both views)
-        raise ValueError(f"{who}: the features hold values that are not finite")
-    cos = torch.empty(rows, dtype=torch.float64, device=a.device)
-    total = torch.empty(1, dtype=torch.float64, device=a.device)
-    _call("mmvae_cca_score", H.ptr(a), H.ptr(b), H.ptr(mean_a), H.ptr(mean_b), H.ptr(proj_a), H.ptr(proj_b), H.ptr(cos),
-          H.ptr(total), rows, a.shape[1], b.shape[1], k, H.stream())
-    return cos, total[0]
-
-
-def sentence_features(ids, emb, weights, eos=2, pc=None):
-    """Frequency-weighted sentence embeddings, the reference's apply_weights and apply_pc (eval/mnistsvhn_helper.py:165-177):
-    ids (B, T) integer tokens, emb (V, E) the embedding table, weights (V,) the tokens' weights (coherence.sif_weights).
-    Per sentence L = index of the first `eos` + 1 (T without one), f = (sum_{t < L} weights[id_t] emb[id_t]) / L in double
-    in token order; with `pc` (E,) float64, a unit vector, f <- f - pc (pc . f), the common component removed.  One wave per
-    sentence, one rounding to fp32.  -> (B, E) fp32.  1 <= E <= 1024, 1 <= T <= 512; every id must lie in [0, V)."""
-    who = "sentence_features"
-    if not torch.is_tensor(ids) or ids.dim() != 2 or ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool:
-        raise ValueError(f"{who}: ids are integer (B, T) tokens")
-    if not torch.is_tensor(emb) or emb.dim() != 2 or not emb.is_floating_point():
-        raise ValueError(f"{who}: emb is the floating (V, E) embedding table")
-    (B, T), (V, E) = ids.shape, emb.shape
-    if not 1 <= E <= H.SENTENCE_MAX_E or not 1 <= T <= H.SENTENCE_MAX_T or B < 1 or V < 1:
-        raise ValueError(f"{who}: B = {B} sentences of T = {T} tokens, V = {V} embeddings of E = {E} (1 <= T <= "
-                         f"{H.SENTENCE_MAX_T}, 1 <= E <= {H.SENTENCE_MAX_E} are on the MI355X path)")
-    if not torch.is_tensor(weights) or tuple(weights.shape) != (V,) or not weights.is_floating_point():
-        raise ValueError(f"{who}: weights are floating ({V},), one per embedding")
-    if pc is not None and (not torch.is_tensor(pc) or tuple(pc.shape) != (E,) or pc.dtype != torch.float64):
-        raise ValueError(f"{who}: pc is a float64 ({E},) unit vector, or None")
-    lo, hi = int(ids.min()), int(ids.max())
-    if lo < 0 or hi >= V:
-        raise ValueError(f"{who}: ids in [{lo}, {hi}] outside the table's [0, {V})")
-    if emb.device.type != "cuda":
-        raise ValueError(f"{who}: emb is on {emb.device}; the kernel runs on the MI355X (there is no host path)")
-    dev = emb.device
-    ids = ids.detach().to(device=dev, dtype=torch.int32).contiguous()
-    emb, weights = H.f32c(emb.detach()), H.f32c(weights.detach().to(dev))
-    pc = None if pc is None else pc.detach().to(dev).contiguous()
-    out = torch.empty(B, E, dtype=torch.float32, device=dev)
-    _call("mmvae_sentence_features", H.ptr(ids), H.ptr(emb), H.ptr(weights), H.ptr(pc), H.ptr(out), B, T, E, V, int(eos),
-          H.stream())
-    return out
-
-
-# ---- image reconstruction quality (csrc/image_quality.hip): PSNR, SSIM, MS-SSIM; float64, forward only -------------------------
-MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)      # Wang et al. 2003, five scales
-
-
-def image_quality_window(win=11, sigma=1.5):
-    """the 1-D window weights in double, summing to 1 (their outer product is the 2-D window): g[i] ~ exp(-(i - (win - 1) / 2)^2
-    / (2 sigma^2)), or 1 / win each for sigma None"""
-    if sigma is None:
-        return np.full(win, 1.0 / win)
-    g = np.exp(-((np.arange(win, dtype=np.float64) - (win - 1) / 2.0) ** 2) / (2.0 * float(sigma) ** 2))
-    return g / g.sum()
-
-
-def image_quality(x, y, win=11, sigma=1.5, data_range=1.0, k1=0.01, k2=0.03, sample_covariance=False, scales=1, weights=None):
-    """How close the images y are to the images x, pair by pair: x, y floating (N, C, H, W), read as fp32, everything after
-    the load in float64, one launch, one workgroup per pair (csrc/image_quality.hip; mmvae_hip.h has the arithmetic).
-      mse, mae   means of (x - y)^2 and |x - y| over C H W;  psnr = 10 log10(data_range^2 / mse), +inf for mse = 0;
-      ssim       Wang et al. 2004: the mean over the C planes of the mean over the (H - win + 1)(W - win + 1) valid window
-                 positions (no padding) of l cs, l = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1), cs = (2 s_xy + C2) /
-                 (s_x^2 + s_y^2 + C2), C1 = (k1 data_range)^2, C2 = (k2 data_range)^2, moments under the window: Gaussian
-                 of `sigma` (the paper's: win 11, sigma 1.5), or uniform for sigma None; `sample_covariance` scales the
-                 (co)variances by win^2 / (win^2 - 1) (scikit-image's default call: win 7, sigma None, sample_covariance True);
-      ms_ssim    `scales` = S levels, level s + 1 the 2 x 2 average pooling of level s (needs even sides; every level sides >=
-                 win): prod_{s < S} max(cs_s, 0)^w_s max(l_S, 0)^w_S of the image's per-level means (over positions, then
-                 channels), clamped at 0 before the powers; S = 1: max(ssim, 0).  `weights` (S,) default to the first S of
-                 (0.0448, 0.2856, 0.3001, 0.2363, 0.1333) divided by their sum -- for S < 5 that is NOT the five-scale
-                 standard, whose images must have sides >= 16 win;
-      levels     (N, S): cs_1 .. cs_{S-1}, l_S.
-    -> {"mse", "mae", "psnr", "ssim", "ms_ssim": (N,) float64, "levels": (N, S) float64} on the device.  No map and no pooled
-    plane is written, no atomics, every sum in a fixed order: a row's bits do not depend on the other rows of the call.
-    win odd in 3 .. 11, win <= H, W <= 64, 1 <= C <= 4, 1 <= S <= 4, finite inputs."""
-    who = "image_quality"
-    for what, t in (("x", x), ("y", y)):
-        if not torch.is_tensor(t) or t.dim() != 4 or not t.is_floating_point():
-            said = f"{tuple(t.shape)}, {t.dtype}" if torch.is_tensor(t) else type(t).__name__
-            raise ValueError(f"{who}: {what} is {said}; floating (N, C, H, W) images")
-    if x.shape != y.shape or x.device != y.device:
-        raise ValueError(f"{who}: x is {tuple(x.shape)} on {x.device}, y {tuple(y.shape)} on {y.device} (pairs of images: the "
-                         f"same shape and device)")
-    N, C, Hh, W = x.shape
-    plan = image_quality_plan((N, C, Hh, W), win, sigma, data_range, k1, k2, sample_covariance, scales, weights)
-    if x.device.type != "cuda":
-        raise ValueError(f"{who}: x is on {x.device}; the kernel runs on the MI355X (there is no host path)")
-    x, y = H.f32c(x.detach()), H.f32c(y.detach())
-    _finite(who, "x", x)
-    _finite(who, "y", y)
-    win, S = plan["win"], plan["scales"]
-    out = torch.empty(N, 5 + S, dtype=torch.float64, device=x.device)
-    _call("mmvae_image_quality", H.ptr(x), H.ptr(y), H.ptr(out), N, C, Hh, W, win, (ctypes.c_double * win)(*plan["window"]),
-          plan["data_range"], plan["c1"], plan["c2"], plan["cov_scale"], S, (ctypes.c_double * S)(*plan["weights"]), H.stream())
-    return {"mse": out[:, 0], "mae": out[:, 1], "psnr": out[:, 2], "ssim": out[:, 3], "ms_ssim": out[:, 4],
-            "levels": out[:, 5:]}
-
-
-def image_quality_plan(shape, win=11, sigma=1.5, data_range=1.0, k1=0.01, k2=0.03, sample_covariance=False, scales=1,
-                       weights=None):
-    """image_quality's checks of its arguments against the images' shape (N, C, H, W), before any device call: ValueError, or
-    -> {"win", "scales", "window": win doubles, "weights": S doubles, "data_range", "c1", "c2", "cov_scale"}"""
-    who = "image_quality"
-    N, C, Hh, W = (int(v) for v in shape)
-    win, S = int(win), int(scales)
-    if not H.IQ_MIN_WIN <= win <= H.IQ_MAX_WIN or win % 2 == 0:
-        raise ValueError(f"{who}: win = {win} (odd, {H.IQ_MIN_WIN} .. {H.IQ_MAX_WIN} are on the MI355X path)")
-    if not (win <= Hh <= H.IQ_MAX_SIDE and win <= W <= H.IQ_MAX_SIDE):
-        raise ValueError(f"{who}: planes of {Hh} x {W} for win = {win} (sides of win .. {H.IQ_MAX_SIDE} are on the MI355X path)")
-    if not 1 <= C <= H.IQ_MAX_CHANNELS or not 1 <= N <= H.IQ_MAX_ROWS:
-        raise ValueError(f"{who}: {N} images of {C} channels (at least one image, 1 .. {H.IQ_MAX_CHANNELS} channels are on the "
-                         f"MI355X path)")
-    if not 1 <= S <= H.IQ_MAX_SCALES:
-        raise ValueError(f"{who}: scales = {S} (1 .. {H.IQ_MAX_SCALES} are on the MI355X path)")
-    h, w = Hh, W
-    for level in range(2, S + 1):
-        if h % 2 or w % 2:
-            raise ValueError(f"{who}: level {level - 1} is {h} x {w}; pooling it into level {level} needs even sides")
-        h, w = h // 2, w // 2
-        if h < win or w < win:
-            raise ValueError(f"{who}: level {level} is {h} x {w}, smaller than win = {win} ({Hh} x {W} images allow scales <= "
-                             f"{level - 1})")
-    if sigma is not None and not (math.isfinite(float(sigma)) and float(sigma) > 0.0):
-        raise ValueError(f"{who}: sigma = {sigma} (a positive width, or None for the uniform window)")
-    L, k1, k2 = float(data_range), float(k1), float(k2)
-    if not (math.isfinite(L) and L > 0.0 and math.isfinite(k1) and k1 > 0.0 and math.isfinite(k2) and k2 > 0.0):
-        raise ValueError(f"{who}: data_range = {data_range}, k1 = {k1}, k2 = {k2} (positive and finite)")
-    if weights is None:
-        msw = np.asarray(MS_SSIM_WEIGHTS[:S], dtype=np.float64)
-        msw = msw / msw.sum()
-    else:
-        msw = np.asarray(weights.detach().cpu().double().numpy() if torch.is_tensor(weights) else weights,
-                         dtype=np.float64).reshape(-1)
-        if msw.shape[0] != S or not np.all(np.isfinite(msw)) or np.any(msw < 0.0):
-            raise ValueError(f"{who}: weights holds {msw.shape[0]} values for scales = {S} (one finite exponent >= 0 per level)")
-    return {"win": win, "scales": S, "window": image_quality_window(win, sigma).tolist(), "weights": msw.tolist(),
-            "data_range": L, "c1": (k1 * L) ** 2, "c2": (k2 * L) ** 2,
-            "cov_scale": win * win / (win * win - 1.0) if sample_covariance else 1.0}
-
-
-# ---- text generation quality (csrc/text_quality.hip): edit distance, BLEU and ROUGE-L counts, NLL; forward only -----------------
-def text_quality_plan(Th, Tr, V, eos=None, trim=None, sep=None, max_order=4):
-    """text_quality's checks of its arguments against the sequences' steps Th (hypothesis), Tr (reference) and the
-    vocabulary V, before any device call: ValueError, or -> {"eos", "trim", "sep": ids, -1 for None; "max_order"}"""
-    who = "text_quality"
-    Th, Tr, V, K = int(Th), int(Tr), int(V), int(max_order)
-    if not (1 <= Th <= H.TQ_MAX_STEPS and 1 <= Tr <= H.TQ_MAX_STEPS):
-        raise ValueError(f"{who}: hypotheses of {Th} steps, references of {Tr} (1 .. {H.TQ_MAX_STEPS} steps are on the MI355X "
-                         f"path)")
-    if not 2 <= V <= H.TQ_MAX_VOCAB:
-        raise ValueError(f"{who}: V = {V} (2 .. {H.TQ_MAX_VOCAB} symbols are on the MI355X path)")
-    if not 1 <= K <= H.TQ_MAX_ORDER:
-        raise ValueError(f"{who}: max_order = {K} (n-gram orders 1 .. {H.TQ_MAX_ORDER})")
-    ids = {}
-    for what, v in (("eos", eos), ("trim", trim), ("sep", sep)):
-        if v is not None and (isinstance(v, bool) or int(v) != v or not 0 <= int(v) < V):
-            raise ValueError(f"{who}: {what} = {v!r} (a token id in [0, {V}), or None)")
-        ids[what] = -1 if v is None else int(v)
-    if ids["sep"] >= 0 and ids["sep"] == ids["eos"]:
-        raise ValueError(f"{who}: sep = eos = {ids['sep']} (the separator must differ from the end marker)")
-    return dict(ids, max_order=K)
-
-
-def _tq_ids(who, what, t, shape, V):
-    """contiguous int32 ids of `shape` (a None entry: any size >= 1), every id in [0, V) (V None: unchecked), or ValueError"""
-    if not torch.is_tensor(t) or t.dim() != len(shape) or t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
-        said = f"{tuple(t.shape)}, {t.dtype}" if torch.is_tensor(t) else type(t).__name__
-        raise ValueError(f"{who}: {what} is {said}; integers of shape {shape}".replace("None", "T"))
-    if any(s is not None and d != s for d, s in zip(t.shape, shape)):
-        raise ValueError(f"{who}: {what} is {tuple(t.shape)}, not {shape}".replace("None", "T"))
-    t = t.detach()
-    if V is not None and t.numel() and not (0 <= int(t.min()) and int(t.max()) < V):
-        raise ValueError(f"{who}: {what} holds ids from {int(t.min())} to {int(t.max())} (token ids lie in [0, {V}))")
-    return t.to(torch.int32).contiguous()
-
-
-def text_quality(hyp, ref_ids, ref_lengths, hyp_lengths=None, eos=None, trim=None, sep=None, max_order=4):
-    """How close the token sequences `hyp` are to the references, pair by pair, in one launch, one wave per pair
-    (csrc/text_quality.hip; mmvae_hip.h has the arithmetic).  hyp: floating (N, Th, V) logits, read as fp32 -- the hypothesis
-    is their argmax, the first maximum of every step -- or integer (N, Th) ids.  ref_ids integer (N, Tr), ref_lengths integer
-    (N,), hyp_lengths integer (N,) or None (Th each); lengths are clamped into [0, T].  eos: a sequence ends before its first
-    eos; trim: trailing tokens equal to trim are then dropped; both sides alike, giving h (Lh tokens) and r (Lr).
-      token   hyp_len Lh, ref_len Lr, same = #{t < min(Lh, Lr): h_t == r_t}, edit = Levenshtein distance, lcs = longest common
-              subsequence, match (N, 4) / total (N, 4): for n = 1 .. max_order the clipped n-gram matches sum_g min(count_h(g),
-              count_r(g)) and max(Lh - n + 1, 0); columns n > max_order are 0.
-      word    with sep: the same (without `same`) over the words, the maximal runs of tokens != sep; None without.
-      pred    (N, Th) the argmax;  nll (N,) float64 = sum_{t < S} (logsumexp(x_t) - x_t[ref_t]), S = min(ref length, Th) =
-              nll_steps (N,): before eos / trim, the decoder's objective.  All three None for an ids hypothesis.
-    -> {"token": {...}, "word": {...} or None, "pred", "nll", "nll_steps", "max_order"}, int32 tensors on the device.  No
-    atomics; a pair's outputs do not depend on the other pairs.  1 <= Th, Tr <= 256, 2 <= V <= 256 (ids form: ids < 256),
-    ids in [0, V), sep != eos.  The logits are expected finite and are not scanned (torch's isfinite().all() is five launches over
-    the whole tensor): a step that holds a NaN or +inf shows as a NaN in the pair's nll."""
-    who = "text_quality"
-    if not torch.is_tensor(hyp) or not ((hyp.is_floating_point() and hyp.dim() == 3) or
-                                        (not hyp.is_floating_point() and hyp.dim() == 2)):
-        said = f"{tuple(hyp.shape)}, {hyp.dtype}" if torch.is_tensor(hyp) else type(hyp).__name__
-        raise ValueError(f"{who}: hyp is {said}; floating (N, Th, V) logits or integer (N, Th) ids")
-    logits = hyp.is_floating_point()
-    N, Th = hyp.shape[:2]
-    V = hyp.shape[2] if logits else H.TQ_MAX_VOCAB
-    if not torch.is_tensor(ref_ids) or ref_ids.dim() != 2:
-        said = f"{tuple(ref_ids.shape)}, {ref_ids.dtype}" if torch.is_tensor(ref_ids) else type(ref_ids).__name__
-        raise ValueError(f"{who}: ref_ids is {said}; integers of shape (N, Tr)")
-    Tr = ref_ids.shape[1]
-    if not 1 <= N <= H.TQ_MAX_ROWS:
-        raise ValueError(f"{who}: {N} pairs (1 .. {H.TQ_MAX_ROWS} a call: one workgroup per pair in one launch)")
-    plan = text_quality_plan(Th, Tr, V, eos, trim, sep, max_order)
-    ref_ids = _tq_ids(who, "ref_ids", ref_ids, (N, None), V)
-    ref_lengths = _tq_ids(who, "ref_lengths", ref_lengths, (N,), None)
-    if hyp_lengths is not None:
-        hyp_lengths = _tq_ids(who, "hyp_lengths", hyp_lengths, (N,), None)
-    hyp = H.f32c(hyp.detach()) if logits else _tq_ids(who, "hyp", hyp, (N, Th), V)
-    dev = hyp.device
-    if any(t is not None and t.device != dev for t in (ref_ids, ref_lengths, hyp_lengths)):
-        raise ValueError(f"{who}: hyp is on {dev}, the references or lengths elsewhere (one device)")
-    if dev.type != "cuda":
-        raise ValueError(f"{who}: hyp is on {dev}; the kernel runs on the MI355X (there is no host path)")
-    K = plan["max_order"]
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    tok, word = i32(N, 13), (i32(N, 12) if plan["sep"] >= 0 else None)
-    pred, nll, steps = (i32(N, Th), torch.empty(N, dtype=torch.float64, device=dev), i32(N)) if logits else (None,) * 3
-    _call("mmvae_text_quality", H.ptr(hyp) if logits else None, None if logits else H.ptr(hyp), H.ptr(ref_ids),
-          H.ptr(ref_lengths), H.ptr(hyp_lengths), H.ptr(pred), H.ptr(tok), H.ptr(word), H.ptr(nll), H.ptr(steps), N, Th, Tr, V,
-          plan["eos"], plan["trim"], plan["sep"], K, H.stream())
-    level = lambda o, same: dict(
-        {"hyp_len": o[:, 0], "ref_len": o[:, 1], "edit": o[:, 2 + same], "lcs": o[:, 3 + same],
-         "match": o[:, 4 + same:8 + same], "total": o[:, 8 + same:12 + same]}, **({"same": o[:, 2]} if same else {}))
-    return {"token": level(tok, 1), "word": None if word is None else level(word, 0), "pred": pred, "nll": nll,
-            "nll_steps": steps, "max_order": K}
-
-
-def _tq_level_summary(parts, K, token):
-    """the summary of one level from the per-pair integer counts of `parts` (dicts of (n,) / (n, 4) integer tensors)"""
-    cat = lambda name: np.concatenate([p[name].detach().cpu().numpy().astype(np.int64) for p in parts])
-    hl, rl, edit, lcs, match, total = (cat(k) for k in ("hyp_len", "ref_len", "edit", "lcs", "match", "total"))
-    n = len(hl)
-    Hs, Rs = int(hl.sum()), int(rl.sum())
-    ms, ts = [int(v) for v in match[:, :K].sum(0)], [int(v) for v in total[:, :K].sum(0)]
-    bp = lambda h, r: math.exp(1.0 - r / h) if h < r else 1.0
-    if Hs == 0 or any(m == 0 for m in ms):
-        bleu = 0.0
-    else:
-        bleu = bp(Hs, Rs) * math.exp(sum(math.log(m / t) for m, t in zip(ms, ts)) / K)
-    sent, rouge = [], []
-    for i in range(n):
-        h, r, l = int(hl[i]), int(rl[i]), int(lcs[i])
-        if h == 0 or match[i, 0] == 0:
-            sent.append(0.0)
-        else:
-            logs = [math.log(int(match[i, 0]) / int(total[i, 0]))]
-            logs += [math.log((int(match[i, k]) + 1) / (int(total[i, k]) + 1)) for k in range(1, K)]
-            sent.append(bp(h, r) * math.exp(sum(logs) / K))
-        P, R = (l / h if h else 0.0), (l / r if r else 0.0)
-        rouge.append(2.0 * P * R / (P + R) if P + R > 0.0 else 0.0)
-    E = int(edit.sum())
-    out = {"n": n, "error_rate": E / Rs if Rs else (0.0 if E == 0 else float("inf")),
-           "exact": float(np.count_nonzero(edit == 0)) / n, "bleu": bleu,
-           "precisions": [m / t if t else 0.0 for m, t in zip(ms, ts)], "sentence_bleu": math.fsum(sent) / n,
-           "rouge_l": math.fsum(rouge) / n}
-    if token:
-        out["accuracy"] = int(cat("same").sum()) / Rs if Rs else 0.0
-    return out
-
-
-def text_quality_summary(parts):
-    """The corpus figures of one or several text_quality results (a dict, or a list of them with one max_order), on the host,
-    from the INTEGER sums of the per-pair counts.  -> {"token": S, "word": S or None}, S per level:
-      n               pairs;
-      error_rate      sum edit / sum ref_len: the character / word error rate (CER / WER) where a token is a character
-                      (0 / 0 = 0, x / 0 = inf);
-      exact           mean(edit == 0);
-      accuracy        sum same / sum ref_len (token level only);
-      bleu            corpus BLEU (Papineni et al. 2002): brevity penalty times the geometric mean over the orders 1 .. K of
-                      sum match_n / sum total_n; brevity penalty exp(1 - sum ref_len / sum hyp_len) when sum hyp_len <
-                      sum ref_len; 0 when a sum match_n or sum hyp_len is 0;
-      precisions      [sum match_n / sum total_n for n = 1 .. K] (0 for an empty total);
-      sentence_bleu   mean over the pairs of the pair's BLEU with Lin & Och's (2004) add-one smoothing of the orders n >= 2,
-                      (match_n + 1) / (total_n + 1), order 1 unsmoothed (no unigram match: 0), the pair's own brevity penalty,
-                      0 for an empty hypothesis;
-      rouge_l         mean over the pairs of F1 = 2 P R / (P + R), P = lcs / hyp_len, R = lcs / ref_len (a zero denominator: 0);
-      nll, perplexity, bits_per_token   (token level; None for ids hypotheses) sum nll / sum nll_steps, its exp, and it
-                      divided by ln 2; nan when no step was scored."""
-    parts = [parts] if isinstance(parts, dict) else list(parts)
-    if not parts:
-        raise ValueError("text_quality_summary: no parts")
-    K = {int(p["max_order"]) for p in parts}
-    if len(K) != 1 or len({p["word"] is None for p in parts}) != 1 or len({p["nll"] is None for p in parts}) != 1:
-        raise ValueError("text_quality_summary: the parts were scored with different max_order, sep or hypothesis forms")
-    K = K.pop()
-    token = _tq_level_summary([p["token"] for p in parts], K, True)
-    word = None if parts[0]["word"] is None else _tq_level_summary([p["word"] for p in parts], K, False)
-    if parts[0]["nll"] is None:
-        token.update(nll=None, perplexity=None, bits_per_token=None)
-    else:
-        steps = sum(int(p["nll_steps"].sum()) for p in parts)
-        total = math.fsum(v for p in parts for v in p["nll"].detach().cpu().tolist())
-        mean = total / steps if steps else float("nan")
-        token.update(nll=mean, perplexity=math.exp(mean), bits_per_token=mean / math.log(2.0))
-    return {"token": token, "word": word}
-
-
-# ---- aggregate posterior, ELBO decomposition and mutual information gap (csrc/aggpost.hip): float64, forward only -----------
-def _aggpost_rows(who, what, X, like=None):
-    """contiguous fp32 (N, D) or ValueError: shape, dtype, the limits, the shape and device of `like`, finite values"""
-    if not torch.is_tensor(X) or X.dim() != 2 or not X.is_floating_point():
-        said = f"{tuple(X.shape)}, {X.dtype}" if torch.is_tensor(X) else type(X).__name__
-        raise ValueError(f"{who}: {what} is {said}; floating (N, D)")
-    N, D = X.shape
-    if not 1 <= N <= H.AGGPOST_MAX_ROWS or not 1 <= D <= H.AGGPOST_MAX_DIM:
-        raise ValueError(f"{who}: {what} is {N} x {D} (1 .. {H.AGGPOST_MAX_ROWS} rows of 1 .. {H.AGGPOST_MAX_DIM} dimensions "
-                         f"are on the MI355X path)")
-    if like is not None and (X.shape != like.shape or X.device != like.device):
-        raise ValueError(f"{who}: {what} is {tuple(X.shape)} on {X.device}, z {tuple(like.shape)} on {like.device}")
-    if not X.is_contiguous():
-        raise ValueError(f"{who}: {what} is not contiguous")
-    X = X.detach()
-    X = X.float() if X.dtype != torch.float32 else X
-    if not bool(torch.isfinite(X).all()):
-        raise ValueError(f"{who}: {what} holds values that are not finite")
-    return X
-
-
-def _aggpost_labels(who, labels, N, device):
-    """contiguous int32 (K, N) on `device` or ValueError: an integer (K, N) tensor, 1 <= K <= the limit, labels >= 0"""
-    if not torch.is_tensor(labels) or labels.dim() != 2 or labels.is_floating_point() or labels.is_complex() \
-            or labels.dtype == torch.bool:
-        said = f"{tuple(labels.shape)}, {labels.dtype}" if torch.is_tensor(labels) else type(labels).__name__
-        raise ValueError(f"{who}: labels is {said}; an integer (K, N) tensor, one row per generative factor")
-    K = labels.shape[0]
-    if not 1 <= K <= H.AGGPOST_MAX_FACTORS or labels.shape[1] != N:
-        raise ValueError(f"{who}: labels is {tuple(labels.shape)}; (K, {N}) with 1 <= K <= {H.AGGPOST_MAX_FACTORS} factors")
-    if labels.device != device:
-        raise ValueError(f"{who}: labels is on {labels.device}, z on {device}")
-    if not labels.is_contiguous():
-        raise ValueError(f"{who}: labels is not contiguous")
-    labels = labels.detach()
-    if int(labels.min()) < 0 or int(labels.max()) > 2 ** 31 - 1:
-        raise ValueError(f"{who}: labels holds values outside [0, 2^31) (classes are numbered from 0)")
-    return labels.to(torch.int32)
-
-
-def aggregate_posterior(z, loc, scale, laplace=False, labels=None, chunks=0):
-    """The aggregate posterior q(z) = (1/N) sum_m q(z | x_m) at every sample: z, loc, scale (N,D), row n of z a draw from
-    posterior n = Normal | Laplace (`laplace`) (loc_n, scale_n); labels (K,N) integers >= 0, one row per generative factor,
-    or None.  With l[n,m,d] = log q(z_nd | x_m) in double from the fp32 inputs:
-      joint (N,)              log q(z_n)  = logsumexp_m sum_d l[n,m,d] - log N
-      marginal (N,D)          log q(z_nd) = logsumexp_m l[n,m,d] - log N
-      conditional (K,N,D)     logsumexp over the m that share factor k's value with n of l[n,m,d] - log(class size); None
-                              without labels
-      self (N,)               sum_d l[n,n,d] = log q(z_n | x_n)       (torch float64 on the device)
-    float64; the N x N x D terms are never written.  `chunks`: how many workgroups share a row's posterior rows (0: the
-    default plan); two plans regroup fp64 sums (agreement to rounding, not bit for bit), two runs with one plan give the
-    same bits.  A z that lies so far from its own posterior that exp overflows raises FloatingPointError."""
-    who = "aggregate_posterior"
-    chunks = _chunks(who, chunks, "chunks")
-    z = _aggpost_rows(who, "z", z)
-    loc, scale = _aggpost_rows(who, "loc", loc, z), _aggpost_rows(who, "scale", scale, z)
-    if not bool((scale > 0).all()):
-        raise ValueError(f"{who}: scale holds values that are not positive")
-    N, D = z.shape
-    lab = None if labels is None else _aggpost_labels(who, labels, N, z.device)
-    K, laplace = 0 if lab is None else lab.shape[0], bool(laplace)
-    if z.device.type != "cuda":
-        raise ValueError(f"{who}: z is on {z.device}; the kernel runs on the MI355X (there is no host path)")
-    ws = torch.empty(H.lib().mmvae_aggpost_ws_doubles(N, D, K, chunks), dtype=torch.float64, device=z.device)
-    joint = torch.empty(N, dtype=torch.float64, device=z.device)
-    marginal = torch.empty(N, D, dtype=torch.float64, device=z.device)
-    cond = None if lab is None else torch.empty(K, N, D, dtype=torch.float64, device=z.device)
-    _call("mmvae_aggpost_lse", H.ptr(z), H.ptr(loc), H.ptr(scale), int(laplace), H.ptr(lab), H.ptr(ws), H.ptr(joint),
-          H.ptr(marginal), H.ptr(cond), N, D, K, chunks, H.stream())
-    s = scale.double()
-    t = (z.double() - loc.double()) / s
-    own = (-t.abs() - torch.log(2.0 * s)) if laplace else (-0.5 * t * t - torch.log(s) - 0.5 * math.log(2.0 * math.pi))
-    if not bool(torch.isfinite(joint).all()) or not bool(torch.isfinite(marginal).all()):
-        raise FloatingPointError(f"{who}: a row of z lies so far from its own posterior that exp(l - l[n,n]) overflows "
-                                 f"(z must be a draw from the posterior of its row)")
-    return {"joint": joint, "marginal": marginal, "conditional": cond, "self": own.sum(1)}
-
-
-_AGG_KEYS = ("joint", "marginal", "conditional", "self")
-
-
-def _aggpost_result(who, agg):
-    """the (joint, marginal, conditional, self) of an aggregate_posterior result or ValueError"""
-    if not isinstance(agg, dict) or any(k not in agg for k in _AGG_KEYS):
-        raise ValueError(f"{who}: agg must be the dict aggregate_posterior returns ({', '.join(_AGG_KEYS)})")
-    joint, marginal, cond, own = (agg[k] for k in _AGG_KEYS)
-    for what, t, dims in (("joint", joint, 1), ("marginal", marginal, 2), ("self", own, 1)):
-        if not torch.is_tensor(t) or t.dtype != torch.float64 or t.dim() != dims:
-            raise ValueError(f"{who}: agg[{what!r}] must be a float64 tensor of {dims} dimension(s)")
-    N, D = marginal.shape
-    if joint.shape != (N,) or own.shape != (N,) or N < 1 or D < 1:
-        raise ValueError(f"{who}: agg holds joint {tuple(joint.shape)}, self {tuple(own.shape)}, marginal {(N, D)}")
-    if cond is not None and (not torch.is_tensor(cond) or cond.dtype != torch.float64 or cond.dim() != 3
-                             or cond.shape[1:] != (N, D)):
-        raise ValueError(f"{who}: agg['conditional'] must be None or float64 (K, {N}, {D})")
-    return joint, marginal, cond, own
-
-
-def elbo_decomposition(agg, lpz):
-    """The decomposition of the ELBO's KL term (Chen et al. 2018) from an aggregate_posterior result and lpz (N,) = sum_d
-    log p(z_nd) under the prior:
-      mi   = mean_n(log q(z_n | x_n) - log q(z_n))         index-code mutual information
-      tc   = mean_n(log q(z_n) - sum_d log q(z_nd))        total correlation
-      dwkl = mean_n(sum_d log q(z_nd) - log p(z_n))        dimension-wise KL
-      kl   = mean_n(log q(z_n | x_n) - log p(z_n))         = mi + tc + dwkl
-    -> 0-d float64 tensors on the device."""
-    who = "elbo_decomposition"
-    joint, marginal, _, own = _aggpost_result(who, agg)
-    if not torch.is_tensor(lpz) or lpz.shape != joint.shape or not lpz.is_floating_point():
-        said = f"{tuple(lpz.shape)}, {lpz.dtype}" if torch.is_tensor(lpz) else type(lpz).__name__
-        raise ValueError(f"{who}: lpz is {said}; floating ({joint.shape[0]},), the prior's log-density of every row of z")
-    if lpz.device != joint.device:
-        raise ValueError(f"{who}: lpz is on {lpz.device}, agg on {joint.device}")
-    lpz = lpz.detach().double()
-    if not bool(torch.isfinite(lpz).all()):
-        raise ValueError(f"{who}: lpz holds values that are not finite")
-    sum_marginal = marginal.sum(1)
-    return {"mi": (own - joint).mean(), "tc": (joint - sum_marginal).mean(), "dwkl": (sum_marginal - lpz).mean(),
-            "kl": (own - lpz).mean()}
-
-
-def mutual_information_gap(agg, labels):
-    """The mutual information gap (Chen et al. 2018) from an aggregate_posterior result that was given `labels` (K,N):
-      h_z (D,)         H(z_d) = -mean_n log q(z_nd)
-      mi (K,D)         I(z_d; v_k) = H(z_d) - H(z_d | v_k), H(z_d | v_k) = -mean_n conditional[k,n,d] (the mean over all n
-                       weights every class by its frequency)
-      h_v (K,)         H(v_k) from the class counts
-      per_factor (K,)  (largest - second largest of mi[k,:]) / H(v_k);  mig = their mean
-    float64 on the device.  D >= 2, and every factor must take at least two values (H(v_k) > 0)."""
-    who = "mutual_information_gap"
-    _, marginal, cond, _ = _aggpost_result(who, agg)
-    if cond is None:
-        raise ValueError(f"{who}: agg holds no conditional (aggregate_posterior was called without labels)")
-    N, D = marginal.shape
-    lab = _aggpost_labels(who, labels, N, marginal.device)
-    if lab.shape[0] != cond.shape[0]:
-        raise ValueError(f"{who}: labels has {lab.shape[0]} factors, agg['conditional'] {cond.shape[0]}")
-    if D < 2:
-        raise ValueError(f"{who}: D = {D} latent dimension (the gap is between the two most informative dimensions)")
-    h_v = []
-    for k in range(lab.shape[0]):
-        p = torch.bincount(lab[k].long()).double() / N
-        p = p[p > 0]
-        if p.numel() < 2:
-            raise ValueError(f"{who}: factor {k} of labels takes a single value (H(v) = 0: the gap is not defined)")
-        h_v.append(-(p * p.log()).sum())
-    h_v = torch.stack(h_v)
-    h_z = -marginal.mean(0)
-    mi = h_z.unsqueeze(0) + cond.mean(1)
-    top = mi.topk(2, dim=1).values
-    per = (top[:, 0] - top[:, 1]) / h_v
-    return {"mig": per.mean(), "per_factor": per, "mi": mi, "h_z": h_z, "h_v": h_v}
-
-
-def digit_hidden(state, kinds, images):
-    """-> (nets,N,50) fp32: relu(fc1) of the digit classifiers, dropout off (the features of DigitClassifier.features)"""
-    kinds, ktab, xtab, _, N = _digit_args(state, kinds, images)
-    hidden = torch.empty(len(kinds), N, 50, device=state.device)
-    if N > 0:
-        _call("mmvae_digit_hidden", H.ptr(state), ktab, xtab, H.ptr(hidden), len(kinds), state.shape[2], N, H.stream())
-    return hidden
-
-
-# ---- cross-modal retrieval of latents (csrc/retrieval.hip): float64 distances, exact ranks, forward only ---------------------
-def _retrieval_sets(who, what, X, like=None):
-    """contiguous fp32 (S, N, D) or ValueError: shape, dtype, the limits, the shape and device of `like`, finite values"""
-    if not torch.is_tensor(X) or X.dim() != 3 or not X.is_floating_point():
-        said = f"{tuple(X.shape)}, {X.dtype}" if torch.is_tensor(X) else type(X).__name__
-        raise ValueError(f"{who}: {what} is {said}; floating (S, N, D), one (N, D) set of rows per modality")
-    S, N, D = X.shape
-    if not 2 <= S <= H.RETRIEVAL_MAX_SETS or not 1 <= N <= H.RETRIEVAL_MAX_ROWS or not 1 <= D <= H.RETRIEVAL_MAX_DIM:
-        raise ValueError(f"{who}: {what} is {S} sets of {N} x {D} (2 .. {H.RETRIEVAL_MAX_SETS} sets of 1 .. "
-                         f"{H.RETRIEVAL_MAX_ROWS} rows of 1 .. {H.RETRIEVAL_MAX_DIM} dimensions are on the MI355X path)")
-    if like is not None and (X.shape != like.shape or X.device != like.device):
-        raise ValueError(f"{who}: {what} is {tuple(X.shape)} on {X.device}, loc {tuple(like.shape)} on {like.device}")
-    X = X.detach()
-    X = (X.float() if X.dtype != torch.float32 else X).contiguous()
-    _finite(who, what, X)
-    return X
-
-
-def _retrieval_ints(who, what, t, form):
-    """an integer tensor on the host from a tensor, an array or nested lists, or ValueError naming the `form` wanted"""
-    if not torch.is_tensor(t):
-        try:
-            t = torch.from_numpy(np.ascontiguousarray(t))
-        except TypeError:
-            raise ValueError(f"{who}: {what} is {type(t).__name__}; {form}") from None
-    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
-        raise ValueError(f"{who}: {what} is {tuple(t.shape)}, {t.dtype}; {form}")
-    return t.detach().cpu()
-
-
-def retrieval_pairs(S):
-    """every ordered pair (query set, gallery set) of S different sets, in lexicographic order: S (S - 1) pairs"""
-    return [(a, b) for a in range(int(S)) for b in range(int(S)) if a != b]
-
-
-def retrieval_ranks(loc, scale=None, pairs=None, match=None, metric="l2", keep=0, chunks=0):
-    """Retrieval of one set of rows from another, for P ordered pairs of the S sets of `loc` (S, N, D) (the latent means of S
-    modalities, say; `scale` (S, N, D) their standard deviations): per pair (query set, gallery set) and query row i, where
-    does the gallery row match[i] -- the row of the same sample -- rank among all N gallery rows by distance to the query?
-      metric "l2"      sum (mq - mg)^2                    "cosine"  1 - mq . mg / (|mq| |mg|), 1 when either norm is 0
-             "w2"      sum (mq - mg)^2 + (sq - sg)^2      "skl"     KL(q || g) + KL(g || q) of diagonal Gaussians
-      (w2, skl: `scale` is needed, > 0), in double from the fp32 values by direct differences; a pair's distance is a function
-      of its two rows alone, so the comparisons are exact with respect to these distances.
-    `pairs`: integer (P, 2) (query set, gallery set), the two different; None: retrieval_pairs(S).  `match`: integer (N,), -1
-    for a row without a partner; None: the identity.  `keep` <= 16 nearest gallery rows are returned per query.
-    -> {"d_match" (P, N) float64 (NaN without a partner), "less", "equal" (P, N) int32: the gallery rows other than the
-        partner that are nearer / exactly as near (-1 without a partner), "nn_d" (P, N, keep) float64 ascending, "nn_idx" (P, N,
-        keep) int32, ordered by (distance, index), padded with (+inf, -1) when N < keep, "pairs": the list of pairs}.
-    The N x N distances are never written.  `chunks`: how many workgroups share a row's gallery rows (0: the default plan);
-    the result does not depend on it, nor on what other pairs the call holds, bit for bit."""
-    who = "retrieval_ranks"
-    if metric not in H.RETRIEVAL_METRICS:
-        raise ValueError(f"{who}: metric = {metric!r} ({', '.join(H.RETRIEVAL_METRICS)})")
-    keep, chunks = int(keep), _chunks(who, chunks, "chunks of gallery rows")
-    if not 0 <= keep <= H.RETRIEVAL_MAX_KEEP:
-        raise ValueError(f"{who}: keep = {keep} neighbours (0 .. {H.RETRIEVAL_MAX_KEEP} are on the MI355X path)")
-    loc = _retrieval_sets(who, "loc", loc)
-    S, N, D = loc.shape
-    if metric in ("w2", "skl"):
-        if scale is None:
-            raise ValueError(f"{who}: metric {metric!r} compares distributions and needs `scale`")
-        scale = _retrieval_sets(who, "scale", scale, loc)
-        if not bool((scale > 0).all()):
-            raise ValueError(f"{who}: scale holds values that are not positive")
-    else:
-        scale = None      # (l2 and cosine read the means alone)
-    if pairs is None:
-        pairs = retrieval_pairs(S)
-    pt = _retrieval_ints(who, "pairs", pairs, "an integer (P, 2) list of (query set, gallery set)")
-    if pt.dim() != 2 or pt.shape[1] != 2 or not 1 <= pt.shape[0] <= H.RETRIEVAL_MAX_PAIRS:
-        raise ValueError(f"{who}: pairs is {tuple(pt.shape)}; (P, 2) with 1 <= P <= {H.RETRIEVAL_MAX_PAIRS} pairs")
-    if int(pt.min()) < 0 or int(pt.max()) >= S or bool((pt[:, 0] == pt[:, 1]).any()):
-        raise ValueError(f"{who}: pairs must hold two different sets out of 0 .. {S - 1} per row")
-    if match is not None:
-        match = _retrieval_ints(who, "match", match, "an integer (N,) list of gallery rows, -1 for none")
-        if tuple(match.shape) != (N,):
-            raise ValueError(f"{who}: match is {tuple(match.shape)}; ({N},), one gallery row per query row")
-        if int(match.min()) < -1 or int(match.max()) >= N:
-            raise ValueError(f"{who}: match holds entries outside -1 .. {N - 1}")
-    if loc.device.type != "cuda":
-        raise ValueError(f"{who}: loc is on {loc.device}; the kernel runs on the MI355X (there is no host path)")
-    dev, P = loc.device, pt.shape[0]
-    pd = pt.to(device=dev, dtype=torch.int32).contiguous()
-    md = None if match is None else match.to(device=dev, dtype=torch.int32).contiguous()
-    ws = torch.empty(H.lib().mmvae_retrieval_ws_bytes(N, P, keep, chunks) // 8, dtype=torch.float64, device=dev)
-    d_match = torch.empty(P, N, dtype=torch.float64, device=dev)
-    less, equal = (torch.empty(P, N, dtype=torch.int32, device=dev) for _ in range(2))
-    nn_d = torch.empty(P, N, keep, dtype=torch.float64, device=dev)
-    nn_idx = torch.empty(P, N, keep, dtype=torch.int32, device=dev)
-    _call("mmvae_retrieval_ranks", H.ptr(loc), H.ptr(scale), H.ptr(pd), H.ptr(md), H.ptr(ws) if ws.numel() else None,
-          H.ptr(d_match), H.ptr(less), H.ptr(equal), H.ptr(nn_d) if keep else None, H.ptr(nn_idx) if keep else None, N, D, S, P,
-          H.RETRIEVAL_METRICS[metric], keep, chunks, H.stream())
-    return {"d_match": d_match, "less": less, "equal": equal, "nn_d": nn_d, "nn_idx": nn_idx,
-            "pairs": [tuple(r) for r in pt.tolist()]}
-
-
-def _retrieval_ks(who, ks):
-    ks = [int(k) for k in ks]
-    if not ks or min(ks) < 1 or len(set(ks)) != len(ks):
-        raise ValueError(f"{who}: ks = {ks} (different positive numbers of neighbours)")
-    return ks
-
-
-def retrieval_summary(less, equal, ks=(1, 5, 10), n_gallery=None):
-    """Recall@k, median rank and their kin from the `less` and `equal` counts of retrieval_ranks; on the host.
-    PESSIMISTIC ranks: rank = 1 + less + equal -- a gallery row exactly as near as the partner is counted as if it were nearer,
-    so a tie never counts as a hit: N identical embeddings score rank N, not 1, and collapsed posteriors score at the far end
-    rather than as perfect retrieval.  Rows without a partner (less < 0) are left out.  `n_gallery`: the gallery's rows
-    (default: the number of query rows).  Per pair (one dict for (N,) counts, a list of P dicts for (P, N)):
-      "recall@k" = share of rows with rank <= k, "chance@k" = min(k / n_gallery, 1), "median_rank", "mean_rank", "mrr" = mean
-      1 / rank, "normalised_rank" = mean (rank - 1) / (n_gallery - 1) (0 best, 1 worst, 0.5 at chance; 0 for one gallery
-      row), "tied_rows" = rows with equal > 0, "n" = rows with a partner (NaN everywhere but the chances when 0)."""
-    who = "retrieval_summary"
-    ks = _retrieval_ks(who, ks)
-    less = _retrieval_ints(who, "less", less, "the integer (N,) or (P, N) counts of retrieval_ranks").numpy()
-    equal = _retrieval_ints(who, "equal", equal, "the integer (N,) or (P, N) counts of retrieval_ranks").numpy()
-    if less.shape != equal.shape or less.ndim not in (1, 2) or less.shape[-1] < 1:
-        raise ValueError(f"{who}: less is {less.shape}, equal {equal.shape}; the (N,) or (P, N) counts of retrieval_ranks")
-    if bool(((less < 0) != (equal < 0)).any()):
-        raise ValueError(f"{who}: less and equal disagree on the rows without a partner")
-    Ng = less.shape[-1] if n_gallery is None else int(n_gallery)
-    most = int((less.astype(np.int64) + equal).max())
-    if Ng < 1 or most >= Ng:
-        raise ValueError(f"{who}: n_gallery = {Ng} rows for a row with less + equal = {most} other rows")
-
-    def one(l, e):
-        has = l >= 0
-        rank = (1 + l[has].astype(np.int64) + e[has].astype(np.int64)).astype(np.float64)
-        n = int(has.sum())
-        out = {"n": n, "tied_rows": int((e[has] > 0).sum())}
-        for k in ks:
-            out[f"recall@{k}"] = float((rank <= k).mean()) if n else float("nan")
-            out[f"chance@{k}"] = min(k / Ng, 1.0)
-        out["median_rank"] = float(np.median(rank)) if n else float("nan")
-        out["mean_rank"] = float(rank.mean()) if n else float("nan")
-        out["mrr"] = float((1.0 / rank).mean()) if n else float("nan")
-        out["normalised_rank"] = (float(((rank - 1.0) / (Ng - 1)).mean()) if Ng > 1 else 0.0) if n else float("nan")
-        return out
-
-    return one(less, equal) if less.ndim == 1 else [one(l, e) for l, e in zip(less, equal)]
-
-
-def retrieval_label_precision(nn_idx, labels_q, labels_g, ks=(1, 5, 10)):
-    """Do a query's nearest gallery rows carry its label?  nn_idx (N, keep): the neighbour lists of one pair from
-    retrieval_ranks (-1: an empty slot); labels_q (N,), labels_g (gallery rows,) integers; every k of `ks` <= keep.  On the
-    host -> {k: {"precision": the mean over the queries of the share of the (filled) first k slots that carry the query's
-    label, "hit": the share of queries with at least one such row among them}}."""
-    who = "retrieval_label_precision"
-    ks = _retrieval_ks(who, ks)
-    idx = _retrieval_ints(who, "nn_idx", nn_idx, "the integer (N, keep) neighbour lists of one pair").numpy()
-    lq = _retrieval_ints(who, "labels_q", labels_q, "an integer (N,) list, one label per query row").numpy()
-    lg = _retrieval_ints(who, "labels_g", labels_g, "an integer list, one label per gallery row").numpy()
-    if idx.ndim != 2 or lq.shape != (idx.shape[0],) or lg.ndim != 1 or lg.shape[0] < 1:
-        raise ValueError(f"{who}: nn_idx is {idx.shape}, labels_q {lq.shape}, labels_g {lg.shape}; (N, keep), (N,) and (gallery "
-                         f"rows,)")
-    if max(ks) > idx.shape[1]:
-        raise ValueError(f"{who}: ks = {ks} for lists of keep = {idx.shape[1]} neighbours")
-    if idx.size and (int(idx.min()) < -1 or int(idx.max()) >= lg.shape[0]):
-        raise ValueError(f"{who}: nn_idx holds entries outside -1 .. {lg.shape[0] - 1}")
-    filled = idx >= 0
-    if not bool(filled[:, 0].all()):
-        raise ValueError(f"{who}: a query has no neighbour at all")
-    same = filled & (lg[np.where(filled, idx, 0)] == lq[:, None])
-    out = {}
-    for k in ks:
-        share = same[:, :k].sum(1) / filled[:, :k].sum(1)
-        out[k] = {"precision": float(share.mean()), "hit": float(same[:, :k].any(1).mean())}
-    return out
+    H.call("mmvae_fill", H.ptr(t), t.numel(), float(value), H.stream())
+
+
+# ---- the evaluation metrics (forward only, no autograd): one module per kernel file, their public names under `ops` ------
+from .metrics.loglik import *              # noqa: E402,F401,F403
+from .metrics.probe import *               # noqa: E402,F401,F403
+from .metrics.coherence import *           # noqa: E402,F401,F403
+from .metrics.digits import *              # noqa: E402,F401,F403
+from .metrics.tsne import *                # noqa: E402,F401,F403
+from .metrics.frechet import *             # noqa: E402,F401,F403
+from .metrics.manifold import *            # noqa: E402,F401,F403
+from .metrics.kid import *                 # noqa: E402,F401,F403
+from .metrics.cluster import *             # noqa: E402,F401,F403
+from .metrics.gmm import *                 # noqa: E402,F401,F403
+from .metrics.cca import *                 # noqa: E402,F401,F403
+from .metrics.image_quality import *       # noqa: E402,F401,F403
+from .metrics.text_quality import *        # noqa: E402,F401,F403
+from .metrics.aggpost import *             # noqa: E402,F401,F403
+from .metrics.retrieval import *           # noqa: E402,F401,F403

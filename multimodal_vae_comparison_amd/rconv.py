@@ -16,7 +16,6 @@ import torch
 from torch.autograd import Function
 
 from . import hipops as H
-from . import ops
 
 PRE_NONE, PRE_RELU, PRE_BN_RELU = 0, 1, 2
 MASK_NONE, MASK_RAW, MASK_BN = 0, 1, 2
@@ -32,7 +31,7 @@ def tables(device, B, Hh, W, K, S, P):
         Ho, Wo = (Hh + 2 * P - K) // S + 1, (W + 2 * P - K) // S + 1
         fwd = torch.empty(K * K, B * Ho * Wo, dtype=torch.int32, device=device)
         bwd = torch.empty(K * K, B * Hh * W, dtype=torch.int32, device=device)
-        ops._call("mmvae_rc_tables", H.ptr(fwd), H.ptr(bwd), B, Hh, W, K, S, P, H.stream())
+        H.call("mmvae_rc_tables", H.ptr(fwd), H.ptr(bwd), B, Hh, W, K, S, P, H.stream())
         t = _tables[key] = (fwd, bwd)
     return t
 
@@ -151,7 +150,7 @@ IDENT = (1, 1, 1, 1, 0)     # (H, W, K, S, P) of a row-to-row (1x1, stride 1) jo
 def launch(*jobs):
     """independent jobs (H.RcJob) in ONE launch"""
     arr = (H.RcJob * len(jobs))(*jobs)
-    ops._call("mmvae_rc_launch", arr, len(jobs), H.stream())
+    H.call("mmvae_rc_launch", arr, len(jobs), H.stream())
 
 
 def _p(t):
@@ -258,8 +257,8 @@ def _tap(bn, Y, b):
     """forward hooks on a BatchNorm module (the tests' ReLU-mask export) see bn(Y) in the engine's own arithmetic"""
     if bn._forward_hooks:
         out = torch.empty_like(Y)
-        ops._call("mmvae_rc_bn_apply", H.ptr(Y), H.ptr(b["mean"]), H.ptr(b["sc"]), H.ptr(bn.bias), H.ptr(out), Y.shape[0],
-                  Y.shape[1], H.stream())
+        H.call("mmvae_rc_bn_apply", H.ptr(Y), H.ptr(b["mean"]), H.ptr(b["sc"]), H.ptr(bn.bias), H.ptr(out), Y.shape[0],
+               Y.shape[1], H.stream())
         bn(out, tap=True)
 
 
@@ -297,9 +296,9 @@ class BottleneckStack(Function):
             Y3, b3 = _fwd(blk.u3, Y2, M2, M2, PRE_BN_RELU, (b2, blk.u2.bn.bias), IDENT, ev)
             out = torch.empty(M2, Y3.shape[1], device=dev)
             R = Yd if Yd is not None else s
-            ops._call("mmvae_rc_blockout", H.ptr(Y3), H.ptr(b3["mean"]), H.ptr(b3["sc"]), H.ptr(blk.u3.bn.bias), H.ptr(R),
-                      H.ptr(bd["mean"]) if bd else None, H.ptr(bd["sc"]) if bd else None,
-                      H.ptr(blk.ud.bn.bias) if bd else None, int(act == H.ACT_RELU), H.ptr(out), M2, Y3.shape[1], H.stream())
+            H.call("mmvae_rc_blockout", H.ptr(Y3), H.ptr(b3["mean"]), H.ptr(b3["sc"]), H.ptr(blk.u3.bn.bias), H.ptr(R),
+                   H.ptr(bd["mean"]) if bd else None, H.ptr(bd["sc"]) if bd else None,
+                   H.ptr(blk.ud.bn.bias) if bd else None, int(act == H.ACT_RELU), H.ptr(out), M2, Y3.shape[1], H.stream())
             if blk.u3.bn._forward_hooks:
                 blk.u3.bn(out, tap=True)
             saved.append((s, Y1, Y2, Y3, Yd, act, (B, Hh, W, Ho, Wo),
@@ -310,7 +309,7 @@ class BottleneckStack(Function):
         ctx.pool = None
         if pool:
             y = torch.empty(B, s.shape[1], device=dev)
-            ops._call("mmvae_avgpool_fwd", H.ptr(s), H.ptr(y), B, Hh * W, s.shape[1], H.ACT_RELU, H.stream())
+            H.call("mmvae_avgpool_fwd", H.ptr(s), H.ptr(y), B, Hh * W, s.shape[1], H.ACT_RELU, H.stream())
             ctx.pool = (s, B, Hh * W)
             return y
         return s
@@ -366,19 +365,19 @@ class BottleneckStack(Function):
                 s_out, pB, pHW = ctx.pool
                 dy, G = G, torch.empty_like(s_out)
                 st3 = _stat(blk.u3, b3, Y3, ev, grads)
-                ops._call("mmvae_rc_pool_bwd_stats", H.ptr(dy), H.ptr(s_out), H.ptr(G), ctypes.byref(st3), pB, pHW,
-                          Y3.shape[1], H.stream())
+                H.call("mmvae_rc_pool_bwd_stats", H.ptr(dy), H.ptr(s_out), H.ptr(G), ctypes.byref(st3), pB, pHW,
+                       Y3.shape[1], H.stream())
             elif not ready:
                 if ctx.pool is not None:
                     s_out, pB, pHW = ctx.pool
                     dy, G = G, torch.empty_like(s_out)
-                    ops._call("mmvae_avgpool_bwd", H.ptr(dy), H.ptr(s_out), H.ptr(G), pB, pHW, s_out.shape[1], H.ACT_RELU,
-                              H.stream())
+                    H.call("mmvae_avgpool_bwd", H.ptr(dy), H.ptr(s_out), H.ptr(G), pB, pHW, s_out.shape[1], H.ACT_RELU,
+                           H.stream())
                 st3 = _stat(blk.u3, b3, Y3, ev, grads)
-                ops._call("mmvae_rc_bn_bwd_stats", H.ptr(G), ctypes.byref(st3), M2, Y3.shape[1], H.stream())
+                H.call("mmvae_rc_bn_bwd_stats", H.ptr(G), ctypes.byref(st3), M2, Y3.shape[1], H.stream())
                 if blk.ud:
                     std = _stat(blk.ud, bd, Yd, ev, grads)
-                    ops._call("mmvae_rc_bn_bwd_stats", H.ptr(G), ctypes.byref(std), M2, Yd.shape[1], H.stream())
+                    H.call("mmvae_rc_bn_bwd_stats", H.ptr(G), ctypes.byref(std), M2, Yd.shape[1], H.stream())
             need_in = bi > 0 or ctx.needs_input_grad[0]
             # conv3's data gradient (-> gradient of bn2's output: ReLU mask from Y2, + bn2's statistics) and the projection
             # shortcut's (on ITS output rows; conv1's epilogue adds it through the stride table): both only need G
@@ -466,16 +465,16 @@ class Stem(Function):
         ctx.gen = unit.stamp(M)
         y = torch.empty(M, Cout, device=dev)
         bn = unit.bn
-        ops._call("mmvae_rc_stem_fwd", H.ptr(x), channels_last_ptr(w), H.ptr(y), M, C, Cout, K * K, ctypes.byref(g),
-                  H.ptr(gamma), H.ptr(beta), H.ptr(bn.running_mean), H.ptr(bn.running_var), H.ptr(b["mean"]), H.ptr(b["rstd"]),
-                  H.ptr(b["sc"]), H.ptr(b["part"]), H.ptr(b["counter"]), float(bn.eps), float(bn.momentum), int(not training),
-                  H.stream())
+        H.call("mmvae_rc_stem_fwd", H.ptr(x), channels_last_ptr(w), H.ptr(y), M, C, Cout, K * K, ctypes.byref(g),
+               H.ptr(gamma), H.ptr(beta), H.ptr(bn.running_mean), H.ptr(bn.running_var), H.ptr(b["mean"]), H.ptr(b["rstd"]),
+               H.ptr(b["sc"]), H.ptr(b["part"]), H.ptr(b["counter"]), float(bn.eps), float(bn.momentum), int(not training),
+               H.stream())
         _tap(bn, y, b)
         Hp, Wp = (g.Ho - 1) // 2 + 1, (g.Wo - 1) // 2 + 1
         out = torch.empty(B * Hp * Wp, Cout, device=dev)
         idx = torch.empty(B * Hp * Wp, Cout, device=dev, dtype=torch.int32)
-        ops._call("mmvae_rc_maxpool_fwd", H.ptr(y), H.ptr(b["mean"]), H.ptr(b["sc"]), H.ptr(beta), H.ptr(out), H.ptr(idx), B,
-                  g.Ho, g.Wo, Cout, H.stream())
+        H.call("mmvae_rc_maxpool_fwd", H.ptr(y), H.ptr(b["mean"]), H.ptr(b["sc"]), H.ptr(beta), H.ptr(out), H.ptr(idx), B,
+               g.Ho, g.Wo, Cout, H.stream())
         ctx.saved = (x, y, idx, w, gamma, beta)
         ctx.cfg = (unit, training, (B, C, Hh, W, K, S, P))
         return out
@@ -498,8 +497,8 @@ class Stem(Function):
                 ret[p] = grads[p][0]
         G = torch.empty_like(y)
         st = _stat(unit, b, y, not training, grads)
-        ops._call("mmvae_rc_maxpool_bwd_stats", H.ptr(H.f32c(dy)), H.ptr(idx), H.ptr(G), H.ptr(b["sc"]), H.ptr(beta),
-                  ctypes.byref(st), B, g.Ho, g.Wo, Cout, H.stream())
+        H.call("mmvae_rc_maxpool_bwd_stats", H.ptr(H.f32c(dy)), H.ptr(idx), H.ptr(G), H.ptr(b["sc"]), H.ptr(beta),
+               ctypes.byref(st), B, g.Ho, g.Wo, Cout, H.stream())
         lib = H.lib()
         key = ("stem_ws", M)
         ws = unit._buf.get(key)
@@ -507,8 +506,8 @@ class Stem(Function):
             ws = unit._buf[key] = (torch.empty(lib.mmvae_rc_stem_wgrad_ws_floats(M, C, Cout, K * K), device=dev),
                                    torch.zeros((Cout // 64) * ((K * K * C + 63) // 64), dtype=torch.int32, device=dev))
         dw, acc = grads[w]
-        ops._call("mmvae_rc_stem_wgrad", H.ptr(G), H.ptr(y), H.ptr(b["pqr"]), H.ptr(x), H.ptr(stem_table(dev, B, C, Hh, W, K, S, P)),
-                  channels_last_ptr(dw), H.ptr(ws[0]), H.ptr(ws[1]), M, C, Cout, K * K, ctypes.byref(g), int(acc), H.stream())
+        H.call("mmvae_rc_stem_wgrad", H.ptr(G), H.ptr(y), H.ptr(b["pqr"]), H.ptr(x), H.ptr(stem_table(dev, B, C, Hh, W, K, S, P)),
+               channels_last_ptr(dw), H.ptr(ws[0]), H.ptr(ws[1]), M, C, Cout, K * K, ctypes.byref(g), int(acc), H.stream())
         ctx.saved = None
         return None, None, None, ret.get(w), ret.get(gamma), ret.get(beta)
 

@@ -195,11 +195,11 @@ def test_the_shapes_cover_what_they_are_there_for(ops):
     assert (R.fit(R.SINGLETON)["counts"][R.fit(R.SINGLETON)["best"]] == 1).any()
     counts = R.fit(5)["counts"][R.fit(5)["best"]]
     assert counts.min() > 64
-    _, _, table, first = ops._silhouette_plan(counts, 1100, 0)
+    _, _, table, first = ops.silhouette_plan(counts, 1100, 0)
     assert len(table) > 1 and (table[:, 2] - table[:, 1]).max() > 1
-    _, _, table, first = ops._silhouette_plan(counts, 1100, 1000)
+    _, _, table, first = ops.silhouette_plan(counts, 1100, 1000)
     assert np.diff(first).min() > 1 and len(table) > len(counts)
-    _, _, one_each, _ = ops._silhouette_plan(counts, 1100, 1)
+    _, _, one_each, _ = ops.silhouette_plan(counts, 1100, 1)
     assert len(one_each) == len(counts)
 
 

@@ -139,11 +139,11 @@ def test_chunk_plan():
     """every cluster's run padded to whole tiles; a chunk holds tiles of one cluster; a cluster's chunks are consecutive"""
     from multimodal_vae_comparison_amd import ops
     counts = np.array(R.CRAFTED_SIZES)
-    offset, padded, table, first = ops._silhouette_plan(counts, 195, 0)
+    offset, padded, table, first = ops.silhouette_plan(counts, 195, 0)
     assert offset.tolist() == [0, 1, 1, 3, 4, 5, 5, 6] and padded == 384
     assert table.tolist() == [[0, 0, 1], [2, 1, 3], [3, 3, 4], [4, 4, 5], [6, 5, 6]] and first.tolist() == [0, 1, 1, 2, 3, 4, 4, 5]
     for chunks in (0, 1, 2, 3, 7, 1000):
-        offset, padded, table, first = ops._silhouette_plan(np.array([300, 200, 0, 600]), 1100, chunks)
+        offset, padded, table, first = ops.silhouette_plan(np.array([300, 200, 0, 600]), 1100, chunks)
         assert padded == 64 * 19 and table.dtype == np.int32 and first.dtype == np.int32 and first[-1] == len(table)
         tiles = []
         for c in range(4):
@@ -152,8 +152,8 @@ def test_chunk_plan():
             tiles += [t for _, t0, t1 in mine for t in range(t0, t1)]
             assert [t for _, t0, t1 in mine for t in range(t0, t1)] == list(range(offset[c], offset[c + 1]))
         assert tiles == list(range(19))
-    assert len(ops._silhouette_plan(np.array([300, 200, 0, 600]), 1100, 1)[2]) == 3
-    assert len(ops._silhouette_plan(np.array([300, 200, 0, 600]), 1100, 1000)[2]) == 19
+    assert len(ops.silhouette_plan(np.array([300, 200, 0, 600]), 1100, 1)[2]) == 3
+    assert len(ops.silhouette_plan(np.array([300, 200, 0, 600]), 1100, 1000)[2]) == 19
 
 
 # ---- 3. the contract on CPU models ----------------------------------------------------------------------------------------------

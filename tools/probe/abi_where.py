@@ -7,7 +7,7 @@ import traceback
 
 sys.path.insert(0, ".")
 import torch
-from multimodal_vae_comparison_amd import ops
+from multimodal_vae_comparison_amd import hipops
 from multimodal_vae_comparison_amd.models.trainer import MultimodalVAE
 from multimodal_vae_comparison_amd.synthetic import workload
 
@@ -18,7 +18,7 @@ tr = MultimodalVAE(cfg, feature_dims=dims, device=dev)
 tr.model.train()
 tr.configure_optimizers()
 tr.capture(data, 1)
-_c = ops._call
+_c = hipops.call
 names, seen, where = [], set(), os.environ.get("WHERE")
 
 
@@ -31,7 +31,7 @@ def call(name, *a):
     return _c(name, *a)
 
 
-ops._call = call
+hipops.call = call
 tr.capture(data, 1)
 print(len(names), "calls per step")
 for k, v in collections.Counter(names).most_common():
