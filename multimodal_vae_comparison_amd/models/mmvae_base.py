@@ -140,8 +140,8 @@ class TorchMMVAE(EvaluationMixin, nn.Module):
         return list(ops.randn((n, B, D), self._noise_state()).unbind(0))
 
     # ---- tower-level concurrency -------------------------------------------------------------------
-    def _tower_streams(self, device, main=0):
-        """stream per modality: modality `main` stays on the current stream (None), the others get side streams
+    def _tower_streams(self, device):
+        """stream per modality: None = the current stream, and ONE tower (of two: the second) on the side stream
         (ops.StreamPlan) so that independent towers overlap -- each of them alone cannot fill the chip at batch 128"""
         names = list(self.vaes.keys())
         key = ops.H.device_key(device)
@@ -149,70 +149,65 @@ class TorchMMVAE(EvaluationMixin, nn.Module):
         if not (ops.StreamPlan.enabled and device.type == "cuda") or len(names) < 2:
             return [None] * len(names)
         # (the two streams of this step, for ops that park weight-gradient launches on the stream they are NOT on)
-        ops.StreamPlan.pair[key] = (torch.cuda.current_stream(device), ops.StreamPlan.get("tower1", device))
+        s = ops.StreamPlan.get("tower1", device)
+        ops.StreamPlan.pair[key] = (torch.cuda.current_stream(device), s)
+        ops.GradReducer.note_stream(device, s)
         # ONE side stream however many towers there are: a captured step with three parallel branches (image, text,
         # actions on their own streams) crashes ROCm 7.2's hipGraphInstantiate (segmentation fault inside capture_end;
-        # two branches and the eager three-stream path are fine) -- the towers beyond the first two share a stream
-        max_side = 1
-        if len(names) >= 3 and max_side == 1:
-            # two streams for three or more towers: the tower with the longest launch chain (number of sub-modules as the
-            # proxy: the 8 + 4-layer action Transformers, a ResNet-50) gets the side stream to itself, the others share
-            # the capture stream (BASELINE configs[4]: 4.48 vs 4.68 ms/step with text + actions sharing the side stream)
+        # two branches and the eager three-stream path are fine).  Three or more towers: the tower with the longest launch
+        # chain (number of sub-modules as the proxy: the 8 + 4-layer action Transformers, a ResNet-50) gets the side stream
+        # to itself, the others share the capture stream (BASELINE configs[4]: 4.48 vs 4.68 ms/step with text + actions
+        # sharing the side stream)
+        heavy = 1
+        if len(names) >= 3:
             heavy = max(range(len(names)), key=lambda i: sum(1 for _ in self.vaes[names[i]].modules()))
-            s = ops.StreamPlan.get("tower1", device)
-            ops.GradReducer.note_stream(device, s)
-            return [s if i == heavy else None for i in range(len(names))]
-        out, side = [], 0
-        for i in range(len(names)):
-            if i == main % len(names):
-                out.append(None)
-                continue
-            side = min(side + 1, max_side)
-            s = ops.StreamPlan.get(f"tower{side}", device)
-            ops.GradReducer.note_stream(device, s)
-            out.append(s)
-        return out
+        return [s if i == heavy else None for i in range(len(names))]
 
-    def _fork(self, streams, device, batch=None):
-        """the side streams wait for what is queued on the current one.  `batch`: the step's input dict -- a tower on a
-        side stream reads its modality's data / masks (encoder input, loss target) from tensors that were allocated on
-        the caller's stream: they are registered with the side stream, or the caching allocator hands their memory out
-        again as soon as the caller drops the batch -- while the side stream's last kernels (the text encoder's embedding
-        backward) have yet to read it.  (Found in round 4: `objective(to_device(batch))` with a temporary dict, two
-        streams, a step following smaller ones in the same process: wrong embedding gradient.)"""
+    def _fork(self, streams, device, batch=None, reads=()):
+        """every stream of `streams` (None: the current one) waits for what is queued on the current one and is handed
+        `reads` and the tensors of `batch`, the step's input dict -- a tower on a side stream reads its modality's data /
+        masks (encoder input, loss target) from tensors that were allocated on the caller's stream: unregistered, the
+        caching allocator hands their memory out again as soon as the caller drops the batch -- while the side stream's
+        last kernels (the text encoder's embedding backward) have yet to read it.  (Found in round 4:
+        `objective(to_device(batch))` with a temporary dict, two streams, a step following smaller ones in the same
+        process: wrong embedding gradient.)"""
         cur = torch.cuda.current_stream(device)
-        for s in streams:
-            if s is not None:
-                s.wait_stream(cur)
-        if batch is not None:      # (every side stream: MoPoE's decoders rotate streams after the fusion)
-            side = [s for s in streams if s is not None]
-            for entry in batch.values():
-                for t in entry.values():
-                    if torch.is_tensor(t) and t.is_cuda:
-                        for s in side:
-                            t.record_stream(s)
+        held = list(reads) + [t for entry in (batch or {}).values() for t in entry.values() if torch.is_tensor(t)]
+        for s in dict.fromkeys(streams):      # (every stream: MoPoE's decoders rotate streams after the fusion)
+            ops.StreamPlan.hand(held, cur if s is None else s, after=cur)
 
     @staticmethod
-    def _join(streams, device):
+    def _join(streams, device, made=()):
+        """the current stream waits for every side stream of `streams` and is handed `made`, what was produced on them"""
         cur = torch.cuda.current_stream(device)
-        for s in streams:
+        for s in dict.fromkeys(streams):
             if s is not None:
-                cur.wait_stream(s)
+                ops.StreamPlan.hand(made, cur, after=s)
+
+    def _tower_phase(self, lanes, body, device, reads=(), batch=None):
+        """One parallel phase of a step, the only place a mixer's bodies change streams: `body(key, stream)` for every
+        (key, stream) of `lanes` with that stream current (None: the caller's).  Before, the streams wait for the caller's
+        and are handed `reads` -- what the bodies read of the caller's stream -- and the input `batch` (_fork); after, the
+        caller's stream waits for them and is handed what the bodies returned, a tensor or a sequence of tensors each
+        (_join).  -> the bodies' return values in lane order"""
+        lanes = list(lanes)
+        streams = [st for _, st in lanes]
+        self._fork(streams, device, batch, reads)
+        out = []
+        for key, st in lanes:
+            with torch.cuda.stream(st):
+                out.append(body(key, st))
+        self._join(streams, device, [t for r in out for t in ((r,) if torch.is_tensor(r) else r)])
+        return out
 
     def _encode_towers(self, mods):
         """every tower's encoder on its stream, joined again -> (packed heads [mu | lv] in modality order, the towers'
-        streams (None: the current one), the current stream, the stream every tower really runs on, device)"""
+        streams (None: the current one), device)"""
         dev = next(v["data"] for v in mods.values() if v["data"] is not None).device
         streams = self._tower_streams(dev)
-        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        real = [cur if st is None else st for st in streams]
-        self._fork(streams, dev, mods)
-        packed = []
-        for n, st in zip(self.vaes, streams):
-            with torch.cuda.stream(st):
-                packed.append(packed_head(*self.vaes[n].enc(mods[n])))
-        self._join(streams, dev)
-        return packed, streams, cur, real, dev
+        packed = self._tower_phase(zip(self.vaes, streams), lambda n, st: packed_head(*self.vaes[n].enc(mods[n])), dev,
+                                   batch=mods)
+        return packed, streams, dev
 
     # ---- plumbing shared by the mixers ----------------------------------------------------------
     def make_output_dict(self, encoder_dist=None, decoder_dist=None, latent_samples=None, joint_dist=None,

@@ -14,13 +14,6 @@ from .mmvae_base import TorchMMVAE, normal, packed_head
 from .objectives import recon_rowsum
 
 
-def _uses(t, stream):
-    """`t` (allocated on another stream) is read by kernels queued on `stream`"""
-    if t is not None and t.is_cuda and stream is not None:
-        base = t._base if t._base is not None else t
-        base.record_stream(stream)
-
-
 class MoPOE(TorchMMVAE):
     """Generalised multimodal ELBO (mmvae_models.py:253-410).
 
@@ -75,21 +68,16 @@ class MoPOE(TorchMMVAE):
         dev = next(v["data"] for v in mods.values() if v["data"] is not None).device
         # (which tower keeps the capture stream, and the capture order of the towers, decide how hipGraph partitions the
         # step into queues: measured, see DESIGN.md section 5 -- tower 0 on the capture stream, captured first)
-        main_tower = 0
-        streams = self._tower_streams(dev, main_tower)
+        streams = self._tower_streams(dev)
         cur = torch.cuda.current_stream(dev)
         real = [cur if st is None else st for st in streams]
         self._fork(streams, dev, mods)
         B, D = next(v["data"] for v in mods.values() if v["data"] is not None).shape[0], self.n_latents
         W = self._elbo_weights(B)
         # the M rsamples (:363-369): drawn by the fusion kernel itself unless the noise is replayed (`eps_override`)
-        eps_mode = "fused"
-        if self.eps_override is not None and eps_mode == "fused":
-            eps_mode = "after"
-        eps = self._draw_many(M, B, D, dev) if eps_mode == "first" else None
+        eps = None
         enc = [None] * M
-        enc_order = list(enumerate(zip(names, streams)))
-        for i, (n, st) in enc_order:
+        for i, (n, st) in enumerate(zip(names, streams)):
             with torch.cuda.stream(st):
                 tower = self.vaes[n].enc
                 tower.raw_heads = True      # lv = softmax(u) + eta is applied by the fused latent kernel
@@ -99,24 +87,18 @@ class MoPOE(TorchMMVAE):
                 finally:
                     tower.raw_heads = False
                 enc[i] = tuple(ops.mark_tensor(t, f"enc {n} out[{j}]") for j, t in enumerate(mu_lv))
-                if eps is None and i == 0 and eps_mode == "after":
-                    # one rsample per modality (:363-369), behind tower 0's encoder: that stream idles until the
+                if i == 0 and self.eps_override is not None:
+                    # one replayed rsample per modality (:363-369), behind tower 0's encoder: that stream idles until the
                     # fusion anyway
                     eps = self._draw_many(M, B, D, dev)
         # the fusion runs on the last tower's stream, the decoders rotate by one stream.  (Round 6,
         # re-measured with the shorter text chain: fusion + every decoder on its OWN tower's stream -- no cross-stream wait
         # on the image chain in either direction -- replays at 0.490 ms against 0.388: hipGraph serialises that layout.)
-        rotate = True
-        fuse = real[-1] if rotate else real[0]
-        self._fuse_stream = fuse0 = fuse
-        for st in real:
-            if st != fuse:
-                fuse.wait_stream(st)
+        self._fuse_stream = fuse = real[-1]
         theta = self._pz_params[1]
-        # tensors that cross streams are registered with the consuming stream: the caching allocator must not hand
-        # their memory to the producing stream again while the consumer's kernels are still queued
-        for t in list(eps or []) + [t for pair in enc for t in pair]:
-            _uses(t, fuse)
+        # every tower's heads (tower 0's with the replayed noise drawn behind them) cross to the fusion's stream
+        for i, st in enumerate(real):
+            ops.StreamPlan.hand(list(enc[i]) + (list(eps or []) if i == 0 else []), fuse, after=st)
         with torch.cuda.stream(fuse):
             packed = [packed_head(mu, lv) for mu, lv in enc]
             if seeds is not None and getattr(self, "early_adam", None) is not None and ops.GradReducer.defer_next:
@@ -126,35 +108,33 @@ class MoPOE(TorchMMVAE):
                                               rng=self._rng_state)
             else:
                 _, kl, z = ops.poe_reparam_kl(theta, packed, eps, True, (1 << (M + 1)) - 1, theta.grad, raw=True)
-        _uses(kl, cur)
-        for st in real:
-            if st != fuse:
-                st.wait_stream(fuse)
+        ops.StreamPlan.hand([kl], cur)
+        order = [(i, names[i], real[(i + M - 1) % M]) for i in range(M)]
+        for i, _, st in order:      # (all of them before the first decoder is queued: none waits for another's launches)
+            ops.StreamPlan.hand([z[i]], st, after=fuse)
         recs = [None] * M
-        order = [(i, names[i], real[(i + M - 1) % M] if rotate else real[i]) for i in range(M)]
         # (the stream of a decoder that does not share the fusion's: idle behind that decoder's backward pass)
-        self._idle_stream = next((st for _, _, st in reversed(order) if st != fuse0), None)
+        self._idle_stream = next((st for _, _, st in reversed(order) if st != fuse), None)
         for i, n, st in order:
             vae = self.vaes[n]
-            _uses(z[i], st)
             with torch.cuda.stream(st):
                 zi = ops.mark_tensor(z[i], f"dec {n} z")
                 if seeds is not None and getattr(self, "early_adam", None) is not None and ops.GradReducer.defer_next:
                     zi = ops.DecoderEnd.apply(zi)           # (parked weight gradients of this decoder: out before the fusion)
-                if seeds is not None and st != fuse0 and ops.GradReducer.side_head is not None:
+                if seeds is not None and st != fuse and ops.GradReducer.side_head is not None:
                     zi = ops.StreamIdlePoint.apply(zi)      # (this decoder's stream idles behind its backward pass)
                 if seeds is not None:      # the term's upstream gradient is known: its kernel also writes its backward
                     with ops.ConstSeed(seeds[i], W[0][i]):
                         # (a bce decoder is handed its target: Dec_CNN then folds the loss into its last layer's launch)
-                        fuse = vae.ltype == "bce" and mods[n]["masks"] is None
+                        fold = vae.ltype == "bce" and mods[n]["masks"] is None
                         out, _ = vae.dec({"latents": zi.unsqueeze(0), "masks": mods[n]["masks"],
-                                          "bce_target": mods[n]["data"] if fuse else None})
+                                          "bce_target": mods[n]["data"] if fold else None})
                         r = recon_rowsum(vae.ltype, out, mods[n], laplace=self._lap(vae))
                 else:
                     out, _ = vae.dec({"latents": zi.unsqueeze(0), "masks": mods[n]["masks"]})
                     r = recon_rowsum(vae.ltype, out, mods[n], laplace=self._lap(vae))
                 recs[i] = ops.mark_tensor(r, f"dec {n} recon")   # (B,) = -lpx_z / llik_scaling
-            _uses(recs[i], cur)
+            ops.StreamPlan.hand([recs[i]], cur)      # (joined by objective() / finish_step())
         self._fusion_inputs = packed        # the towers' packed head outputs: where the backward can be cut in two
         return recs, kl, W, streams, dev
 
@@ -336,42 +316,37 @@ class POE(TorchMMVAE):
         # ---- encoders: packed[s][n] for n in subset s ----
         packed = [dict() for _ in subsets]
         raw_heads = dev.type == "cuda" and all(hasattr(v.enc, "raw_heads") and v.enc.enc_mu_logvar for v in self.vaes.values())
-        self._fork(streams, dev, mods)
-        for n, st in zip(names, streams):
+        def encode(n, st):
             member = [s for s, S in enumerate(subsets) if n in S]
-            with torch.cuda.stream(st):
-                enc = self.vaes[n].enc
-                # lv = softmax(u) + eta is applied by the fusion kernels (as MoPOE._elbo_terms does): no softmax launch
-                # behind the heads, none in front of their backward
-                enc.raw_heads = raw_heads
-                try:
-                    if one_call(enc):
-                        p = packed_head(*enc(mods[n]))
-                        for s in member:
-                            packed[s][n] = p
-                    elif self.batch_dropout_towers and len(member) > 1 and getattr(enc, "takes_repeat", False) and \
-                            enc.repeat_ok(mods[n]):
-                        # an encoder WITH dropout whose passes differ only in their masks: all of them as one call over
-                        # len(member) * B sequences (round 5: the text encoder's positional term follows the sample's
-                        # position in the ORIGINAL batch, ops.embed_pe), rows k * B + b
-                        p = packed_head(*enc(dict(mods[n], repeat=len(member))))
-                        for s, part in zip(member, ops.split_rows(p, len(member))):      # (row blocks; ONE cat in backward)
-                            packed[s][n] = part
-                    else:
-                        for s in member:
-                            packed[s][n] = packed_head(*enc(mods[n]))
-                finally:
-                    enc.raw_heads = False
-        self._join(streams, dev)
+            enc = self.vaes[n].enc
+            # lv = softmax(u) + eta is applied by the fusion kernels (as MoPOE._elbo_terms does): no softmax launch
+            # behind the heads, none in front of their backward
+            enc.raw_heads = raw_heads
+            try:
+                if one_call(enc):
+                    p = packed_head(*enc(mods[n]))
+                    for s in member:
+                        packed[s][n] = p
+                elif self.batch_dropout_towers and len(member) > 1 and getattr(enc, "takes_repeat", False) and \
+                        enc.repeat_ok(mods[n]):
+                    # an encoder WITH dropout whose passes differ only in their masks: all of them as one call over
+                    # len(member) * B sequences (round 5: the text encoder's positional term follows the sample's
+                    # position in the ORIGINAL batch, ops.embed_pe), rows k * B + b
+                    p = packed_head(*enc(dict(mods[n], repeat=len(member))))
+                    for s, part in zip(member, ops.split_rows(p, len(member))):      # (row blocks; ONE cat in backward)
+                        packed[s][n] = part
+                else:
+                    for s in member:
+                        packed[s][n] = packed_head(*enc(mods[n]))
+            finally:
+                enc.raw_heads = False
+            return [packed[s][n] for s in member]
         # Tensors that cross streams (a tower's heads -> the fusion; the latent samples -> decoder calls on the other stream;
-        # their row sums -> the ELBO assembly) are registered with the consuming stream.  Without it the allocator hands a
-        # block out again as soon as the host drops the last reference -- found in round 6 in the CAPTURED step: the
+        # their row sums -> the ELBO assembly) are handed to the consuming stream (_tower_phase).  Without it the allocator
+        # hands a block out again as soon as the host drops the last reference -- found in round 6 in the CAPTURED step: the
         # image-only subset's z (capture stream) was re-used by the image decoder's backward while the text decoder's
         # cross-attention weight gradient, queued long before on the side stream, had yet to read it.
-        cur = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
-        for d_ in packed:
-            for t in d_.values():
-                _uses(t, cur)
+        self._tower_phase(zip(names, streams), encode, dev, batch=mods)
         # ---- fusion per subset (one noise draw each, in subset order) ----
         zs, kl_blocks = [], []
         D = self.n_latents
@@ -411,30 +386,27 @@ class POE(TorchMMVAE):
         plan = [(len(g), D, [(s_, k, 0) for k, s_ in enumerate(g)]) for _, _, g, _ in jobs]
         z_ins = ops.rows_fan(plan, zs) if (zs[0].is_cuda and ops.RowsFan.supported(plan, zs)) else None
         rec_blocks = []
-        self._fork(streams, dev, mods)
-        for j_, ((i, n, g, gm), (st, begun)) in enumerate(zip(jobs, lanes)):
+
+        def decode(j_, st):
+            (i, n, g, gm), begun = jobs[j_], lanes[j_][1]
             vae = self.vaes[n]
-            with torch.cuda.stream(st):
-                c0 = ops.CALLS[0]
-                m_in = gm if (gm is None or len(g) == 1) else gm.repeat(len(g), 1)
-                if z_ins is not None:
-                    z_in = z_ins[j_]
-                    _uses(z_in, st)
-                else:
-                    for s_ in g:
-                        _uses(zs[s_], st)
-                    z_in = torch.cat([zs[s_] for s_ in g], 0) if len(g) > 1 else zs[g[0]]
-                job = {"latents": z_in.unsqueeze(0), "masks": m_in}
-                if begun is not None:
-                    job["drop_begun"] = begun
-                if gm is None and mods[n]["masks"] is not None and getattr(vae.dec, "takes_keep_steps", False):
-                    job["keep_steps"] = int(mods[n]["masks"].shape[1])      # (recon_rowsum slices to the target's mask length)
-                out, _ = vae.dec(job)
-                r = recon_rowsum(vae.ltype, out, mods[n])                    # target row = output row % B
-                _uses(r, cur)
-                rec_blocks.append((r.view(len(g), B), i, list(g)))           # the call's rows as ONE (passes, B) block
-                self._job_calls[(n, len(g), gm is None, B)] = ops.CALLS[0] - c0
-        self._join(streams, dev)
+            c0 = ops.CALLS[0]
+            m_in = gm if (gm is None or len(g) == 1) else gm.repeat(len(g), 1)
+            if z_ins is not None:
+                z_in = z_ins[j_]
+            else:
+                z_in = torch.cat([zs[s_] for s_ in g], 0) if len(g) > 1 else zs[g[0]]
+            job = {"latents": z_in.unsqueeze(0), "masks": m_in}
+            if begun is not None:
+                job["drop_begun"] = begun
+            if gm is None and mods[n]["masks"] is not None and getattr(vae.dec, "takes_keep_steps", False):
+                job["keep_steps"] = int(mods[n]["masks"].shape[1])      # (recon_rowsum slices to the target's mask length)
+            out, _ = vae.dec(job)
+            r = recon_rowsum(vae.ltype, out, mods[n])                    # target row = output row % B
+            rec_blocks.append((r.view(len(g), B), i, list(g)))           # the call's rows as ONE (passes, B) block
+            self._job_calls[(n, len(g), gm is None, B)] = ops.CALLS[0] - c0
+            return r
+        self._tower_phase([(j_, st) for j_, (st, _) in enumerate(lanes)], decode, dev, reads=z_ins or zs, batch=mods)
         # ELBO assembly straight on the calls' row BLOCKS (round 5: slicing the batched row sums and selecting the joint KL
         # row cost ~40 ATen fill / copy / add launches per step in forward + autograd): every block is addressed in place,
         # a row that does not enter an output has weight 0.  Outputs: loss, kld and -- while they fit (<= 4 outputs) -- the
@@ -612,27 +584,19 @@ class MVTCAE(POE):
         try:
             for e in encs if raw_heads else []:
                 e.raw_heads = True
-            packed, streams, cur, real, dev = self._encode_towers(mods)
+            packed, streams, dev = self._encode_towers(mods)
         finally:
             for e in encs if raw_heads else []:
                 e.raw_heads = False
-        # tensors that cross streams are registered with the consuming stream (see POE.objective)
-        for t in packed:
-            _uses(t, cur)
         B, D = packed[0].shape[0], self.n_latents
         eps = self._draw(B, D, dev)
         _, kl, z = ops.tc_fusion(theta, packed, eps, theta.grad, raw=raw_heads)
-        for st in real:
-            _uses(z, st)
-        recs = [None] * M
-        self._fork(streams, dev, mods)
-        for i, (n, st) in enumerate(zip(names, streams)):
+
+        def decode(n, st):
             vae = self.vaes[n]
-            with torch.cuda.stream(st):
-                out, _ = vae.dec({"latents": z.unsqueeze(0), "masks": mods[n]["masks"]})
-                recs[i] = recon_rowsum(vae.ltype, out, mods[n])      # (B,)
-            _uses(recs[i], cur)
-        self._join(streams, dev)
+            out, _ = vae.dec({"latents": z.unsqueeze(0), "masks": mods[n]["masks"]})
+            return recon_rowsum(vae.ltype, out, mods[n])      # (B,)
+        recs = self._tower_phase(zip(names, streams), decode, dev, reads=[z], batch=mods)
         out = ops.lincomb_rows(recs + [kl], self._tc_weights())
         with torch.no_grad():      # logged only: every modality's row sum over the batch
             if M <= ops.H.LC_MAX_OUT:
@@ -698,7 +662,7 @@ class MOE(TorchMMVAE):
         # extracted-mask parity test splits them by pass).  optimal_sigma fits ONE sigma per call: its passes stay apart.
         # The shipped config_cdspritesplus.yml step is a chain of ~260 launches, ~115 of them the text decoder's two
         # op-by-op passes: 4.00 -> 3.4 ms/step.
-        packed, streams, cur, real, dev = self._encode_towers(data)
+        packed, streams, dev = self._encode_towers(data)
         B, D = packed[0].shape[0], self.n_latents
         zs, kls = [], []
         for i in range(M):
@@ -710,34 +674,28 @@ class MOE(TorchMMVAE):
                 _, kl, z = ops.poe_reparam_kl(self._theta0, [packed[i]], [eps], 2, 0b10)
                 kls.append(ops.kl_row(kl, 1))      # (kl_mask 0b10: row 1 is the only one the backward reads)
             zs.append(z[0])
-        for t in packed + zs:         # read by both towers' decoder sides
-            for st in real:
-                _uses(t, st)
-        rows, W = [None] * (2 * M), []
-        self._fork(streams, dev, data)
-        for r, (n, st) in enumerate(zip(names, streams)):
-            vae = self.vaes[n]
+        def decode(r, st):
+            vae = self.vaes[names[r]]
+            mod = data[names[r]]
             o = [s for s in range(M) if s != r][-1]
-            with torch.cuda.stream(st):
-                mk = data[n]["masks"]
-                if vae.ltype != "optimal_sigma" and self.batch_passes:
-                    z2 = torch.cat([zs[r], zs[o]], 0)
-                    out, _ = vae.dec({"latents": z2.unsqueeze(0), "masks": None if mk is None else mk.repeat(2, 1)})
-                    # own: dist.Normal(*px_z) (:101-103); cross (rows B..2B): vae.px_z = the config's `prior` family (:115)
-                    rs = recon_rowsum(vae.ltype, out, data[n], laplace=(0b10, B) if self._laplace[r] else False)
-                    own_r, cross_r = rs.view(2, B).unbind(0)      # (backward: one stack instead of two zero-fill + copy pairs)
-                else:
-                    own, _ = vae.dec({"latents": zs[r].unsqueeze(0), "masks": mk})
-                    cross, _ = vae.dec({"latents": zs[o].unsqueeze(0), "masks": mk})
-                    own_r = recon_rowsum(vae.ltype, own, data[n])
-                    cross_r = recon_rowsum(vae.ltype, cross, data[n], laplace=self._laplace[r])
-                ratio = ops.laplace_logratio if self._laplace[r] else ops.normal_logratio
-                lw = ratio(packed[r], packed[o].detach(), zs[o].detach())
-                rows[2 * r], rows[2 * r + 1] = own_r, ops.expmul(lw, cross_r)
-            for t in (rows[2 * r], rows[2 * r + 1]):
-                _uses(t, cur)
-            W += [float(vae.llik_scaling)] * 2
-        self._join(streams, dev)
+            mk = mod["masks"]
+            if vae.ltype != "optimal_sigma" and self.batch_passes:
+                z2 = torch.cat([zs[r], zs[o]], 0)
+                out, _ = vae.dec({"latents": z2.unsqueeze(0), "masks": None if mk is None else mk.repeat(2, 1)})
+                # own: dist.Normal(*px_z) (:101-103); cross (rows B..2B): vae.px_z = the config's `prior` family (:115)
+                rs = recon_rowsum(vae.ltype, out, mod, laplace=(0b10, B) if self._laplace[r] else False)
+                own_r, cross_r = rs.view(2, B).unbind(0)      # (backward: one stack instead of two zero-fill + copy pairs)
+            else:
+                own, _ = vae.dec({"latents": zs[r].unsqueeze(0), "masks": mk})
+                cross, _ = vae.dec({"latents": zs[o].unsqueeze(0), "masks": mk})
+                own_r = recon_rowsum(vae.ltype, own, mod)
+                cross_r = recon_rowsum(vae.ltype, cross, mod, laplace=self._laplace[r])
+            ratio = ops.laplace_logratio if self._laplace[r] else ops.normal_logratio
+            lw = ratio(packed[r], packed[o].detach(), zs[o].detach())
+            return own_r, ops.expmul(lw, cross_r)
+        # (the heads and the samples are read by both towers' decoder sides)
+        rows = [t for pair in self._tower_phase(enumerate(streams), decode, dev, reads=packed + zs, batch=data) for t in pair]
+        W = [float(vae.llik_scaling) for vae in self.vaes.values() for _ in range(2)]
         kld = torch.stack(kls)                                              # (M, B), also the logged "kld"
         loss = ops.moe_elbo(rows, W, kld, self.obj_fn.beta, M)
         with torch.no_grad():                                               # logged only: lpx rows, reference sign
@@ -753,7 +711,7 @@ class MOE(TorchMMVAE):
         self._begin_step()
         names = list(self.vaes.keys())
         M, K, D = len(names), int(self.K), self.n_latents
-        packed, streams, cur, real, dev = self._encode_towers(data)
+        packed, streams, dev = self._encode_towers(data)
         B = packed[0].shape[0]
         eps = [self._draw_k(m, K, B, D, dev) for m in range(M)]
         theta = self._pz_params[1]
@@ -762,37 +720,29 @@ class MOE(TorchMMVAE):
         lat, z = ops.moe_ksample(theta, packed, eps, self._laplace, theta.grad,
                                  beta=float(self.obj_fn.beta) if iwae else 1.0)          # z: (M,K,B,D)
         KB = K * B
-        rows, lam = [None] * (2 * M), []
-        for st in real:
-            _uses(z, st)
-        self._fork(streams, dev, data)
-        for r, (n, st) in enumerate(zip(names, streams)):
+        def decode(r, st):
+            n = names[r]
             vae = self.vaes[n]
             if not iwae and (vae.ltype != "lprob" or data[n]["masks"] is not None):
                 raise NotImplementedError("moe dreg: recon_loss lprob on unmasked modalities (the MNIST / SVHN towers) "
                                           "is what keeps the K axis in the reference")
             self.obj_fn.set_ltype(vae.ltype)
             o = 1 - r
-            with torch.cuda.stream(st):
-                out, _ = vae.dec({"latents": z.view(M * K, B, D), "masks": data[n]["masks"]})     # (M*K, B, ...) / (M*K*B, ...)
-                # own block r: dist.Normal (:101-103); cross block o: vae.px_z = the config's `prior` family (:115)
-                lap_mask = (1 << o) if self._laplace[r] else 0
-                if vae.ltype == "optimal_sigma":
-                    # optimal_sigma fits ONE sigma per reference call, and the reference evaluates the own and the cross
-                    # reconstruction in separate calls (mmvae_models.py:63-78): row sums per source posterior (found by
-                    # the K-sample test on the action towers, round 5: one sigma over all M K B rows was 9e-4 off)
-                    flat = out.reshape(M, KB, *out.shape[-3:]) if out.dim() >= 4 else out.reshape(M, KB, -1)
-                    blocks = [recon_rowsum(vae.ltype, flat[m], data[n]) for m in range(M)]
-                    rs = blocks[0]
-                    for blk in blocks:
-                        _uses(blk, cur)
-                else:
-                    rs = recon_rowsum(vae.ltype, out, data[n], laplace=(lap_mask, KB))          # (M*K*B,)
-                    blocks = rs.view(M, KB).unbind(0)
-                rows[2 * r], rows[2 * r + 1] = blocks[r], blocks[o]
-            _uses(rs, cur)
-            lam.append(float(vae.llik_scaling))
-        self._join(streams, dev)
+            out, _ = vae.dec({"latents": z.view(M * K, B, D), "masks": data[n]["masks"]})     # (M*K, B, ...) / (M*K*B, ...)
+            # own block r: dist.Normal (:101-103); cross block o: vae.px_z = the config's `prior` family (:115)
+            lap_mask = (1 << o) if self._laplace[r] else 0
+            if vae.ltype == "optimal_sigma":
+                # optimal_sigma fits ONE sigma per reference call, and the reference evaluates the own and the cross
+                # reconstruction in separate calls (mmvae_models.py:63-78): row sums per source posterior (found by
+                # the K-sample test on the action towers, round 5: one sigma over all M K B rows was 9e-4 off)
+                flat = out.reshape(M, KB, *out.shape[-3:]) if out.dim() >= 4 else out.reshape(M, KB, -1)
+                blocks = [recon_rowsum(vae.ltype, flat[m], data[n]) for m in range(M)]
+            else:
+                rs = recon_rowsum(vae.ltype, out, data[n], laplace=(lap_mask, KB))          # (M*K*B,)
+                blocks = rs.view(M, KB).unbind(0)
+            return blocks[r], blocks[o]
+        rows = [t for pair in self._tower_phase(enumerate(streams), decode, dev, reads=[z], batch=data) for t in pair]
+        lam = [float(vae.llik_scaling) for vae in self.vaes.values()]
         return self.obj_fn.calculate_loss({"lat": lat, "rows": rows, "lam": lam})
 
     def modality_mixing(self, mods):
@@ -881,7 +831,7 @@ class DMVAE(TorchMMVAE):
         # modality) -- as ONE call over (2 + (M - 1)) B latent samples (the row-sum kernels pair output row k with target
         # row k % B; a decoder with dropout draws its masks once for all passes; optimal_sigma fits one sigma per call:
         # its passes stay apart).  BASELINE configs[3]: 1.54 -> 1.2 ms/step.
-        packed, streams, cur, real, dev = self._encode_towers(mods)
+        packed, streams, dev = self._encode_towers(mods)
         B = packed[0].shape[0]
         P = [self.vaes[n].private_latents for n in names]
         # noise in the reference's draw order (mmvae_models.py:486-502)
@@ -917,10 +867,6 @@ class DMVAE(TorchMMVAE):
             _, klp, zp = ops.poe_reparam_kl(self._theta0[:, :P[m]].contiguous(), [packed[m]], [e_pr[m]], 2, 0b10, None,
                                             cols=(D, P[m]))
             z_pr[m], kl_pr[m] = zp[0], klp
-        for t in [zj[0]] + list(z_sh.values()) + list(z_cr.values()) + list(z_pr.values()):
-            for st in real:
-                _uses(t, st)
-        per = [None] * M
         # every decoder's input batch -- rows [own | joint | cross...] x columns [shared | private] -- from ONE launch for all
         # modalities, and every sample's gradient as one sum in backward (ops.RowsFan): 2 cat + 1 repeat per modality forward,
         # a repeat-sum, the strided slices' copies and an addition per shared sample backward before
@@ -940,30 +886,25 @@ class DMVAE(TorchMMVAE):
                              [(src(z_pr[i]), k, D) for k in range(len(zs_i))]))
             if ops.RowsFan.supported(plan, srcs):
                 lats = ops.rows_fan(plan, srcs)
-        self._fork(streams, dev, mods)
-        for i, (n, st) in enumerate(zip(names, streams)):
+
+        def decode(i, st):
+            n = names[i]
             vae = self.vaes[n]
-            with torch.cuda.stream(st):
-                zs_i = [z_sh[i], zj[0]] + [z_cr[(i, m)] for m in range(M) if m != i]      # decode order own, joint, cross
-                mk = mods[n]["masks"]                                                  # (mmvae_models.py:494-502)
-                if vae.ltype != "optimal_sigma" and self.batch_passes:
-                    NP = len(zs_i)
-                    if lats is not None:
-                        lat = lats[i]
-                        _uses(lat, st)
-                    else:
-                        lat = torch.cat([torch.cat(zs_i, 0), z_pr[i].repeat(NP, 1)], -1)
-                    out, _ = vae.dec({"latents": lat.unsqueeze(0), "masks": None if mk is None else mk.repeat(NP, 1)})
-                    rs = recon_rowsum(vae.ltype, out, mods[n], laplace=self._lap(vae))
-                    per[i] = [rs.view(NP, B)]                  # ONE (passes, B) block: rows own, joint, cross...
-                else:
-                    per[i] = []
-                    for z in zs_i:
-                        out, _ = vae.dec({"latents": torch.cat([z, z_pr[i]], -1).unsqueeze(0), "masks": mk})
-                        per[i].append(recon_rowsum(vae.ltype, out, mods[n], laplace=self._lap(vae)).view(1, B))
-            for t in per[i]:
-                _uses(t, cur)
-        self._join(streams, dev)
+            zs_i = [z_sh[i], zj[0]] + [z_cr[(i, m)] for m in range(M) if m != i]      # decode order own, joint, cross
+            mk = mods[n]["masks"]                                                  # (mmvae_models.py:494-502)
+            if vae.ltype != "optimal_sigma" and self.batch_passes:
+                NP = len(zs_i)
+                lat = lats[i] if lats is not None else torch.cat([torch.cat(zs_i, 0), z_pr[i].repeat(NP, 1)], -1)
+                out, _ = vae.dec({"latents": lat.unsqueeze(0), "masks": None if mk is None else mk.repeat(NP, 1)})
+                rs = recon_rowsum(vae.ltype, out, mods[n], laplace=self._lap(vae))
+                return [rs.view(NP, B)]                    # ONE (passes, B) block: rows own, joint, cross...
+            blocks = []
+            for z in zs_i:
+                out, _ = vae.dec({"latents": torch.cat([z, z_pr[i]], -1).unsqueeze(0), "masks": mk})
+                blocks.append(recon_rowsum(vae.ltype, out, mods[n], laplace=self._lap(vae)).view(1, B))
+            return blocks
+        reads = [zj[0]] + list(z_sh.values()) + list(z_cr.values()) + list(z_pr.values()) + list(lats or [])
+        per = self._tower_phase(enumerate(streams), decode, dev, reads=reads, batch=mods)
         # ELBO assembly on the calls' row BLOCKS (as POE.objective: selecting rows out of the batched row sums / the KL
         # blocks cost a zero-fill and a copy per row in autograd's select / unbind backward -- 15 launches per step at
         # M = 2): every block is addressed in place, a row that does not enter an output has weight 0

@@ -302,10 +302,8 @@ class GradReducer:
     @classmethod
     def _cw_launch(cls, dev, ev):
         side = cls.cw_streams[1]
-        side.wait_event(ev)
-        for j in cls.cw_jobs:
-            for t in j[:2]:      # x, dy: allocated on the chain's stream, read on the other one
-                (t._base if t._base is not None else t).record_stream(side)
+        # x, dy: allocated on the chain's stream, read on the other one
+        StreamPlan.hand([t for j in cls.cw_jobs for t in j[:2]], side, after=ev)
         with torch.cuda.stream(side):
             cls.flush_cw()
             cls.cw_done = side.record_event()
@@ -525,6 +523,21 @@ class StreamPlan:
         if cur == pr[1]:
             return pr[0]
         return None
+
+    @staticmethod
+    def hand(tensors, to, after=None):
+        """THE way a tensor crosses streams: kernels queued on stream `to` from here on read `tensors`, which another
+        stream allocated.  `after` (a stream or an event: what produced them): `to` first waits for it.  Every CUDA tensor
+        is then registered with `to` -- without that the caching allocator hands its block to the allocating stream again
+        as soon as the host drops the last reference, whatever `to` still has queued.  None entries, CPU tensors and a
+        `to` of None are ignored.  (record_stream registers the tensor's STORAGE: a view stands for its whole block.)"""
+        if to is None:
+            return
+        if after is not None and after != to:
+            (to.wait_event if isinstance(after, torch.cuda.Event) else to.wait_stream)(after)
+        for t in tensors:
+            if t is not None and t.is_cuda:
+                t.record_stream(to)
 
 
 def _defer(*grads):
@@ -2918,12 +2931,10 @@ class Ffn32(Function):
             ev = torch.cuda.Event()
             ev.record(cur)
             bwd(dx, None)
-            other.wait_event(ev)
+            held = (x, dy) if wsplit is None else (x, dy, wsplit, rsplit)
+            StreamPlan.hand(held, other, after=ev)
             with torch.cuda.stream(other):
                 bwd(None, ws)
-            held = (x, dy) if wsplit is None else (x, dy, wsplit, rsplit)
-            for t in held:
-                t.record_stream(other)
             GradReducer.keep(x.device, *held)
             GradReducer.note_stream(x.device, other)
         else:
