@@ -390,6 +390,32 @@ int mmvae_tc_fusion_bwd(const mmvae_tc_bwd_args* a, const float* theta, const fl
                         int accumulate, mmvae_stream_t stream);
 size_t mmvae_tc_fusion_ws_floats(int B, int D);
 
+/* ------------------------------------------------------------------------------------------------
+ * Jensen-Shannon fusion (mmJSD: Sutter, Daunhawer, Vogt, NeurIPS 2020): the weighted geometric mean of the E unimodal
+ * posteriors and the prior (the "dynamic prior"), the KL of each of the E + 1 to it, and ONE reparameterised sample per
+ * row from the expert sel[b] names, forward and backward (csrc/jsfusion.hip).  Pointer tables, ld_in, raw_heads, eps / z /
+ * dz, ws, dtheta and accumulate are those of mmvae_tc_fusion_*.  Expert j < E is N(mu_j, sigma_j = lv_j): the head is read
+ * as the SCALE, as the mixture of experts samples from it; j = E is the prior N(0, sp), sp = softmax(theta) D.
+ * weights: E + 1 host floats pi_0 .. pi_E (pi_E: the prior's), each finite and >= 0, their sum > 0, or MMVAE_ERR_ARG.
+ *   T_j = pi_j / sigma_j^2, P = sum_j T_j, f = sum_j T_j mu_j / P, m_j = mu_j - f (formed from pairwise differences)
+ *   prior (2,B,D) : f, P^-1/2                                  (not differentiable)
+ *   kl (E+1,B)    : row j: sum_d KL(N(mu_j, sigma_j) || N(f, P^-1/2))
+ *                          = sum_d [ -log(sigma_j^2 P) + P (sigma_j^2 + m_j^2) - 1 ] / 2            (unweighted)
+ *   z (B,D)       : mu_s + sigma_s eps, s = sel[b] (int32, B values).  The expert is found by comparing indices: a value
+ *                   outside [0, E) selects nothing, its z row is 0 and no gradient flows from it.
+ * bwd: dz (B,D), dkl (E+1,B) -> dmu[e], dlv[e] (d/d sigma_e; raw_heads: d/du), dtheta as mmvae_tc_fusion_bwd; every sum in
+ *   one fixed order, no atomics: bit-reproducible from run to run.
+ * 1 <= E <= MMVAE_MAX_EXPERTS and D <= 256; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing
+ * (mmvae_js_fusion_ws_floats: 0).
+ * ---------------------------------------------------------------------------------------------- */
+int mmvae_js_fusion_fwd(const mmvae_tc_fwd_args* a, const float* weights, const float* theta, const float* eps,
+                        const int* sel, float* prior, float* kl, float* z, int E, int B, int D, int ld_in, int raw_heads,
+                        mmvae_stream_t stream);
+int mmvae_js_fusion_bwd(const mmvae_tc_bwd_args* a, const float* weights, const float* theta, const float* eps,
+                        const int* sel, const float* dz, const float* dkl, float* dtheta, float* ws, int E, int B, int D,
+                        int ld_in, int raw_heads, int accumulate, mmvae_stream_t stream);
+size_t mmvae_js_fusion_ws_floats(int B, int D);
+
 /* Latent samples -> decoder inputs, and the transpose (round 6).  The reference decodes every subset's sample in a call of its
  * own (POE.objective, models/mmvae_models.py:159-187) and builds DMVAE's decoder inputs with torch.cat([z_shared, z_private], -1)
  * per pass (:494-502); here a decoder's passes are one batch, and the batches of ALL decoders are written by one launch:

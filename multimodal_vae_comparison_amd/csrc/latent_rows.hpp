@@ -1,4 +1,5 @@
-// Row helpers shared by the fused latent ops (latent.hip: product of experts; tcfusion.hip: total-correlation fusion):
+// Row helpers shared by the fused latent ops (latent.hip: product of experts; tcfusion.hip: total-correlation fusion;
+// jsfusion.hip: Jensen-Shannon fusion):
 // one wavefront per sample, lanes over the latent dimension in POE_SLOTS column slots of 64.
 #pragma once
 #include "common.hpp"
@@ -67,5 +68,44 @@ __device__ __forceinline__ float kl_elem(float mu, float s, float sp) {
 static inline int poe_blocks(int B) {
   int waves = B < POE_MAX_WAVES ? B : POE_MAX_WAVES;
   return (waves + 3) / 4;
+}
+
+// The fold of the prior gradient behind tcfusion.hip's and jsfusion.hip's backward kernels, whose workgroups each leave one
+// partial row of d loss / d sp in ws.
+// dtheta_d (+)= D s_d (dsp_d - sum_k s_k dsp_k), dsp = the workgroups' partial rows summed in row order: wave w takes rows
+// w, w + 4, ..., the four sums are combined in wave order (D <= 256)
+static __global__ __launch_bounds__(256) void theta_fold_kernel(const float* __restrict__ theta, const float* __restrict__ ws,
+                                                                float* __restrict__ dtheta, int nrows, int D,
+                                                                int accumulate) {
+  __shared__ float part[4][64 * POE_SLOTS];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int s = 0; s < POE_SLOTS; ++s) {
+    const int d = lane + 64 * s;
+    float acc = 0.f;
+    if (d < D)
+      for (int r = wave; r < nrows; r += 4) acc += ws[(size_t)r * D + d];
+    part[wave][d] = acc;
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  float sp[POE_SLOTS], sm[POE_SLOTS], dsp[POE_SLOTS];
+  prior_sigma(theta, D, lane, sp, sm);
+  float dot = 0.f;
+#pragma unroll
+  for (int s = 0; s < POE_SLOTS; ++s) {
+    const int d = lane + 64 * s;
+    dsp[s] = part[0][d] + part[1][d] + part[2][d] + part[3][d];
+    dot += dsp[s] * sm[s];
+  }
+  dot = wave_sum(dot);
+#pragma unroll
+  for (int s = 0; s < POE_SLOTS; ++s) {
+    const int d = lane + 64 * s;
+    if (d < D) {
+      const float g = (float)D * sm[s] * (dsp[s] - dot);
+      dtheta[d] = accumulate ? dtheta[d] + g : g;
+    }
+  }
 }
 

@@ -177,42 +177,6 @@ __global__ __launch_bounds__(256) void tc_bwd_kernel(mmvae_tc_bwd_args a, const 
         part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
 }
 
-// dtheta_d (+)= D s_d (dsp_d - sum_k s_k dsp_k), dsp = the workgroups' partial rows summed in row order: wave w takes rows
-// w, w + 4, ..., the four sums are combined in wave order (D <= 256)
-__global__ __launch_bounds__(256) void tc_theta_kernel(const float* __restrict__ theta, const float* __restrict__ ws,
-                                                       float* __restrict__ dtheta, int nrows, int D, int accumulate) {
-  __shared__ float part[4][64 * POE_SLOTS];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    float acc = 0.f;
-    if (d < D)
-      for (int r = wave; r < nrows; r += 4) acc += ws[(size_t)r * D + d];
-    part[wave][d] = acc;
-  }
-  __syncthreads();
-  if (wave != 0) return;
-  float sp[POE_SLOTS], sm[POE_SLOTS], dsp[POE_SLOTS];
-  prior_sigma(theta, D, lane, sp, sm);
-  float dot = 0.f;
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    dsp[s] = part[0][d] + part[1][d] + part[2][d] + part[3][d];
-    dot += dsp[s] * sm[s];
-  }
-  dot = wave_sum(dot);
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    if (d < D) {
-      const float g = (float)D * sm[s] * (dsp[s] - dot);
-      dtheta[d] = accumulate ? dtheta[d] + g : g;
-    }
-  }
-}
-
 static inline bool tc_supported(int E, int D) { return E <= MMVAE_MAX_EXPERTS && D <= 64 * POE_SLOTS; }
 
 extern "C" size_t mmvae_tc_fusion_ws_floats(int B, int D) {
@@ -241,7 +205,7 @@ extern "C" int mmvae_tc_fusion_bwd(const mmvae_tc_bwd_args* a, const float* thet
   hipLaunchKernelGGL(tc_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *a, theta, eps, dz, dkl, ws, E, B, D,
                      ld_in, raw_heads ? 1 : 0);
   if (dtheta)
-    hipLaunchKernelGGL(tc_theta_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, theta, ws, dtheta, nb, D,
+    hipLaunchKernelGGL(theta_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, theta, ws, dtheta, nb, D,
                        accumulate ? 1 : 0);
   return mmvae_launch_status();
 }

@@ -203,6 +203,9 @@ SIGNATURES = {
     "mmvae_tc_fusion_fwd": (c_i, [ctypes.POINTER(TcFwdArgs)] + [c_p] * 5 + [c_i] * 5 + [c_p]),
     "mmvae_tc_fusion_bwd": (c_i, [ctypes.POINTER(TcBwdArgs)] + [c_p] * 6 + [c_i] * 6 + [c_p]),
     "mmvae_tc_fusion_ws_floats": (c_sz, [c_i, c_i]),
+    "mmvae_js_fusion_fwd": (c_i, [ctypes.POINTER(TcFwdArgs), ctypes.POINTER(c_f)] + [c_p] * 6 + [c_i] * 5 + [c_p]),
+    "mmvae_js_fusion_bwd": (c_i, [ctypes.POINTER(TcBwdArgs), ctypes.POINTER(c_f)] + [c_p] * 7 + [c_i] * 6 + [c_p]),
+    "mmvae_js_fusion_ws_floats": (c_sz, [c_i, c_i]),
     "mmvae_bce_rowsum_fwd": (c_i, [c_p] * 3 + [c_i] * 3 + [c_p]),
     "mmvae_bce_sigmoid_clamp_bwd": (c_i, [c_p] * 4 + [c_i] * 3 + [c_p]),
     "mmvae_bce_rowsum_bwd": (c_i, [c_p] * 4 + [c_i] * 2 + [c_p]),

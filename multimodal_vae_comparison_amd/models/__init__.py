@@ -5,6 +5,7 @@ from .mmvae_models import POE as poe
 from .mmvae_models import MoPOE as mopoe
 from .mmvae_models import DMVAE as dmvae
 from .mmvae_models import MVTCAE as mvtcae
+from .mmvae_models import MMJSD as mmjsd
 from .vae import VAE
 
-__all__ = ["moe", "poe", "mopoe", "dmvae", "mvtcae", "VAE"]
+__all__ = ["moe", "poe", "mopoe", "dmvae", "mvtcae", "mmjsd", "VAE"]

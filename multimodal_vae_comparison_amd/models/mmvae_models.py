@@ -800,6 +800,106 @@ class MOE(TorchMMVAE):
         return self.make_output_dict(qz, px, zs, cross_decoder_dist=cross)
 
 
+class MMJSD(MOE):
+    """mmJSD, Jensen-Shannon objective (Sutter, Daunhawer, Vogt, NeurIPS 2020; not in the reference: a plugin on the base
+    class's contract).  The unimodal posteriors are MOE's, q_e = N(mu_e, sigma = lv_e); the KL of the mixture to the prior
+    is replaced by the Jensen-Shannon divergence of the M posteriors and the prior N(0, softmax(theta) D) with weights pi:
+    every one's KL to their weighted geometric mean, the dynamic prior.  Row b draws its latent from ONE expert,
+    sel[b] = (b M) // B (contiguous balanced chunks, the paper's mixture-component selection), and every modality is
+    decoded once from it (MOE's elbo: twice).  With r_m the reconstruction row sums (the sign POE gives them), kl[e] the
+    experts' rows and kl[M] the prior's:
+
+        loss = sum_b [ sum_m llik_m r_m(b) + beta (sum_e pi_e kl[e][b] + pi_M kl[M][b]) ]
+
+    `model_cfg: {prior_weight: w}`, 0 < w < 1, gives pi_M = w and every expert (1 - w) / M; the default is the paper's
+    uniform 1 / (M + 1).  The latent side of a step is ONE fused kernel each way (ops.js_fusion).  Inference, the
+    evaluation hooks and the metrics are MOE's, unchanged: conditioning on several modalities is the MIXTURE over their
+    posteriors, the dynamic prior is a training-time regulariser only."""
+
+    def __init__(self, vaes, n_latents: int, obj_config: dict, model_config=None):
+        for name, vae in vaes.items():
+            if vae.prior_str not in ("normal", "gaussian"):
+                raise NotImplementedError(f"mmjsd: prior '{vae.prior_str}' ({name}): the geometric mean and the KL terms to "
+                                          f"it are Gaussian; only normal priors are on this path")
+            if vae.private_latents is not None:
+                raise NotImplementedError(f"mmjsd: private_latents ({name}): the Jensen-Shannon objective has one shared "
+                                          f"latent space")
+        if obj_config.get("obj", "elbo") != "elbo":
+            raise NotImplementedError(f"mmjsd: obj '{obj_config['obj']}': the Jensen-Shannon bound is built on obj elbo")
+        if int(obj_config.get("K", 1)) != 1:
+            raise NotImplementedError(f"mmjsd: K = {obj_config['K']}: one latent sample per step (K = 1) only")
+        M = len(vaes)
+        w = float((model_config or {}).get("prior_weight", 1.0 / (M + 1)))
+        if not 0.0 < w < 1.0:
+            raise ValueError(f"mmjsd: model_cfg prior_weight = {w} must lie in (0, 1)")
+        super().__init__(vaes, n_latents, obj_config, model_config)
+        self.modelName = "mmjsd"
+        self.prior_weight = w
+        self._sel = {}      # (B, M, device) -> the rows' expert indices, built once: the captured step only reads it
+
+    def _js_pi(self):
+        """pi_0 .. pi_M: the experts' weights and, last, the prior's"""
+        M = len(self.vaes)
+        return [(1.0 - self.prior_weight) / M] * M + [self.prior_weight]
+
+    def _js_weights(self):
+        """rows of the loss assembly (loss, kld, kld_prior, kld_experts) over [M recon rows, M expert KL rows, the prior's]"""
+        M, beta, pi = len(self.vaes), float(self.obj_fn.beta), self._js_pi()
+        lam = [float(v.llik_scaling) for v in self.vaes.values()]
+        return [lam + [beta * p for p in pi],
+                [0.0] * M + pi,
+                [0.0] * M + [0.0] * M + [1.0],
+                [0.0] * M + [1.0 / M] * M + [0.0]]
+
+    def _selection(self, B, dev):
+        """sel[b] = (b M) // B as int32 on the device"""
+        M = len(self.vaes)
+        key = (B, M, str(dev))
+        if key not in self._sel:
+            self._sel[key] = ((torch.arange(B, dtype=torch.int64) * M) // B).to(device=dev, dtype=torch.int32)
+        return self._sel[key]
+
+    def objective(self, mods):
+        """one encoder pass and one decoder pass per modality (MOE's elbo: one and two), the towers on their streams"""
+        names = list(self.vaes.keys())
+        M = len(names)
+        missing = [n for n in names if mods[n]["data"] is None]
+        if missing:
+            raise ValueError(f"mmjsd.objective: {missing} has no data: training needs every modality (evaluation with "
+                             f"missing modalities goes through forward() / the metrics' given=)")
+        self._begin_step()
+        theta = self._pz_params[1]
+        dev = mods[names[0]]["data"].device
+        encs = [v.enc for v in self.vaes.values()]
+        # lv = softmax(u) + eta is applied by the fusion kernel (as MVTCAE.objective does): no softmax launch behind the heads
+        raw_heads = dev.type == "cuda" and all(hasattr(e, "raw_heads") and e.enc_mu_logvar for e in encs)
+        try:
+            for e in encs if raw_heads else []:
+                e.raw_heads = True
+            packed, streams, dev = self._encode_towers(mods)
+        finally:
+            for e in encs if raw_heads else []:
+                e.raw_heads = False
+        B, D = packed[0].shape[0], self.n_latents
+        eps = self._draw(B, D, dev)
+        _, kl, z = ops.js_fusion(theta, packed, eps, self._selection(B, dev), self._js_pi(), theta.grad, raw=raw_heads)
+
+        def decode(n, st):
+            vae = self.vaes[n]
+            out, _ = vae.dec({"latents": z.unsqueeze(0), "masks": mods[n]["masks"]})
+            return recon_rowsum(vae.ltype, out, mods[n])      # (B,)
+        recs = self._tower_phase(zip(names, streams), decode, dev, reads=[z], batch=mods)
+        out = ops.lincomb_rows(recs + [kl], self._js_weights())
+        with torch.no_grad():      # logged only: every modality's row sum over the batch
+            if M <= ops.H.LC_MAX_OUT:
+                ind = list(ops.lincomb_rows([r.detach() for r in recs],
+                                            [[1.0 if j == i else 0.0 for j in range(M)] for i in range(M)]))
+            else:
+                ind = [r.detach().sum() for r in recs]
+        return {"loss": out[0], "reconstruction_loss": ind, "kld": out[1], "kld_prior": out[2].detach(),
+                "kld_experts": out[3].detach()}
+
+
 class DMVAE(TorchMMVAE):
     """DMVAE, shared + private latents (mmvae_models.py:413-509), K = 1, all modalities present.
 

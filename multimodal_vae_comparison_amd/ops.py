@@ -1454,6 +1454,89 @@ def tc_fusion(theta, packed, eps, gtheta=None, raw=False):
     return TcFusion.apply(theta, gtheta, raw, eps, *packed)
 
 
+class JsFusion(Function):
+    """Weighted geometric mean of the E experts N(mu_e, sigma = lv_e) and the prior (the dynamic prior) -> KL of each of
+    the E + 1 to it (rows 0 .. E-1 the experts', row E the prior's) -> ONE reparameterised sample per row from expert
+    sel[b]: mmJSD's latent op (csrc/jsfusion.hip).  packed[e]: (B, 2 D) = [mu_e | lv_e] head outputs.  Returns prior
+    (2,B,D) = [mean, scale] [not differentiable], kl (E+1,B), z (B,D)."""
+
+    @staticmethod
+    def forward(ctx, theta, gtheta, raw, weights, sel, eps, *packed):
+        packed = [H.f32c(t) for t in packed]
+        theta, eps = H.f32c(theta), H.f32c(eps)
+        E = len(packed)
+        B, D2 = packed[0].shape
+        D = D2 // 2
+        assert all(p.shape == (B, D2) for p in packed) and eps.shape == (B, D) and theta.numel() == D
+        assert sel.dtype == torch.int32 and sel.shape == (B,) and sel.is_contiguous() and len(weights) == E + 1
+        dev = packed[0].device
+        prior = torch.empty(2, B, D, device=dev)
+        kl = torch.empty(E + 1, B, device=dev)
+        z = torch.empty(B, D, device=dev)
+        a = H.TcFwdArgs()
+        for e, p in enumerate(packed[:H.MAX_EXPERTS]):
+            a.mu[e] = p.data_ptr()
+            a.lv[e] = p.data_ptr() + 4 * D
+        w = (H.c_f * (E + 1))(*weights)
+        H.call("mmvae_js_fusion_fwd", ctypes.byref(a), w, H.ptr(theta), H.ptr(eps), H.ptr(sel), H.ptr(prior), H.ptr(kl),
+               H.ptr(z), E, B, D, D2, int(bool(raw)), H.stream())
+        ctx.save_for_backward(theta, eps, sel, *packed)
+        ctx.cfg = (gtheta, E, B, D, int(bool(raw)), w)
+        ctx.mark_non_differentiable(prior)
+        ctx.set_materialize_grads(False)
+        return prior, kl, z
+
+    @staticmethod
+    def backward(ctx, _dp, dkl, dz):
+        gtheta, E, B, D, raw, w = ctx.cfg
+        theta, eps, sel = ctx.saved_tensors[:3]
+        packed = ctx.saved_tensors[3:]
+        dev = theta.device
+        # (an absent upstream gradient goes in as NULL: the kernel takes it as zeros)
+        dkl = H.f32c(dkl) if dkl is not None else None
+        dz = H.f32c(dz) if dz is not None else None
+        dpacked = [torch.empty_like(p) for p in packed]
+        a = H.TcBwdArgs()
+        for e, p in enumerate(packed):
+            a.mu[e] = p.data_ptr()
+            a.lv[e] = p.data_ptr() + 4 * D
+            a.dmu[e] = dpacked[e].data_ptr()
+            a.dlv[e] = dpacked[e].data_ptr() + 4 * D
+        if gtheta is not None:
+            dth, acc, ret = gtheta, 1, None
+            GradReducer.writes(dev, gtheta)
+        elif ctx.needs_input_grad[0]:
+            dth = ret = torch.empty_like(theta)
+            acc = 0
+        else:
+            dth, acc, ret = None, 0, None
+        ws = H.workspace(H.lib().mmvae_js_fusion_ws_floats(B, D), dev)
+        H.call("mmvae_js_fusion_bwd", ctypes.byref(a), w, H.ptr(theta), H.ptr(eps), H.ptr(sel), H.ptr(dz), H.ptr(dkl),
+               H.ptr(dth), H.ptr(ws), E, B, D, 2 * D, raw, acc, H.stream())
+        return (ret, None, None, None, None, None, *dpacked)
+
+
+def js_fusion(theta, packed, eps, sel, weights, gtheta=None, raw=False):
+    """-> prior (2,B,D), kl (E+1,B), z (B,D) of the Jensen-Shannon fusion (JsFusion).  sel: the expert every row's sample is
+    drawn from, int32 (B,): a list or a CPU tensor is checked against [0, E) here and moved to the device, a device tensor
+    is taken as is (the kernel compares indices: a value no expert has gives a zero row).  weights: pi_0 .. pi_E, the
+    last one the prior's; gtheta, raw: as tc_fusion"""
+    E, dev = len(packed), packed[0].device
+    weights = [float(x) for x in weights]
+    if len(weights) != E + 1:
+        raise ValueError(f"js_fusion: {len(weights)} weights for {E} experts and the prior ({E + 1} wanted)")
+    if not (torch.is_tensor(sel) and sel.is_cuda):
+        sel = torch.as_tensor(sel).reshape(-1)
+        if sel.dtype.is_floating_point or sel.dtype == torch.bool:
+            raise ValueError(f"js_fusion: sel holds expert indices, not {sel.dtype}")
+        if sel.numel() and not (0 <= int(sel.min()) and int(sel.max()) < E):
+            raise ValueError(f"js_fusion: sel values must lie in [0, {E}): found [{int(sel.min())}, {int(sel.max())}]")
+        sel = sel.to(device=dev, dtype=torch.int32)
+    elif sel.dtype != torch.int32:
+        sel = sel.to(torch.int32)
+    return JsFusion.apply(theta, gtheta, raw, weights, sel.contiguous(), eps, *packed)
+
+
 class RowsFan(Function):
     """Latent samples -> the decoders' input batches in ONE launch, and every sample's gradient as ONE sum in backward
     (csrc/latent.hip: mmvae_rows_fan_fwd / _bwd).  plan = [(R, W, [(source index, row block r, first column c0), ...]), ...]:
