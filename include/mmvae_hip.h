@@ -416,6 +416,34 @@ int mmvae_js_fusion_bwd(const mmvae_tc_bwd_args* a, const float* weights, const 
                         int ld_in, int raw_heads, int accumulate, mmvae_stream_t stream);
 size_t mmvae_js_fusion_ws_floats(int B, int D);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mixture-of-experts prior (MMVM VAE: Sutter et al., "Unity by Diversity", NeurIPS 2024): ONE reparameterised sample from
+ * EVERY one of the E unimodal posteriors, the one-sample estimate of each posterior's KL to the uniform mixture of all E
+ * (the data-dependent prior), its closed-form KL to the fixed prior and the responsibilities, forward and backward
+ * (csrc/mixprior.hip).  The pointer tables are those of mmvae_poe_reparam_kl_*: mu[e] / lv[e] rows are ld_in floats apart,
+ * eps[e] / z[e] / dz[e] are contiguous (B,D); raw_heads, ws, dtheta and accumulate are those of mmvae_tc_fusion_*.  Expert j
+ * is q_j = N(mu_j, sigma_j = lv_j): the head is read as the SCALE, as the mixture of experts samples from it; the fixed
+ * prior is N(0, sp), sp = softmax(theta) D.  With z_m = mu_m + sigma_m eps_m:
+ *   u_mj = ((mu_m - mu_j) + sigma_m eps_m) / sigma_j
+ *   D_mj = sum_d [ -(u_mj - eps_m)(u_mj + eps_m) / 2 - log(sigma_j / sigma_m) ]  = log q_j(z_m) - log q_m(z_m), D_mm = 0
+ *   z[m] (B,D)    : z_m
+ *   kl (2E,B)     : row m     : log q_m(z_m) - log (1/E) sum_j q_j(z_m) = log E - log sum_j exp(D_mj)
+ *                   row E + m : sum_d KL(N(mu_m, sigma_m) || N(0, sp))
+ *   resp (E,E,B)  : resp[m][j] = softmax_j D_mj: the weight of q_j in the mixture density at z_m   (not differentiable)
+ * The absolute log-densities are never formed.
+ * bwd: dz[m] (B,D), dkl (2E,B), resp as the forward pass wrote it (the row sums are not taken again) -> dmu[e], dlv[e]
+ *   (d/d sigma_e; raw_heads: d/du), dtheta as mmvae_tc_fusion_bwd.  dkl NULL and every dz[m] NULL on its own: an absent
+ *   upstream gradient, taken as zeros.  Every sum in one fixed order, no atomics: bit-reproducible from run to run.
+ * 1 <= E <= MMVAE_MAX_EXPERTS and D <= 256; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing
+ * (mmvae_mixprior_ws_floats: 0).
+ * ---------------------------------------------------------------------------------------------- */
+int mmvae_mixprior_fwd(const mmvae_poe_fwd_args* a, const float* theta, float* kl, float* resp, int E, int B, int D,
+                       int ld_in, int raw_heads, mmvae_stream_t stream);
+int mmvae_mixprior_bwd(const mmvae_poe_bwd_args* a, const float* theta, const float* resp, const float* dkl,
+                       float* dtheta, float* ws, int E, int B, int D, int ld_in, int raw_heads, int accumulate,
+                       mmvae_stream_t stream);
+size_t mmvae_mixprior_ws_floats(int B, int D);
+
 /* Latent samples -> decoder inputs, and the transpose (round 6).  The reference decodes every subset's sample in a call of its
  * own (POE.objective, models/mmvae_models.py:159-187) and builds DMVAE's decoder inputs with torch.cat([z_shared, z_private], -1)
  * per pass (:494-502); here a decoder's passes are one batch, and the batches of ALL decoders are written by one launch:

@@ -1,0 +1,246 @@
+// Mixture-of-experts prior (MMVM VAE: Sutter et al., "Unity by Diversity", NeurIPS 2024) for gfx950: one reparameterised
+// sample from EVERY one of the E unimodal posteriors, the one-sample estimate of every posterior's KL to the uniform mixture
+// of all E (the data-dependent prior), its closed-form KL to the fixed prior and the responsibilities, forward and backward,
+// in one launch each way (+ the fold of the prior gradient).  The layout is jsfusion.hip's: one wavefront per sample, lanes
+// over the latent dimension in POE_SLOTS column slots, wave-shuffle row sums; no atomics and no in-launch election -- every
+// sum is taken in one fixed order.
+//
+// Expert j is q_j = N(mu_j, sigma_j = lv_j) (the head read as the SCALE, as MOE samples from it), the fixed prior is
+// N(0, sp), sp = softmax(theta) D.  Per row, with z_m = mu_m + sigma_m eps_m and h = (1/E) sum_j q_j:
+//   delta_mj = (mu_m - mu_j) + sigma_m eps_m                                    z_m - mu_j, formed from the difference
+//   u_mj     = delta_mj / sigma_j,   u_mm = eps_m
+//   D_mj     = sum_d [ -1/2 (u_mj - eps_m)(u_mj + eps_m) - log(sigma_j / sigma_m) ]   = log q_j(z_m) - log q_m(z_m), D_mm = 0
+//   kl_mix[m] = log q_m(z_m) - log h(z_m) = log E - log sum_j exp(D_mj)          (shifted by max_j D_mj >= 0)
+//   resp[m][j] = softmax_j D_mj
+//   kl_std[m] = sum_d KL(N(mu_m, sigma_m) || N(0, sp))
+// The absolute log-densities are never formed: at D = 256 they reach the hundreds and their difference keeps their
+// rounding, at scales of 1e-5 log sigma does (float32 on the host against float64: 4.8e-5 and 6.8e-5 of a KL entry against
+// 2.7e-6 and 7.4e-7 in this form).
+// Backward, with g_m = dkl[m], g'_m = dkl[E + m], gz_m = dz[m], c_mj = -g_m resp[m][j] (the responsibilities are read
+// back, the row sums are not taken again), r = 1 / sp^2, per element and for every ordered pair m != j:
+//   dmu_m  += -c_mj u_mj / sigma_j                      dmu_j  += c_mj u_mj / sigma_j
+//   dsg_m  +=  c_mj (1 / sigma_m - u_mj eps_m / sigma_j)  dsg_j  += c_mj (u_mj^2 - 1) / sigma_j
+// on top of dmu_m = gz_m + g'_m mu_m r, dsg_m = gz_m eps_m + g'_m (sigma_m r - 1 / sigma_m);
+//   dsp = sum_m g'_m (1 - (sigma_m^2 + mu_m^2) r) / sp.
+// The pairs are walked sample by sample (m outermost), so every gradient element is a sum over the E samples in order.
+#include "common.hpp"
+#include "latent_rows.hpp"
+
+__global__ __launch_bounds__(256) void mixprior_fwd_kernel(mmvae_poe_fwd_args a, const float* __restrict__ theta,
+                                                           float* __restrict__ kl, float* __restrict__ resp, int E, int B,
+                                                           int D, int ld, int raw) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * 4;
+  float sp[POE_SLOTS], sm[POE_SLOTS];
+  prior_sigma(theta, D, lane, sp, sm);
+  const float logE = logf((float)E);
+  for (int b = wave; b < B; b += nwaves) {
+    float dl[MMVAE_MAX_EXPERTS][MMVAE_MAX_EXPERTS], ks[MMVAE_MAX_EXPERTS];
+#pragma unroll
+    for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {
+      ks[m] = 0.f;
+#pragma unroll
+      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) dl[m][j] = 0.f;
+    }
+    float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS];
+    if (raw) {
+#pragma unroll
+      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
+        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
+    }
+#pragma unroll
+    for (int s = 0; s < POE_SLOTS; ++s) {
+      const int d = lane + 64 * s;
+      if (d < D) {
+        const size_t o = (size_t)b * D + d;    // contiguous (B,D) tensors
+        const size_t oi = (size_t)b * ld + d;  // strided expert tensors
+        float mu[MMVAE_MAX_EXPERTS], sg[MMVAE_MAX_EXPERTS], ep[MMVAE_MAX_EXPERTS];
+#pragma unroll
+        for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
+          if (e >= E) continue;
+          mu[e] = a.mu[e][oi];
+          sg[e] = a.lv[e][oi];
+          if (raw) sg[e] = expf(sg[e] - umx[e]) * uinv[e] + 1e-6f;
+          ep[e] = a.eps[e][o];
+          a.z[e][o] = mu[e] + sg[e] * ep[e];
+          ks[e] += kl_elem(mu[e], sg[e], sp[s]);
+        }
+#pragma unroll
+        for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {
+          if (m >= E) continue;
+#pragma unroll
+          for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
+            if (j >= E || j == m) continue;
+            const float u = ((mu[m] - mu[j]) + sg[m] * ep[m]) / sg[j];
+            dl[m][j] += -0.5f * (u - ep[m]) * (u + ep[m]) - logf(sg[j] / sg[m]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {
+      if (m >= E) continue;
+      const float kstd = wave_sum(ks[m]);
+      float mx = 0.f;      // D_mm = 0 is one of the E
+#pragma unroll
+      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
+        if (j >= E || j == m) continue;
+        dl[m][j] = wave_sum(dl[m][j]);
+        mx = fmaxf(mx, dl[m][j]);
+      }
+      float ex[MMVAE_MAX_EXPERTS], S = 0.f;
+#pragma unroll
+      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
+        if (j >= E) continue;
+        ex[j] = expf(dl[m][j] - mx);      // (dl[m][m] is the 0 it was set to)
+        S += ex[j];
+      }
+      if (lane == 0) {
+        kl[(size_t)m * B + b] = logE - (mx + logf(S));
+        kl[(size_t)(E + m) * B + b] = kstd;
+        const float invS = 1.0f / S;
+#pragma unroll
+        for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j)
+          if (j < E) resp[((size_t)m * E + j) * B + b] = ex[j] * invS;
+      }
+    }
+  }
+}
+
+// a.dz[m] / dkl == NULL: that upstream gradient is absent and counts as zeros
+__global__ __launch_bounds__(256) void mixprior_bwd_kernel(mmvae_poe_bwd_args a, const float* __restrict__ theta,
+                                                           const float* __restrict__ resp, const float* __restrict__ dkl,
+                                                           float* __restrict__ ws, int E, int B, int D, int ld, int raw) {
+  __shared__ float part[4][64 * POE_SLOTS];
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int nwaves = gridDim.x * 4;
+  float sp[POE_SLOTS], sm[POE_SLOTS], dsp[POE_SLOTS];
+  prior_sigma(theta, D, lane, sp, sm);
+#pragma unroll
+  for (int s = 0; s < POE_SLOTS; ++s) dsp[s] = 0.f;
+  for (int b = wave; b < B; b += nwaves) {
+    float c[MMVAE_MAX_EXPERTS][MMVAE_MAX_EXPERTS], gs[MMVAE_MAX_EXPERTS];
+#pragma unroll
+    for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {
+      if (m >= E) continue;
+      const float g = dkl ? dkl[(size_t)m * B + b] : 0.f;
+      gs[m] = dkl ? dkl[(size_t)(E + m) * B + b] : 0.f;
+#pragma unroll
+      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j)
+        if (j < E && j != m) c[m][j] = -g * resp[((size_t)m * E + j) * B + b];
+    }
+    float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS], udot[MMVAE_MAX_EXPERTS];
+#pragma unroll
+    for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) udot[e] = 0.f;
+    if (raw) {
+#pragma unroll
+      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
+        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
+    }
+#pragma unroll
+    for (int s = 0; s < POE_SLOTS; ++s) {
+      const int d = lane + 64 * s;
+      if (d < D) {
+        const size_t o = (size_t)b * D + d;    // contiguous (B,D) tensors
+        const size_t oi = (size_t)b * ld + d;  // strided expert tensors
+        float mu[MMVAE_MAX_EXPERTS], sg[MMVAE_MAX_EXPERTS], ep[MMVAE_MAX_EXPERTS], inv[MMVAE_MAX_EXPERTS];
+        float dmu[MMVAE_MAX_EXPERTS], dsg[MMVAE_MAX_EXPERTS];
+        const float r = 1.0f / (sp[s] * sp[s]);
+        float dspv = 0.f;
+#pragma unroll
+        for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
+          if (e >= E) continue;
+          mu[e] = a.mu[e][oi];
+          sg[e] = a.lv[e][oi];
+          if (raw) sg[e] = expf(sg[e] - umx[e]) * uinv[e] + 1e-6f;
+          ep[e] = a.eps[e][o];
+          inv[e] = 1.0f / sg[e];
+          const float gz = a.dz[e] ? a.dz[e][o] : 0.f;
+          dmu[e] = gz + gs[e] * (mu[e] * r);
+          dsg[e] = gz * ep[e] + gs[e] * (sg[e] * r - inv[e]);
+          dspv += gs[e] * ((1.0f - (sg[e] * sg[e] + mu[e] * mu[e]) * r) / sp[s]);
+        }
+        dsp[s] += dspv;
+#pragma unroll
+        for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {      // sample m: its own expert's terms and every other expert's
+          if (m >= E) continue;
+#pragma unroll
+          for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
+            if (j >= E || j == m) continue;
+            const float u = ((mu[m] - mu[j]) + sg[m] * ep[m]) / sg[j];
+            const float t = c[m][j] * (u * inv[j]);
+            dmu[m] -= t;
+            dmu[j] += t;
+            dsg[m] += c[m][j] * (inv[m] - u * ep[m] * inv[j]);
+            dsg[j] += c[m][j] * ((u * u - 1.0f) * inv[j]);
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
+          if (e >= E) continue;
+          a.dmu[e][oi] = dmu[e];
+          a.dlv[e][oi] = dsg[e];
+          udot[e] += (sg[e] - 1e-6f) * dsg[e];
+        }
+      }
+    }
+    if (raw) {      // through sigma = softmax(u) + 1e-6:  du = s (dsg - sum(s dsg)),  s = sigma - 1e-6
+#pragma unroll
+      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
+        if (e >= E) continue;
+        const float dot = wave_sum(udot[e]);
+#pragma unroll
+        for (int s = 0; s < POE_SLOTS; ++s) {
+          const int d = lane + 64 * s;
+          if (d < D) {
+            const size_t oi = (size_t)b * ld + d;
+            const float sv = expf(a.lv[e][oi] - umx[e]) * uinv[e];
+            // (one column: the softmax of one logit is the constant 1 and du is 0, as in jsfusion.hip)
+            a.dlv[e][oi] = D == 1 ? 0.f : sv * (a.dlv[e][oi] - dot);
+          }
+        }
+      }
+    }
+  }
+  // the workgroup's partial prior-gradient row: its four waves in wave order
+#pragma unroll
+  for (int s = 0; s < POE_SLOTS; ++s) part[threadIdx.x >> 6][lane + 64 * s] = dsp[s];
+  __syncthreads();
+  if ((int)threadIdx.x < D)
+    ws[(size_t)blockIdx.x * D + threadIdx.x] =
+        part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+static inline bool mixprior_supported(int E, int D) { return E <= MMVAE_MAX_EXPERTS && D <= 64 * POE_SLOTS; }
+
+extern "C" size_t mmvae_mixprior_ws_floats(int B, int D) {
+  if (B <= 0 || D <= 0 || D > 64 * POE_SLOTS) return 0;
+  return (size_t)poe_blocks(B) * D;
+}
+
+extern "C" int mmvae_mixprior_fwd(const mmvae_poe_fwd_args* a, const float* theta, float* kl, float* resp, int E, int B,
+                                  int D, int ld_in, int raw_heads, mmvae_stream_t stream) {
+  MMVAE_CHECK_ARG(a && theta && kl && resp && B > 0 && D > 0 && E > 0 && ld_in >= D);
+  if (!mixprior_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
+  for (int e = 0; e < E; ++e) MMVAE_CHECK_ARG(a->mu[e] && a->lv[e] && a->eps[e] && a->z[e]);
+  hipLaunchKernelGGL(mixprior_fwd_kernel, dim3(poe_blocks(B)), dim3(256), 0, (hipStream_t)stream, *a, theta, kl, resp, E,
+                     B, D, ld_in, raw_heads ? 1 : 0);
+  return mmvae_launch_status();
+}
+
+extern "C" int mmvae_mixprior_bwd(const mmvae_poe_bwd_args* a, const float* theta, const float* resp, const float* dkl,
+                                  float* dtheta, float* ws, int E, int B, int D, int ld_in, int raw_heads, int accumulate,
+                                  mmvae_stream_t stream) {
+  MMVAE_CHECK_ARG(a && theta && resp && ws && B > 0 && D > 0 && E > 0 && ld_in >= D);
+  if (!mixprior_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
+  for (int e = 0; e < E; ++e) MMVAE_CHECK_ARG(a->mu[e] && a->lv[e] && a->eps[e] && a->dmu[e] && a->dlv[e]);
+  const int nb = poe_blocks(B);
+  hipLaunchKernelGGL(mixprior_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *a, theta, resp, dkl, ws, E, B, D,
+                     ld_in, raw_heads ? 1 : 0);
+  if (dtheta)
+    hipLaunchKernelGGL(theta_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, theta, ws, dtheta, nb, D,
+                       accumulate ? 1 : 0);
+  return mmvae_launch_status();
+}

@@ -206,6 +206,9 @@ SIGNATURES = {
     "mmvae_js_fusion_fwd": (c_i, [ctypes.POINTER(TcFwdArgs), ctypes.POINTER(c_f)] + [c_p] * 6 + [c_i] * 5 + [c_p]),
     "mmvae_js_fusion_bwd": (c_i, [ctypes.POINTER(TcBwdArgs), ctypes.POINTER(c_f)] + [c_p] * 7 + [c_i] * 6 + [c_p]),
     "mmvae_js_fusion_ws_floats": (c_sz, [c_i, c_i]),
+    "mmvae_mixprior_fwd": (c_i, [ctypes.POINTER(PoeFwdArgs)] + [c_p] * 3 + [c_i] * 5 + [c_p]),
+    "mmvae_mixprior_bwd": (c_i, [ctypes.POINTER(PoeBwdArgs)] + [c_p] * 5 + [c_i] * 6 + [c_p]),
+    "mmvae_mixprior_ws_floats": (c_sz, [c_i, c_i]),
     "mmvae_bce_rowsum_fwd": (c_i, [c_p] * 3 + [c_i] * 3 + [c_p]),
     "mmvae_bce_sigmoid_clamp_bwd": (c_i, [c_p] * 4 + [c_i] * 3 + [c_p]),
     "mmvae_bce_rowsum_bwd": (c_i, [c_p] * 4 + [c_i] * 2 + [c_p]),

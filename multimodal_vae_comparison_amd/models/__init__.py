@@ -6,6 +6,7 @@ from .mmvae_models import MoPOE as mopoe
 from .mmvae_models import DMVAE as dmvae
 from .mmvae_models import MVTCAE as mvtcae
 from .mmvae_models import MMJSD as mmjsd
+from .mmvae_models import MMVM as mmvm
 from .vae import VAE
 
-__all__ = ["moe", "poe", "mopoe", "dmvae", "mvtcae", "mmjsd", "VAE"]
+__all__ = ["moe", "poe", "mopoe", "dmvae", "mvtcae", "mmjsd", "mmvm", "VAE"]

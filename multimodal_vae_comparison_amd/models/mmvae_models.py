@@ -900,6 +900,96 @@ class MMJSD(MOE):
                 "kld_experts": out[3].detach()}
 
 
+class MMVM(MOE):
+    """MMVM VAE, mixture-of-experts prior (Sutter et al., "Unity by Diversity", NeurIPS 2024; not in the reference: a plugin
+    on the base class's contract).  Nothing is aggregated: every modality keeps its own posterior q_m = N(mu_m, sigma = lv_m)
+    (MOE's), its own sample z_m and decodes itself from it alone.  The fixed prior is replaced by a data-dependent one,
+    h = (1/M) sum_j q_j of the same sample, which pulls the M posteriors towards each other.  With r_m the reconstruction
+    row sums (the sign POE gives them), kl_mix[m] = log q_m(z_m) - log h(z_m), the one-sample estimate of KL(q_m || h), and
+    kl_std[m] = KL(q_m || N(0, softmax(theta) D)) in closed form:
+
+        loss = sum_b [ sum_m llik_m r_m(b) + beta sum_m (alpha kl_mix[m][b] + (1 - alpha) kl_std[m][b]) ]
+
+    `model_cfg: {alpha: a}`, 0 <= a <= 1, default 1 (the paper's objective); a = 0 is M independent VAEs, at a = 1 the
+    prior parameter receives an exactly zero gradient.  The latent side of a step is ONE fused kernel each way
+    (ops.mixprior_fusion).  Inference, the evaluation hooks and the metrics are MOE's, unchanged.  With the default alpha
+    the objective matches nothing to N(0, 1): joint generation should draw from a density fitted to the latents
+    (fit_latent_density / sample_latent_density, handed to the metrics as eps= / joint_eps=)."""
+
+    def __init__(self, vaes, n_latents: int, obj_config: dict, model_config=None):
+        for name, vae in vaes.items():
+            if vae.prior_str not in ("normal", "gaussian"):
+                raise NotImplementedError(f"mmvm: prior '{vae.prior_str}' ({name}): the mixture prior's densities and the KL "
+                                          f"terms are Gaussian; only normal priors are on this path")
+            if vae.private_latents is not None:
+                raise NotImplementedError(f"mmvm: private_latents ({name}): the mixture-of-experts prior has one shared "
+                                          f"latent space")
+        if obj_config.get("obj", "elbo") != "elbo":
+            raise NotImplementedError(f"mmvm: obj '{obj_config['obj']}': the mixture-prior bound is built on obj elbo")
+        if int(obj_config.get("K", 1)) != 1:
+            raise NotImplementedError(f"mmvm: K = {obj_config['K']}: one latent sample per modality and step (K = 1) only")
+        alpha = float((model_config or {}).get("alpha", 1.0))
+        if not 0.0 <= alpha <= 1.0:
+            raise ValueError(f"mmvm: model_cfg alpha = {alpha} must lie in [0, 1]")
+        super().__init__(vaes, n_latents, obj_config, model_config)
+        self.modelName = "mmvm"
+        self.alpha = alpha
+
+    def _mm_weights(self):
+        """rows of the loss assembly (loss, kld, kld_mix, kld_std) over [M recon rows, M kl_mix rows, M kl_std rows]"""
+        M, a, beta = len(self.vaes), self.alpha, float(self.obj_fn.beta)
+        lam = [float(v.llik_scaling) for v in self.vaes.values()]
+        return [lam + [beta * a] * M + [beta * (1.0 - a)] * M,
+                [0.0] * M + [a] * M + [1.0 - a] * M,
+                [0.0] * M + [1.0] * M + [0.0] * M,
+                [0.0] * M + [0.0] * M + [1.0] * M]
+
+    def objective(self, mods):
+        """one encoder pass and one decoder pass per modality (MOE's elbo: one and two), the towers on their streams"""
+        names = list(self.vaes.keys())
+        M = len(names)
+        missing = [n for n in names if mods[n]["data"] is None]
+        if missing:
+            raise ValueError(f"mmvm.objective: {missing} has no data: training needs every modality (evaluation with "
+                             f"missing modalities goes through forward() / the metrics' given=)")
+        self._begin_step()
+        theta = self._pz_params[1]
+        dev = mods[names[0]]["data"].device
+        encs = [v.enc for v in self.vaes.values()]
+        # lv = softmax(u) + eta is applied by the fusion kernel (as MMJSD.objective does): no softmax launch behind the heads
+        raw_heads = dev.type == "cuda" and all(hasattr(e, "raw_heads") and e.enc_mu_logvar for e in encs)
+        try:
+            for e in encs if raw_heads else []:
+                e.raw_heads = True
+            packed, streams, dev = self._encode_towers(mods)
+        finally:
+            for e in encs if raw_heads else []:
+                e.raw_heads = False
+        B, D = packed[0].shape[0], self.n_latents
+        if self.eps_override is not None:      # M recorded draws, in modality order
+            eps = torch.stack([self._draw(B, D, dev) for _ in range(M)])
+        else:
+            eps = ops.randn((M, B, D), self._noise_state())
+        zs, kl, resp = ops.mixprior_fusion(theta, packed, eps, theta.grad, raw=raw_heads)
+
+        def decode(i, st):
+            vae = self.vaes[names[i]]
+            out, _ = vae.dec({"latents": zs[i].unsqueeze(0), "masks": mods[names[i]]["masks"]})
+            return recon_rowsum(vae.ltype, out, mods[names[i]])      # (B,)
+        recs = self._tower_phase(enumerate(streams), decode, dev, reads=list(zs), batch=mods)
+        out = ops.lincomb_rows(recs + [kl], self._mm_weights())
+        with torch.no_grad():      # logged only: every modality's row sum over the batch, the mean own-responsibility
+            if M <= ops.H.LC_MAX_OUT:
+                ind = list(ops.lincomb_rows([r.detach() for r in recs],
+                                            [[1.0 if j == i else 0.0 for j in range(M)] for i in range(M)]))
+            else:
+                ind = [r.detach().sum() for r in recs]
+            # 1 / M: the posteriors are indistinguishable; 1: they are disjoint and the regulariser's gradient has vanished
+            resp_self = resp.diagonal(dim1=0, dim2=1).mean()
+        return {"loss": out[0], "reconstruction_loss": ind, "kld": out[1], "kld_mix": out[2].detach(),
+                "kld_std": out[3].detach(), "resp_self": resp_self}
+
+
 class DMVAE(TorchMMVAE):
     """DMVAE, shared + private latents (mmvae_models.py:413-509), K = 1, all modalities present.
 

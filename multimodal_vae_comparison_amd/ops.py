@@ -1537,6 +1537,82 @@ def js_fusion(theta, packed, eps, sel, weights, gtheta=None, raw=False):
     return JsFusion.apply(theta, gtheta, raw, weights, sel.contiguous(), eps, *packed)
 
 
+class MixPriorFusion(Function):
+    """ONE reparameterised sample from EVERY expert N(mu_e, sigma = lv_e) -> the one-sample estimate of every expert's KL
+    to the uniform mixture of all E (rows 0 .. E-1) and its closed-form KL to the prior (rows E .. 2E-1) -> the
+    responsibilities: the MMVM VAE's latent op (csrc/mixprior.hip).  packed[e]: (B, 2 D) = [mu_e | lv_e] head outputs, eps
+    (E,B,D).  Returns kl (2E,B), resp (E,E,B) [not differentiable], z_0 .. z_{E-1} (B,D) each: E outputs, so that every
+    decoder's gradient arrives on its own (or as None) and goes to the kernel as it is."""
+
+    @staticmethod
+    def forward(ctx, theta, gtheta, raw, eps, *packed):
+        packed = [H.f32c(t) for t in packed]
+        theta, eps = H.f32c(theta), H.f32c(eps)
+        E = len(packed)
+        B, D2 = packed[0].shape
+        D = D2 // 2
+        assert all(p.shape == (B, D2) for p in packed) and eps.shape == (E, B, D) and theta.numel() == D
+        dev = packed[0].device
+        kl = torch.empty(2 * E, B, device=dev)
+        resp = torch.empty(E, E, B, device=dev)
+        zs = [torch.empty(B, D, device=dev) for _ in range(E)]
+        a = H.PoeFwdArgs()
+        for e, p in enumerate(packed[:H.MAX_EXPERTS]):
+            a.mu[e] = p.data_ptr()
+            a.lv[e] = p.data_ptr() + 4 * D
+            a.eps[e] = eps.data_ptr() + 4 * e * B * D
+            a.z[e] = zs[e].data_ptr()
+        H.call("mmvae_mixprior_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(kl), H.ptr(resp), E, B, D, D2, int(bool(raw)),
+               H.stream())
+        ctx.save_for_backward(theta, eps, resp, *packed)
+        ctx.cfg = (gtheta, E, B, D, int(bool(raw)))
+        ctx.mark_non_differentiable(resp)
+        ctx.set_materialize_grads(False)
+        return (kl, resp, *zs)
+
+    @staticmethod
+    def backward(ctx, dkl, _dresp, *dzs):
+        gtheta, E, B, D, raw = ctx.cfg
+        theta, eps, resp = ctx.saved_tensors[:3]
+        packed = ctx.saved_tensors[3:]
+        dev = theta.device
+        # (an absent upstream gradient goes in as NULL: the kernel takes it as zeros)
+        dkl = H.f32c(dkl) if dkl is not None else None
+        dzs = [H.f32c(g) if g is not None else None for g in dzs]
+        dpacked = [torch.empty_like(p) for p in packed]
+        a = H.PoeBwdArgs()
+        for e, p in enumerate(packed):
+            a.mu[e] = p.data_ptr()
+            a.lv[e] = p.data_ptr() + 4 * D
+            a.eps[e] = eps.data_ptr() + 4 * e * B * D
+            a.dz[e] = H.ptr(dzs[e])
+            a.dmu[e] = dpacked[e].data_ptr()
+            a.dlv[e] = dpacked[e].data_ptr() + 4 * D
+        if gtheta is not None:
+            dth, acc, ret = gtheta, 1, None
+            GradReducer.writes(dev, gtheta)
+        elif ctx.needs_input_grad[0]:
+            dth = ret = torch.empty_like(theta)
+            acc = 0
+        else:
+            dth, acc, ret = None, 0, None
+        ws = H.workspace(H.lib().mmvae_mixprior_ws_floats(B, D), dev)
+        H.call("mmvae_mixprior_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(resp), H.ptr(dkl), H.ptr(dth), H.ptr(ws), E, B, D,
+               2 * D, raw, acc, H.stream())
+        return (ret, None, None, None, *dpacked)
+
+
+def mixprior_fusion(theta, packed, eps, gtheta=None, raw=False):
+    """-> z (a tuple of E tensors (B,D), z[e] = mu_e + sigma_e eps[e]), kl (2E,B), resp (E,E,B) of the mixture-of-experts
+    prior (MixPriorFusion).  eps: (E,B,D) standard-normal draws; gtheta, raw: as tc_fusion"""
+    E = len(packed)
+    if tuple(eps.shape) != (E, packed[0].shape[0], packed[0].shape[1] // 2):
+        raise ValueError(f"mixprior_fusion: eps is {tuple(eps.shape)}; {E} experts of shape {tuple(packed[0].shape)} want "
+                         f"({E}, {packed[0].shape[0]}, {packed[0].shape[1] // 2})")
+    kl, resp, *zs = MixPriorFusion.apply(theta, gtheta, raw, eps, *packed)
+    return tuple(zs), kl, resp
+
+
 class RowsFan(Function):
     """Latent samples -> the decoders' input batches in ONE launch, and every sample's gradient as ONE sum in backward
     (csrc/latent.hip: mmvae_rows_fan_fwd / _bwd).  plan = [(R, W, [(source index, row block r, first column c0), ...]), ...]:

@@ -136,7 +136,7 @@ def step_flops_per_sample(meta):
     M = len(meta["mods"])
     K = meta.get("K", 1)
     passes = {"mopoe": (1, 1), "poe": (2 ** (M - 1), 2 ** M - 1), "moe": (1, M * K), "dmvae": (1, 3), "mvtcae": (1, 1),
-              "mmjsd": (1, 1)}[meta["mixing"]]
+              "mmjsd": (1, 1), "mmvm": (1, 1)}[meta["mixing"]]
     macs = 0
     for m in meta["mods"]:
         e, d = tower_macs(m, meta["D"], meta["T"])
