@@ -64,11 +64,7 @@ __global__ __launch_bounds__(256) void js_fwd_kernel(mmvae_tc_fwd_args a, js_wei
 #pragma unroll
     for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) klacc[e] = 0.f;
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS];
-    if (raw) {
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
-        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
-    }
+    if (raw) raw_head_stats(a.lv, E, (size_t)b * ld, D, lane, umx, uinv);
 #pragma unroll
     for (int s = 0; s < POE_SLOTS; ++s) {
       const int d = lane + 64 * s;
@@ -139,11 +135,7 @@ __global__ __launch_bounds__(256) void js_bwd_kernel(mmvae_tc_bwd_args a, js_wei
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS], udot[MMVAE_MAX_EXPERTS];
 #pragma unroll
     for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) udot[e] = 0.f;
-    if (raw) {
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
-        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
-    }
+    if (raw) raw_head_stats(a.lv, E, (size_t)b * ld, D, lane, umx, uinv);
 #pragma unroll
     for (int s = 0; s < POE_SLOTS; ++s) {
       const int d = lane + 64 * s;
@@ -196,34 +188,10 @@ __global__ __launch_bounds__(256) void js_bwd_kernel(mmvae_tc_bwd_args a, js_wei
         dsp[s] += gP * (P * sp[s] - 1.0f / sp[s]) - 2.0f * Tp * dTp / sp[s];
       }
     }
-    if (raw) {      // through sigma = softmax(u) + 1e-6:  du = s (dsg - sum(s dsg)),  s = sigma - 1e-6
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
-        if (e >= E) continue;
-        const float dot = wave_sum(udot[e]);
-#pragma unroll
-        for (int s = 0; s < POE_SLOTS; ++s) {
-          const int d = lane + 64 * s;
-          if (d < D) {
-            const size_t oi = (size_t)b * ld + d;
-            const float sv = expf(a.lv[e][oi] - umx[e]) * uinv[e];
-            // (one column: the softmax of one logit is the constant 1 and du is 0, as in tcfusion.hip)
-            a.dlv[e][oi] = D == 1 ? 0.f : sv * (a.dlv[e][oi] - dot);
-          }
-        }
-      }
-    }
+    if (raw) raw_head_bwd(a.lv, a.dlv, E, (size_t)b * ld, D, lane, umx, uinv, udot);
   }
-  // the workgroup's partial prior-gradient row: its four waves in wave order
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) part[threadIdx.x >> 6][lane + 64 * s] = dsp[s];
-  __syncthreads();
-  if ((int)threadIdx.x < D)
-    ws[(size_t)blockIdx.x * D + threadIdx.x] =
-        part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  prior_grad_row(dsp, part, ws, D, lane);
 }
-
-static inline bool js_supported(int E, int D) { return E <= MMVAE_MAX_EXPERTS && D <= 64 * POE_SLOTS; }
 
 // pi_0 .. pi_E from the host: every one finite and >= 0, their sum > 0
 static inline bool js_take_weights(const float* weights, int E, js_weights* w) {
@@ -238,16 +206,13 @@ static inline bool js_take_weights(const float* weights, int E, js_weights* w) {
   return true;
 }
 
-extern "C" size_t mmvae_js_fusion_ws_floats(int B, int D) {
-  if (B <= 0 || D <= 0 || D > 64 * POE_SLOTS) return 0;
-  return (size_t)poe_blocks(B) * D;
-}
+extern "C" size_t mmvae_js_fusion_ws_floats(int B, int D) { return fusion_ws_floats(B, D); }
 
 extern "C" int mmvae_js_fusion_fwd(const mmvae_tc_fwd_args* a, const float* weights, const float* theta, const float* eps,
                                    const int* sel, float* prior, float* kl, float* z, int E, int B, int D, int ld_in,
                                    int raw_heads, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(a && weights && theta && eps && sel && prior && kl && z && B > 0 && D > 0 && E > 0 && ld_in >= D);
-  if (!js_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
+  if (!fusion_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
   for (int e = 0; e < E; ++e) MMVAE_CHECK_ARG(a->mu[e] && a->lv[e]);
   js_weights w;
   MMVAE_CHECK_ARG(js_take_weights(weights, E, &w));
@@ -260,15 +225,12 @@ extern "C" int mmvae_js_fusion_bwd(const mmvae_tc_bwd_args* a, const float* weig
                                    const int* sel, const float* dz, const float* dkl, float* dtheta, float* ws, int E,
                                    int B, int D, int ld_in, int raw_heads, int accumulate, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(a && weights && theta && eps && sel && ws && B > 0 && D > 0 && E > 0 && ld_in >= D);
-  if (!js_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
+  if (!fusion_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
   for (int e = 0; e < E; ++e) MMVAE_CHECK_ARG(a->mu[e] && a->lv[e] && a->dmu[e] && a->dlv[e]);
   js_weights w;
   MMVAE_CHECK_ARG(js_take_weights(weights, E, &w));
-  const int nb = poe_blocks(B);
-  hipLaunchKernelGGL(js_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *a, w, theta, eps, sel, dz, dkl, ws, E, B,
+  hipLaunchKernelGGL(js_bwd_kernel, dim3(poe_blocks(B)), dim3(256), 0, (hipStream_t)stream, *a, w, theta, eps, sel, dz, dkl, ws, E, B,
                      D, ld_in, raw_heads ? 1 : 0);
-  if (dtheta)
-    hipLaunchKernelGGL(theta_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, theta, ws, dtheta, nb, D,
-                       accumulate ? 1 : 0);
+  launch_theta_fold(theta, ws, dtheta, B, D, accumulate, stream);
   return mmvae_launch_status();
 }

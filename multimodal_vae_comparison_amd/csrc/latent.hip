@@ -68,11 +68,7 @@ __global__ __launch_bounds__(256) void poe_fwd_kernel(mmvae_poe_fwd_args a, cons
 #pragma unroll
     for (int j = 0; j <= MMVAE_MAX_EXPERTS; ++j) klacc[j] = 0.f;
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS];
-    if (raw) {
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
-        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
-    }
+    if (raw) raw_head_stats(a.lv, E, (size_t)b * ld, D, lane, umx, uinv);
 #pragma unroll
     for (int s = 0; s < POE_SLOTS; ++s) {
       const int d = lane + 64 * s;
@@ -132,12 +128,6 @@ __global__ __launch_bounds__(256) void poe_fwd_kernel(mmvae_poe_fwd_args a, cons
 //   dmu_e = G_mu * T_e * varJ                                  + gk_e * mu_e / sp^2
 //   dlv_e = [G_mu (mu_e - muJ) varJ - G_var varJ^2] * (-exp(lv_e) T_e^2)  + gk_e * (lv_e / sp^2 - 1 / lv_e)
 //   dsp  += sum_j gk_j * (1 - (s_j^2 + mu_j^2) / sp^2) / sp
-// COHERENT: the partial rows were written by other workgroups of the SAME launch with agent-scope write-through stores
-// (poe_ws_store); read them with agent-scope loads that bypass the (per-XCD, non-coherent) L2
-template <bool COHERENT = false>
-__device__ __forceinline__ void poe_theta_body(const float* __restrict__ theta, const float* __restrict__ ws,
-                                               float* __restrict__ dtheta, int nrows, int D, int accumulate,
-                                               float (*part)[64 * POE_SLOTS]);
 __device__ __forceinline__ void poe_ws_store(float* p, float v) {
   __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -177,11 +167,7 @@ __global__ __launch_bounds__(256) void poe_bwd_kernel(mmvae_poe_bwd_args a, cons
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS], udot[MMVAE_MAX_EXPERTS];
 #pragma unroll
     for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) udot[e] = 0.f;
-    if (raw) {
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
-        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
-    }
+    if (raw) raw_head_stats(a.lv, E, (size_t)b * ld, D, lane, umx, uinv);
 #pragma unroll
     for (int s = 0; s < POE_SLOTS; ++s) {
       const int d = lane + 64 * s;
@@ -246,24 +232,7 @@ __global__ __launch_bounds__(256) void poe_bwd_kernel(mmvae_poe_bwd_args a, cons
       dsp[s] += dspe;
       }
     }
-    if (raw) {      // through lv = softmax(u) + 1e-6:  du = s (dlv - sum(s dlv)),  s = lv - 1e-6
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
-        if (e >= E) continue;
-        const float dot = wave_sum(udot[e]);
-#pragma unroll
-        for (int s = 0; s < POE_SLOTS; ++s) {
-          const int d = lane + 64 * s;
-          if (d < D) {
-            const size_t oi = (size_t)b * ld + d;
-            const float sv = expf(a.lv[e][oi] - umx[e]) * uinv[e];
-            // (D == 1: the softmax of one logit is the constant 1 and du is 0; s = lv - 1e-6 in `dot` is rounded, and
-            // s (dlv - s dlv) came out as 6e-8 dlv)
-            a.dlv[e][oi] = D == 1 ? 0.f : sv * (a.dlv[e][oi] - dot);
-          }
-        }
-      }
-    }
+    if (raw) raw_head_bwd(a.lv, a.dlv, E, (size_t)b * ld, D, lane, umx, uinv, udot);
   }
 #pragma unroll
   for (int s = 0; s < POE_SLOTS; ++s) {
@@ -283,54 +252,7 @@ __global__ __launch_bounds__(256) void poe_bwd_kernel(mmvae_poe_bwd_args a, cons
   }
 }
 
-// dtheta_d (+)= D * s_d * (dsp_d - sum_k s_k dsp_k), dsp = sum over the per-wave partial rows.
-// 4 waves split the rows, 8 independent loads in flight per lane, LDS combine (D <= 256).
-template <bool COHERENT>
-__device__ __forceinline__ void poe_theta_body(const float* __restrict__ theta, const float* __restrict__ ws,
-                                               float* __restrict__ dtheta, int nrows, int D, int accumulate,
-                                               float (*part)[64 * POE_SLOTS]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  auto ld = [&](size_t i) -> float {
-    return COHERENT ? __hip_atomic_load(ws + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : ws[i];
-  };
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    float acc = 0.f;
-    if (d < D) {
-      int r = wave;
-      for (; r + 28 < nrows; r += 32) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = ld((size_t)(r + 4 * u) * D + d);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc += v[u];
-      }
-      for (; r < nrows; r += 4) acc += ld((size_t)r * D + d);
-    }
-    part[wave][d] = acc;
-  }
-  __syncthreads();
-  if (wave != 0) return;
-  float sp[POE_SLOTS], sm[POE_SLOTS], dsp[POE_SLOTS];
-  prior_sigma(theta, D, lane, sp, sm);
-  float dot = 0.f;
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    dsp[s] = part[0][d] + part[1][d] + part[2][d] + part[3][d];
-    dot += dsp[s] * sm[s];
-  }
-  dot = wave_sum(dot);
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) {
-    const int d = lane + 64 * s;
-    if (d < D) {
-      float g = (float)D * sm[s] * (dsp[s] - dot);
-      dtheta[d] = accumulate ? dtheta[d] + g : g;
-    }
-  }
-}
+// the fold as a second launch (no ticket): latent_rows.hpp's body over the per-wave partial rows
 __global__ __launch_bounds__(256) void poe_theta_kernel(const float* __restrict__ theta, const float* __restrict__ ws,
                                                         float* __restrict__ dtheta, int nrows, int D, int accumulate) {
   __shared__ float part[4][64 * POE_SLOTS];

@@ -31,11 +31,7 @@ __global__ __launch_bounds__(256) void tc_fwd_kernel(mmvae_tc_fwd_args a, const 
 #pragma unroll
     for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) klacc[e] = 0.f;
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS];
-    if (raw) {
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
-        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
-    }
+    if (raw) raw_head_stats(a.lv, E, (size_t)b * ld, D, lane, umx, uinv);
 #pragma unroll
     for (int s = 0; s < POE_SLOTS; ++s) {
       const int d = lane + 64 * s;
@@ -99,11 +95,7 @@ __global__ __launch_bounds__(256) void tc_bwd_kernel(mmvae_tc_bwd_args a, const 
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS], udot[MMVAE_MAX_EXPERTS];
 #pragma unroll
     for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) udot[e] = 0.f;
-    if (raw) {
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e)
-        if (e < E) row_softmax_stats(a.lv[e] + (size_t)b * ld, D, lane, &umx[e], &uinv[e]);
-    }
+    if (raw) raw_head_stats(a.lv, E, (size_t)b * ld, D, lane, umx, uinv);
 #pragma unroll
     for (int s = 0; s < POE_SLOTS; ++s) {
       const int d = lane + 64 * s;
@@ -150,45 +142,18 @@ __global__ __launch_bounds__(256) void tc_bwd_kernel(mmvae_tc_bwd_args a, const 
         }
       }
     }
-    if (raw) {      // through lv = softmax(u) + 1e-6:  du = s (dlv - sum(s dlv)),  s = lv - 1e-6
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
-        if (e >= E) continue;
-        const float dot = wave_sum(udot[e]);
-#pragma unroll
-        for (int s = 0; s < POE_SLOTS; ++s) {
-          const int d = lane + 64 * s;
-          if (d < D) {
-            const size_t oi = (size_t)b * ld + d;
-            const float sv = expf(a.lv[e][oi] - umx[e]) * uinv[e];
-            // (one column: the softmax of one logit is the constant 1 and du is 0, as in latent.hip)
-            a.dlv[e][oi] = D == 1 ? 0.f : sv * (a.dlv[e][oi] - dot);
-          }
-        }
-      }
-    }
+    if (raw) raw_head_bwd(a.lv, a.dlv, E, (size_t)b * ld, D, lane, umx, uinv, udot);
   }
-  // the workgroup's partial prior-gradient row: its four waves in wave order
-#pragma unroll
-  for (int s = 0; s < POE_SLOTS; ++s) part[threadIdx.x >> 6][lane + 64 * s] = dsp[s];
-  __syncthreads();
-  if ((int)threadIdx.x < D)
-    ws[(size_t)blockIdx.x * D + threadIdx.x] =
-        part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+  prior_grad_row(dsp, part, ws, D, lane);
 }
 
-static inline bool tc_supported(int E, int D) { return E <= MMVAE_MAX_EXPERTS && D <= 64 * POE_SLOTS; }
-
-extern "C" size_t mmvae_tc_fusion_ws_floats(int B, int D) {
-  if (B <= 0 || D <= 0 || D > 64 * POE_SLOTS) return 0;
-  return (size_t)poe_blocks(B) * D;
-}
+extern "C" size_t mmvae_tc_fusion_ws_floats(int B, int D) { return fusion_ws_floats(B, D); }
 
 extern "C" int mmvae_tc_fusion_fwd(const mmvae_tc_fwd_args* a, const float* theta, const float* eps, float* joint,
                                    float* kl, float* z, int E, int B, int D, int ld_in, int raw_heads,
                                    mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(a && theta && eps && joint && kl && z && B > 0 && D > 0 && E > 0 && ld_in >= D);
-  if (!tc_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
+  if (!fusion_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
   for (int e = 0; e < E; ++e) MMVAE_CHECK_ARG(a->mu[e] && a->lv[e]);
   hipLaunchKernelGGL(tc_fwd_kernel, dim3(poe_blocks(B)), dim3(256), 0, (hipStream_t)stream, *a, theta, eps, joint, kl, z,
                      E, B, D, ld_in, raw_heads ? 1 : 0);
@@ -199,13 +164,10 @@ extern "C" int mmvae_tc_fusion_bwd(const mmvae_tc_bwd_args* a, const float* thet
                                    const float* dkl, float* dtheta, float* ws, int E, int B, int D, int ld_in,
                                    int raw_heads, int accumulate, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(a && theta && eps && ws && B > 0 && D > 0 && E > 0 && ld_in >= D);
-  if (!tc_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
+  if (!fusion_supported(E, D)) return MMVAE_ERR_UNSUPPORTED;
   for (int e = 0; e < E; ++e) MMVAE_CHECK_ARG(a->mu[e] && a->lv[e] && a->dmu[e] && a->dlv[e]);
-  const int nb = poe_blocks(B);
-  hipLaunchKernelGGL(tc_bwd_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, *a, theta, eps, dz, dkl, ws, E, B, D,
+  hipLaunchKernelGGL(tc_bwd_kernel, dim3(poe_blocks(B)), dim3(256), 0, (hipStream_t)stream, *a, theta, eps, dz, dkl, ws, E, B, D,
                      ld_in, raw_heads ? 1 : 0);
-  if (dtheta)
-    hipLaunchKernelGGL(theta_fold_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, theta, ws, dtheta, nb, D,
-                       accumulate ? 1 : 0);
+  launch_theta_fold(theta, ws, dtheta, B, D, accumulate, stream);
   return mmvae_launch_status();
 }

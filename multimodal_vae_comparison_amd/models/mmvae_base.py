@@ -10,7 +10,7 @@ import torch.nn.functional as F
 from .. import ops
 from .evaluation import EvaluationMixin
 from .nn_modules import DropoutState
-from .objectives import MultimodalObjective
+from .objectives import MultimodalObjective, recon_rowsum
 from .output_storage import VAEOutput
 
 # the decoders' first dropout-counter advance rides on the first encoder's launch (DropoutState.link;
@@ -200,14 +200,73 @@ class TorchMMVAE(EvaluationMixin, nn.Module):
         self._join(streams, device, [t for r in out for t in ((r,) if torch.is_tensor(r) else r)])
         return out
 
-    def _encode_towers(self, mods):
+    def _encode_towers(self, mods, raw_heads=False):
         """every tower's encoder on its stream, joined again -> (packed heads [mu | lv] in modality order, the towers'
-        streams (None: the current one), device)"""
+        streams (None: the current one), device, raw).  `raw_heads`: where every tower can, the heads come back as
+        [mu | raw logvar-head output] -- lv = softmax(u) + eta is then the fusion kernel's to apply, no softmax launch behind
+        the heads -- and `raw` says that they did: it is the fusion op's `raw=`"""
         dev = next(v["data"] for v in mods.values() if v["data"] is not None).device
+        encs = [v.enc for v in self.vaes.values()]
+        raw = bool(raw_heads) and dev.type == "cuda" and all(hasattr(e, "raw_heads") and e.enc_mu_logvar for e in encs)
         streams = self._tower_streams(dev)
-        packed = self._tower_phase(zip(self.vaes, streams), lambda n, st: packed_head(*self.vaes[n].enc(mods[n])), dev,
-                                   batch=mods)
-        return packed, streams, dev
+        try:
+            for e in encs if raw else []:
+                e.raw_heads = True
+            packed = self._tower_phase(zip(self.vaes, streams), lambda n, st: packed_head(*self.vaes[n].enc(mods[n])), dev,
+                                       batch=mods)
+        finally:
+            for e in encs if raw else []:
+                e.raw_heads = False
+        return packed, streams, dev, raw
+
+    @staticmethod
+    def _refuse_beyond_single_pass(name, vaes, obj_config, gaussian, one_space, bound, one_sample):
+        """the configurations no single-pass mixer (MVTCAE, MMJSD, MMVM) runs, refused in the mixer's own words"""
+        for mod, vae in vaes.items():
+            if vae.prior_str not in ("normal", "gaussian"):
+                raise NotImplementedError(f"{name}: prior '{vae.prior_str}' ({mod}): {gaussian} are Gaussian; only normal "
+                                          f"priors are on this path")
+            if vae.private_latents is not None:
+                raise NotImplementedError(f"{name}: private_latents ({mod}): the {one_space} has one shared latent space")
+        if obj_config.get("obj", "elbo") != "elbo":
+            raise NotImplementedError(f"{name}: obj '{obj_config['obj']}': the {bound} bound is built on obj elbo")
+        if int(obj_config.get("K", 1)) != 1:
+            raise NotImplementedError(f"{name}: K = {obj_config['K']}: one latent sample per {one_sample} (K = 1) only")
+
+    def _single_pass_objective(self, mods, fuse, logged, weights):
+        """The step MVTCAE, MMJSD and MMVM share: one encoder pass and one decoder pass per modality, the towers on their
+        streams, ONE fused latent kernel each way between them.  fuse(theta, packed, B, D, dev, raw) draws the step's noise
+        and calls the mixer's fusion op -> (z, kl, extra): z the one sample every modality decodes from, or a tuple with
+        modality i's at z[i]; kl the op's KL rows; extra {name: callable} further logged entries, evaluated last.
+        weights: the rows of the loss assembly over [M recon rows, the KL rows] -- the loss, "kld", then one per name in
+        `logged`."""
+        names = list(self.vaes.keys())
+        M = len(names)
+        missing = [n for n in names if mods[n]["data"] is None]
+        if missing:
+            raise ValueError(f"{self.modelName}.objective: {missing} has no data: training needs every modality "
+                             f"(evaluation with missing modalities goes through forward() / the metrics' given=)")
+        self._begin_step()
+        theta = self._pz_params[1]
+        packed, streams, dev, raw = self._encode_towers(mods, raw_heads=True)
+        z, kl, extra = fuse(theta, packed, packed[0].shape[0], self.n_latents, dev, raw)
+        zs = [z] * M if torch.is_tensor(z) else z
+
+        def decode(i, st):
+            vae = self.vaes[names[i]]
+            out, _ = vae.dec({"latents": zs[i].unsqueeze(0), "masks": mods[names[i]]["masks"]})
+            return recon_rowsum(vae.ltype, out, mods[names[i]])      # (B,)
+        recs = self._tower_phase(enumerate(streams), decode, dev, reads=[z] if torch.is_tensor(z) else list(z), batch=mods)
+        out = ops.lincomb_rows(recs + [kl], weights)
+        with torch.no_grad():      # logged only: every modality's row sum over the batch, the mixer's own entries
+            if M <= ops.H.LC_MAX_OUT:
+                ind = list(ops.lincomb_rows([r.detach() for r in recs],
+                                            [[1.0 if j == i else 0.0 for j in range(M)] for i in range(M)]))
+            else:
+                ind = [r.detach().sum() for r in recs]
+            extra = {k: f() for k, f in extra.items()}
+        return {"loss": out[0], "reconstruction_loss": ind, "kld": out[1],
+                **{k: o.detach() for k, o in zip(logged, out[2:])}, **extra}
 
     # ---- plumbing shared by the mixers ----------------------------------------------------------
     def make_output_dict(self, encoder_dist=None, decoder_dist=None, latent_samples=None, joint_dist=None,

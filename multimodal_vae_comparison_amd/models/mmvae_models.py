@@ -540,17 +540,8 @@ class MVTCAE(POE):
     prior_expert = False
 
     def __init__(self, vaes, n_latents: int, obj_config: dict, model_config=None):
-        for name, vae in vaes.items():
-            if vae.prior_str not in ("normal", "gaussian"):
-                raise NotImplementedError(f"mvtcae: prior '{vae.prior_str}' ({name}): the KL terms between the joint and "
-                                          f"the experts are Gaussian; only normal priors are on this path")
-            if vae.private_latents is not None:
-                raise NotImplementedError(f"mvtcae: private_latents ({name}): the total-correlation objective has one "
-                                          f"shared latent space")
-        if obj_config.get("obj", "elbo") != "elbo":
-            raise NotImplementedError(f"mvtcae: obj '{obj_config['obj']}': the total-correlation bound is built on obj elbo")
-        if int(obj_config.get("K", 1)) != 1:
-            raise NotImplementedError(f"mvtcae: K = {obj_config['K']}: one latent sample per step (K = 1) only")
+        self._refuse_beyond_single_pass("mvtcae", vaes, obj_config, "the KL terms between the joint and the experts",
+                                        "total-correlation objective", "total-correlation", "step")
         alpha = float((model_config or {}).get("alpha", 5.0 / 6.0))
         if not 0.0 <= alpha <= 1.0:
             raise ValueError(f"mvtcae: model_cfg alpha = {alpha} must lie in [0, 1]")
@@ -569,43 +560,10 @@ class MVTCAE(POE):
 
     def objective(self, mods):
         """one encoder pass and one decoder pass per modality (POE: 2^(M-1) and 2^M - 1), the towers on their streams"""
-        names = list(self.vaes.keys())
-        M = len(names)
-        missing = [n for n in names if mods[n]["data"] is None]
-        if missing:
-            raise ValueError(f"mvtcae.objective: {missing} has no data: training needs every modality (evaluation with "
-                             f"missing modalities goes through forward() / the metrics' given=)")
-        self._begin_step()
-        theta = self._pz_params[1]
-        dev = mods[names[0]]["data"].device
-        encs = [v.enc for v in self.vaes.values()]
-        # lv = softmax(u) + eta is applied by the fusion kernel (as POE.objective does): no softmax launch behind the heads
-        raw_heads = dev.type == "cuda" and all(hasattr(e, "raw_heads") and e.enc_mu_logvar for e in encs)
-        try:
-            for e in encs if raw_heads else []:
-                e.raw_heads = True
-            packed, streams, dev = self._encode_towers(mods)
-        finally:
-            for e in encs if raw_heads else []:
-                e.raw_heads = False
-        B, D = packed[0].shape[0], self.n_latents
-        eps = self._draw(B, D, dev)
-        _, kl, z = ops.tc_fusion(theta, packed, eps, theta.grad, raw=raw_heads)
-
-        def decode(n, st):
-            vae = self.vaes[n]
-            out, _ = vae.dec({"latents": z.unsqueeze(0), "masks": mods[n]["masks"]})
-            return recon_rowsum(vae.ltype, out, mods[n])      # (B,)
-        recs = self._tower_phase(zip(names, streams), decode, dev, reads=[z], batch=mods)
-        out = ops.lincomb_rows(recs + [kl], self._tc_weights())
-        with torch.no_grad():      # logged only: every modality's row sum over the batch
-            if M <= ops.H.LC_MAX_OUT:
-                ind = list(ops.lincomb_rows([r.detach() for r in recs],
-                                            [[1.0 if j == i else 0.0 for j in range(M)] for i in range(M)]))
-            else:
-                ind = [r.detach().sum() for r in recs]
-        return {"loss": out[0], "reconstruction_loss": ind, "kld": out[1], "kld_prior": out[2].detach(),
-                "kld_cond": out[3].detach()}
+        def fuse(theta, packed, B, D, dev, raw):
+            _, kl, z = ops.tc_fusion(theta, packed, self._draw(B, D, dev), theta.grad, raw=raw)
+            return z, kl, {}
+        return self._single_pass_objective(mods, fuse, ("kld_prior", "kld_cond"), self._tc_weights())
 
 
 class MOE(TorchMMVAE):
@@ -662,7 +620,7 @@ class MOE(TorchMMVAE):
         # extracted-mask parity test splits them by pass).  optimal_sigma fits ONE sigma per call: its passes stay apart.
         # The shipped config_cdspritesplus.yml step is a chain of ~260 launches, ~115 of them the text decoder's two
         # op-by-op passes: 4.00 -> 3.4 ms/step.
-        packed, streams, dev = self._encode_towers(data)
+        packed, streams, dev, _ = self._encode_towers(data)
         B, D = packed[0].shape[0], self.n_latents
         zs, kls = [], []
         for i in range(M):
@@ -711,7 +669,7 @@ class MOE(TorchMMVAE):
         self._begin_step()
         names = list(self.vaes.keys())
         M, K, D = len(names), int(self.K), self.n_latents
-        packed, streams, dev = self._encode_towers(data)
+        packed, streams, dev, _ = self._encode_towers(data)
         B = packed[0].shape[0]
         eps = [self._draw_k(m, K, B, D, dev) for m in range(M)]
         theta = self._pz_params[1]
@@ -817,17 +775,8 @@ class MMJSD(MOE):
     posteriors, the dynamic prior is a training-time regulariser only."""
 
     def __init__(self, vaes, n_latents: int, obj_config: dict, model_config=None):
-        for name, vae in vaes.items():
-            if vae.prior_str not in ("normal", "gaussian"):
-                raise NotImplementedError(f"mmjsd: prior '{vae.prior_str}' ({name}): the geometric mean and the KL terms to "
-                                          f"it are Gaussian; only normal priors are on this path")
-            if vae.private_latents is not None:
-                raise NotImplementedError(f"mmjsd: private_latents ({name}): the Jensen-Shannon objective has one shared "
-                                          f"latent space")
-        if obj_config.get("obj", "elbo") != "elbo":
-            raise NotImplementedError(f"mmjsd: obj '{obj_config['obj']}': the Jensen-Shannon bound is built on obj elbo")
-        if int(obj_config.get("K", 1)) != 1:
-            raise NotImplementedError(f"mmjsd: K = {obj_config['K']}: one latent sample per step (K = 1) only")
+        self._refuse_beyond_single_pass("mmjsd", vaes, obj_config, "the geometric mean and the KL terms to it",
+                                        "Jensen-Shannon objective", "Jensen-Shannon", "step")
         M = len(vaes)
         w = float((model_config or {}).get("prior_weight", 1.0 / (M + 1)))
         if not 0.0 < w < 1.0:
@@ -861,43 +810,11 @@ class MMJSD(MOE):
 
     def objective(self, mods):
         """one encoder pass and one decoder pass per modality (MOE's elbo: one and two), the towers on their streams"""
-        names = list(self.vaes.keys())
-        M = len(names)
-        missing = [n for n in names if mods[n]["data"] is None]
-        if missing:
-            raise ValueError(f"mmjsd.objective: {missing} has no data: training needs every modality (evaluation with "
-                             f"missing modalities goes through forward() / the metrics' given=)")
-        self._begin_step()
-        theta = self._pz_params[1]
-        dev = mods[names[0]]["data"].device
-        encs = [v.enc for v in self.vaes.values()]
-        # lv = softmax(u) + eta is applied by the fusion kernel (as MVTCAE.objective does): no softmax launch behind the heads
-        raw_heads = dev.type == "cuda" and all(hasattr(e, "raw_heads") and e.enc_mu_logvar for e in encs)
-        try:
-            for e in encs if raw_heads else []:
-                e.raw_heads = True
-            packed, streams, dev = self._encode_towers(mods)
-        finally:
-            for e in encs if raw_heads else []:
-                e.raw_heads = False
-        B, D = packed[0].shape[0], self.n_latents
-        eps = self._draw(B, D, dev)
-        _, kl, z = ops.js_fusion(theta, packed, eps, self._selection(B, dev), self._js_pi(), theta.grad, raw=raw_heads)
-
-        def decode(n, st):
-            vae = self.vaes[n]
-            out, _ = vae.dec({"latents": z.unsqueeze(0), "masks": mods[n]["masks"]})
-            return recon_rowsum(vae.ltype, out, mods[n])      # (B,)
-        recs = self._tower_phase(zip(names, streams), decode, dev, reads=[z], batch=mods)
-        out = ops.lincomb_rows(recs + [kl], self._js_weights())
-        with torch.no_grad():      # logged only: every modality's row sum over the batch
-            if M <= ops.H.LC_MAX_OUT:
-                ind = list(ops.lincomb_rows([r.detach() for r in recs],
-                                            [[1.0 if j == i else 0.0 for j in range(M)] for i in range(M)]))
-            else:
-                ind = [r.detach().sum() for r in recs]
-        return {"loss": out[0], "reconstruction_loss": ind, "kld": out[1], "kld_prior": out[2].detach(),
-                "kld_experts": out[3].detach()}
+        def fuse(theta, packed, B, D, dev, raw):
+            _, kl, z = ops.js_fusion(theta, packed, self._draw(B, D, dev), self._selection(B, dev), self._js_pi(), theta.grad,
+                                     raw=raw)
+            return z, kl, {}
+        return self._single_pass_objective(mods, fuse, ("kld_prior", "kld_experts"), self._js_weights())
 
 
 class MMVM(MOE):
@@ -917,17 +834,8 @@ class MMVM(MOE):
     (fit_latent_density / sample_latent_density, handed to the metrics as eps= / joint_eps=)."""
 
     def __init__(self, vaes, n_latents: int, obj_config: dict, model_config=None):
-        for name, vae in vaes.items():
-            if vae.prior_str not in ("normal", "gaussian"):
-                raise NotImplementedError(f"mmvm: prior '{vae.prior_str}' ({name}): the mixture prior's densities and the KL "
-                                          f"terms are Gaussian; only normal priors are on this path")
-            if vae.private_latents is not None:
-                raise NotImplementedError(f"mmvm: private_latents ({name}): the mixture-of-experts prior has one shared "
-                                          f"latent space")
-        if obj_config.get("obj", "elbo") != "elbo":
-            raise NotImplementedError(f"mmvm: obj '{obj_config['obj']}': the mixture-prior bound is built on obj elbo")
-        if int(obj_config.get("K", 1)) != 1:
-            raise NotImplementedError(f"mmvm: K = {obj_config['K']}: one latent sample per modality and step (K = 1) only")
+        self._refuse_beyond_single_pass("mmvm", vaes, obj_config, "the mixture prior's densities and the KL terms",
+                                        "mixture-of-experts prior", "mixture-prior", "modality and step")
         alpha = float((model_config or {}).get("alpha", 1.0))
         if not 0.0 <= alpha <= 1.0:
             raise ValueError(f"mmvm: model_cfg alpha = {alpha} must lie in [0, 1]")
@@ -946,48 +854,16 @@ class MMVM(MOE):
 
     def objective(self, mods):
         """one encoder pass and one decoder pass per modality (MOE's elbo: one and two), the towers on their streams"""
-        names = list(self.vaes.keys())
-        M = len(names)
-        missing = [n for n in names if mods[n]["data"] is None]
-        if missing:
-            raise ValueError(f"mmvm.objective: {missing} has no data: training needs every modality (evaluation with "
-                             f"missing modalities goes through forward() / the metrics' given=)")
-        self._begin_step()
-        theta = self._pz_params[1]
-        dev = mods[names[0]]["data"].device
-        encs = [v.enc for v in self.vaes.values()]
-        # lv = softmax(u) + eta is applied by the fusion kernel (as MMJSD.objective does): no softmax launch behind the heads
-        raw_heads = dev.type == "cuda" and all(hasattr(e, "raw_heads") and e.enc_mu_logvar for e in encs)
-        try:
-            for e in encs if raw_heads else []:
-                e.raw_heads = True
-            packed, streams, dev = self._encode_towers(mods)
-        finally:
-            for e in encs if raw_heads else []:
-                e.raw_heads = False
-        B, D = packed[0].shape[0], self.n_latents
-        if self.eps_override is not None:      # M recorded draws, in modality order
-            eps = torch.stack([self._draw(B, D, dev) for _ in range(M)])
-        else:
-            eps = ops.randn((M, B, D), self._noise_state())
-        zs, kl, resp = ops.mixprior_fusion(theta, packed, eps, theta.grad, raw=raw_heads)
-
-        def decode(i, st):
-            vae = self.vaes[names[i]]
-            out, _ = vae.dec({"latents": zs[i].unsqueeze(0), "masks": mods[names[i]]["masks"]})
-            return recon_rowsum(vae.ltype, out, mods[names[i]])      # (B,)
-        recs = self._tower_phase(enumerate(streams), decode, dev, reads=list(zs), batch=mods)
-        out = ops.lincomb_rows(recs + [kl], self._mm_weights())
-        with torch.no_grad():      # logged only: every modality's row sum over the batch, the mean own-responsibility
-            if M <= ops.H.LC_MAX_OUT:
-                ind = list(ops.lincomb_rows([r.detach() for r in recs],
-                                            [[1.0 if j == i else 0.0 for j in range(M)] for i in range(M)]))
+        def fuse(theta, packed, B, D, dev, raw):
+            M = len(packed)
+            if self.eps_override is not None:      # M recorded draws, in modality order
+                eps = torch.stack([self._draw(B, D, dev) for _ in range(M)])
             else:
-                ind = [r.detach().sum() for r in recs]
+                eps = ops.randn((M, B, D), self._noise_state())
+            zs, kl, resp = ops.mixprior_fusion(theta, packed, eps, theta.grad, raw=raw)
             # 1 / M: the posteriors are indistinguishable; 1: they are disjoint and the regulariser's gradient has vanished
-            resp_self = resp.diagonal(dim1=0, dim2=1).mean()
-        return {"loss": out[0], "reconstruction_loss": ind, "kld": out[1], "kld_mix": out[2].detach(),
-                "kld_std": out[3].detach(), "resp_self": resp_self}
+            return zs, kl, {"resp_self": lambda: resp.diagonal(dim1=0, dim2=1).mean()}
+        return self._single_pass_objective(mods, fuse, ("kld_mix", "kld_std"), self._mm_weights())
 
 
 class DMVAE(TorchMMVAE):
@@ -1021,7 +897,7 @@ class DMVAE(TorchMMVAE):
         # modality) -- as ONE call over (2 + (M - 1)) B latent samples (the row-sum kernels pair output row k with target
         # row k % B; a decoder with dropout draws its masks once for all passes; optimal_sigma fits one sigma per call:
         # its passes stay apart).  BASELINE configs[3]: 1.54 -> 1.2 ms/step.
-        packed, streams, dev = self._encode_towers(mods)
+        packed, streams, dev, _ = self._encode_towers(mods)
         B = packed[0].shape[0]
         P = [self.vaes[n].private_latents for n in names]
         # noise in the reference's draw order (mmvae_models.py:486-502)

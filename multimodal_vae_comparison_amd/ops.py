@@ -1375,18 +1375,62 @@ class PoeReparamKL(Function):
         for i in range(n_z if dz is not None else 0):
             a.eps[i] = eps[i].data_ptr()
             a.dz[i] = dz[i].data_ptr()
-        if gtheta is not None:
-            dth, acc, ret = gtheta, 1, None
-            GradReducer.writes(dev, gtheta)
-        else:
-            dth = ret = torch.empty_like(theta)
-            acc = 0
+        dth, acc, ret = _theta_grad_dest(theta, gtheta, True)      # (a fresh tensor whether autograd wants it or not)
         ws = H.workspace(H.lib().mmvae_poe_ws_floats(B, D), dev)
         H.call("mmvae_poe_reparam_kl_bwd_acc", ctypes.byref(a), H.ptr(theta), H.ptr(dkl), H.ptr(dth), H.ptr(ws),
                _poe_ticket(dev), E,
                int(with_prior), n_z if dz is not None else 0, kl_mask, B, D, 2 * Dtot, raw, acc, acc_packed, H.stream())
         return (ret, None, None, None, None, None, None, None, None, *(dpacked if ret_packed is None else ret_packed),
                 *([None] * ctx.n_eps_in))
+
+
+# ---- plumbing under the three single-pass fusions (TcFusion, JsFusion, MixPriorFusion) --------------------------------
+def _fusion_inputs(theta, eps, packed, eps_per_expert=False):
+    """float32 contiguous inputs and their shared shape checks: E heads (B, 2 D) = [mu_e | lv_e], theta of D numbers, eps
+    (B,D) or, `eps_per_expert`, (E,B,D) -> (packed, theta, eps, E, B, D, device)"""
+    packed = [H.f32c(t) for t in packed]
+    theta, eps = H.f32c(theta), H.f32c(eps)
+    E = len(packed)
+    B, D2 = packed[0].shape
+    D = D2 // 2
+    assert all(p.shape == (B, D2) for p in packed) and theta.numel() == D
+    assert eps.shape == ((E, B, D) if eps_per_expert else (B, D))
+    return packed, theta, eps, E, B, D, packed[0].device
+
+
+def _head_tables(a, packed, D, dpacked=None):
+    """the pointer table `a`: mu / lv of every head and, backward, dmu / dlv of its gradient tensor -> a.  (No more than
+    the table holds: a longer list reaches the kernel's entry as its E, which refuses it.)"""
+    for e, p in enumerate(packed[:H.MAX_EXPERTS]):
+        a.mu[e] = p.data_ptr()
+        a.lv[e] = p.data_ptr() + 4 * D
+        if dpacked is not None:
+            a.dmu[e] = dpacked[e].data_ptr()
+            a.dlv[e] = dpacked[e].data_ptr() + 4 * D
+    return a
+
+
+def _upstream(g):
+    """an upstream gradient for a kernel: an absent one goes in as NULL and the kernel takes it as zeros"""
+    return H.f32c(g) if g is not None else None
+
+
+def _theta_grad_dest(theta, gtheta, wanted):
+    """where a fusion's backward pass leaves the prior parameter's gradient -> (dth, acc, ret): added to the preset view
+    `gtheta`; else written to a fresh tensor that goes back to autograd; else, not `wanted`, nowhere (dth None: the fold
+    is not launched)"""
+    if gtheta is not None:
+        GradReducer.writes(theta.device, gtheta)
+        return gtheta, 1, None
+    if not wanted:
+        return None, 0, None
+    ret = torch.empty_like(theta)
+    return ret, 0, ret
+
+
+def _fusion_ws(ws_floats, B, D, dev):
+    """the backward kernel's partial prior-gradient rows; ws_floats: the name of the op's mmvae_*_ws_floats"""
+    return H.workspace(getattr(H.lib(), ws_floats)(B, D), dev)
 
 
 class TcFusion(Function):
@@ -1396,22 +1440,13 @@ class TcFusion(Function):
 
     @staticmethod
     def forward(ctx, theta, gtheta, raw, eps, *packed):
-        packed = [H.f32c(t) for t in packed]
-        theta, eps = H.f32c(theta), H.f32c(eps)
-        E = len(packed)
-        B, D2 = packed[0].shape
-        D = D2 // 2
-        assert all(p.shape == (B, D2) for p in packed) and eps.shape == (B, D) and theta.numel() == D
-        dev = packed[0].device
+        packed, theta, eps, E, B, D, dev = _fusion_inputs(theta, eps, packed)
         joint = torch.empty(2, B, D, device=dev)
         kl = torch.empty(E + 1, B, device=dev)
         z = torch.empty(B, D, device=dev)
-        a = H.TcFwdArgs()
-        for e, p in enumerate(packed[:H.MAX_EXPERTS]):
-            a.mu[e] = p.data_ptr()
-            a.lv[e] = p.data_ptr() + 4 * D
+        a = _head_tables(H.TcFwdArgs(), packed, D)
         H.call("mmvae_tc_fusion_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(joint), H.ptr(kl), H.ptr(z), E, B, D,
-               D2, int(bool(raw)), H.stream())
+               2 * D, int(bool(raw)), H.stream())
         ctx.save_for_backward(theta, eps, *packed)
         ctx.cfg = (gtheta, E, B, D, int(bool(raw)))
         ctx.mark_non_differentiable(joint)
@@ -1421,28 +1456,12 @@ class TcFusion(Function):
     @staticmethod
     def backward(ctx, _dj, dkl, dz):
         gtheta, E, B, D, raw = ctx.cfg
-        theta, eps = ctx.saved_tensors[:2]
-        packed = ctx.saved_tensors[2:]
-        dev = theta.device
-        # (an absent upstream gradient goes in as NULL: the kernel takes it as zeros)
-        dkl = H.f32c(dkl) if dkl is not None else None
-        dz = H.f32c(dz) if dz is not None else None
+        theta, eps, *packed = ctx.saved_tensors
         dpacked = [torch.empty_like(p) for p in packed]
-        a = H.TcBwdArgs()
-        for e, p in enumerate(packed):
-            a.mu[e] = p.data_ptr()
-            a.lv[e] = p.data_ptr() + 4 * D
-            a.dmu[e] = dpacked[e].data_ptr()
-            a.dlv[e] = dpacked[e].data_ptr() + 4 * D
-        if gtheta is not None:
-            dth, acc, ret = gtheta, 1, None
-            GradReducer.writes(dev, gtheta)
-        elif ctx.needs_input_grad[0]:
-            dth = ret = torch.empty_like(theta)
-            acc = 0
-        else:
-            dth, acc, ret = None, 0, None
-        ws = H.workspace(H.lib().mmvae_tc_fusion_ws_floats(B, D), dev)
+        a = _head_tables(H.TcBwdArgs(), packed, D, dpacked)
+        dth, acc, ret = _theta_grad_dest(theta, gtheta, ctx.needs_input_grad[0])
+        ws = _fusion_ws("mmvae_tc_fusion_ws_floats", B, D, theta.device)
+        dz, dkl = _upstream(dz), _upstream(dkl)
         H.call("mmvae_tc_fusion_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps), H.ptr(dz), H.ptr(dkl), H.ptr(dth),
                H.ptr(ws), E, B, D, 2 * D, raw, acc, H.stream())
         return (ret, None, None, None, *dpacked)
@@ -1462,24 +1481,15 @@ class JsFusion(Function):
 
     @staticmethod
     def forward(ctx, theta, gtheta, raw, weights, sel, eps, *packed):
-        packed = [H.f32c(t) for t in packed]
-        theta, eps = H.f32c(theta), H.f32c(eps)
-        E = len(packed)
-        B, D2 = packed[0].shape
-        D = D2 // 2
-        assert all(p.shape == (B, D2) for p in packed) and eps.shape == (B, D) and theta.numel() == D
+        packed, theta, eps, E, B, D, dev = _fusion_inputs(theta, eps, packed)
         assert sel.dtype == torch.int32 and sel.shape == (B,) and sel.is_contiguous() and len(weights) == E + 1
-        dev = packed[0].device
         prior = torch.empty(2, B, D, device=dev)
         kl = torch.empty(E + 1, B, device=dev)
         z = torch.empty(B, D, device=dev)
-        a = H.TcFwdArgs()
-        for e, p in enumerate(packed[:H.MAX_EXPERTS]):
-            a.mu[e] = p.data_ptr()
-            a.lv[e] = p.data_ptr() + 4 * D
+        a = _head_tables(H.TcFwdArgs(), packed, D)
         w = (H.c_f * (E + 1))(*weights)
         H.call("mmvae_js_fusion_fwd", ctypes.byref(a), w, H.ptr(theta), H.ptr(eps), H.ptr(sel), H.ptr(prior), H.ptr(kl),
-               H.ptr(z), E, B, D, D2, int(bool(raw)), H.stream())
+               H.ptr(z), E, B, D, 2 * D, int(bool(raw)), H.stream())
         ctx.save_for_backward(theta, eps, sel, *packed)
         ctx.cfg = (gtheta, E, B, D, int(bool(raw)), w)
         ctx.mark_non_differentiable(prior)
@@ -1489,28 +1499,12 @@ class JsFusion(Function):
     @staticmethod
     def backward(ctx, _dp, dkl, dz):
         gtheta, E, B, D, raw, w = ctx.cfg
-        theta, eps, sel = ctx.saved_tensors[:3]
-        packed = ctx.saved_tensors[3:]
-        dev = theta.device
-        # (an absent upstream gradient goes in as NULL: the kernel takes it as zeros)
-        dkl = H.f32c(dkl) if dkl is not None else None
-        dz = H.f32c(dz) if dz is not None else None
+        theta, eps, sel, *packed = ctx.saved_tensors
         dpacked = [torch.empty_like(p) for p in packed]
-        a = H.TcBwdArgs()
-        for e, p in enumerate(packed):
-            a.mu[e] = p.data_ptr()
-            a.lv[e] = p.data_ptr() + 4 * D
-            a.dmu[e] = dpacked[e].data_ptr()
-            a.dlv[e] = dpacked[e].data_ptr() + 4 * D
-        if gtheta is not None:
-            dth, acc, ret = gtheta, 1, None
-            GradReducer.writes(dev, gtheta)
-        elif ctx.needs_input_grad[0]:
-            dth = ret = torch.empty_like(theta)
-            acc = 0
-        else:
-            dth, acc, ret = None, 0, None
-        ws = H.workspace(H.lib().mmvae_js_fusion_ws_floats(B, D), dev)
+        a = _head_tables(H.TcBwdArgs(), packed, D, dpacked)
+        dth, acc, ret = _theta_grad_dest(theta, gtheta, ctx.needs_input_grad[0])
+        ws = _fusion_ws("mmvae_js_fusion_ws_floats", B, D, theta.device)
+        dz, dkl = _upstream(dz), _upstream(dkl)
         H.call("mmvae_js_fusion_bwd", ctypes.byref(a), w, H.ptr(theta), H.ptr(eps), H.ptr(sel), H.ptr(dz), H.ptr(dkl),
                H.ptr(dth), H.ptr(ws), E, B, D, 2 * D, raw, acc, H.stream())
         return (ret, None, None, None, None, None, *dpacked)
@@ -1546,23 +1540,15 @@ class MixPriorFusion(Function):
 
     @staticmethod
     def forward(ctx, theta, gtheta, raw, eps, *packed):
-        packed = [H.f32c(t) for t in packed]
-        theta, eps = H.f32c(theta), H.f32c(eps)
-        E = len(packed)
-        B, D2 = packed[0].shape
-        D = D2 // 2
-        assert all(p.shape == (B, D2) for p in packed) and eps.shape == (E, B, D) and theta.numel() == D
-        dev = packed[0].device
+        packed, theta, eps, E, B, D, dev = _fusion_inputs(theta, eps, packed, eps_per_expert=True)
         kl = torch.empty(2 * E, B, device=dev)
         resp = torch.empty(E, E, B, device=dev)
         zs = [torch.empty(B, D, device=dev) for _ in range(E)]
-        a = H.PoeFwdArgs()
-        for e, p in enumerate(packed[:H.MAX_EXPERTS]):
-            a.mu[e] = p.data_ptr()
-            a.lv[e] = p.data_ptr() + 4 * D
+        a = _head_tables(H.PoeFwdArgs(), packed, D)
+        for e in range(min(E, H.MAX_EXPERTS)):
             a.eps[e] = eps.data_ptr() + 4 * e * B * D
             a.z[e] = zs[e].data_ptr()
-        H.call("mmvae_mixprior_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(kl), H.ptr(resp), E, B, D, D2, int(bool(raw)),
+        H.call("mmvae_mixprior_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(kl), H.ptr(resp), E, B, D, 2 * D, int(bool(raw)),
                H.stream())
         ctx.save_for_backward(theta, eps, resp, *packed)
         ctx.cfg = (gtheta, E, B, D, int(bool(raw)))
@@ -1573,30 +1559,15 @@ class MixPriorFusion(Function):
     @staticmethod
     def backward(ctx, dkl, _dresp, *dzs):
         gtheta, E, B, D, raw = ctx.cfg
-        theta, eps, resp = ctx.saved_tensors[:3]
-        packed = ctx.saved_tensors[3:]
-        dev = theta.device
-        # (an absent upstream gradient goes in as NULL: the kernel takes it as zeros)
-        dkl = H.f32c(dkl) if dkl is not None else None
-        dzs = [H.f32c(g) if g is not None else None for g in dzs]
+        theta, eps, resp, *packed = ctx.saved_tensors
         dpacked = [torch.empty_like(p) for p in packed]
-        a = H.PoeBwdArgs()
-        for e, p in enumerate(packed):
-            a.mu[e] = p.data_ptr()
-            a.lv[e] = p.data_ptr() + 4 * D
+        a = _head_tables(H.PoeBwdArgs(), packed, D, dpacked)
+        dkl, dzs = _upstream(dkl), [_upstream(g) for g in dzs]
+        for e in range(E):
             a.eps[e] = eps.data_ptr() + 4 * e * B * D
             a.dz[e] = H.ptr(dzs[e])
-            a.dmu[e] = dpacked[e].data_ptr()
-            a.dlv[e] = dpacked[e].data_ptr() + 4 * D
-        if gtheta is not None:
-            dth, acc, ret = gtheta, 1, None
-            GradReducer.writes(dev, gtheta)
-        elif ctx.needs_input_grad[0]:
-            dth = ret = torch.empty_like(theta)
-            acc = 0
-        else:
-            dth, acc, ret = None, 0, None
-        ws = H.workspace(H.lib().mmvae_mixprior_ws_floats(B, D), dev)
+        dth, acc, ret = _theta_grad_dest(theta, gtheta, ctx.needs_input_grad[0])
+        ws = _fusion_ws("mmvae_mixprior_ws_floats", B, D, theta.device)
         H.call("mmvae_mixprior_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(resp), H.ptr(dkl), H.ptr(dth), H.ptr(ws), E, B, D,
                2 * D, raw, acc, H.stream())
         return (ret, None, None, None, *dpacked)

@@ -113,7 +113,9 @@ FAR_CASES = _pids([Case(3, 32, B0, far=True), Case(3, 70, B0, raw=True, far=True
 TINY_CASES = _pids([Case(2, 32, B0, scale=TINY), Case(8, 256, 7, scale=TINY)])
 # one case per width class for the tests of the plumbing around the kernels
 FAMILY_CASES = [Case(3, 32, B0), Case(3, 70, B0, raw=True)]
-THETA_CASES = _pids([Case(2, D, B, raw=raw) for D, raw in ((32, True), (70, False)) for B in (5, 1100)])
+# (116 and 129 rows leave 29 and 33 partial rows: the first counts at which one wave of the fold enters its 8-way unrolled
+# loop and another does not)
+THETA_CASES = _pids([Case(2, D, B, raw=raw) for D, raw in ((32, True), (70, False)) for B in (5, 116, 129, 1100)])
 
 
 def spread(D):

@@ -95,7 +95,7 @@ def test_case_tables_cover_what_the_gpu_suite_claims():
     assert {c.B for c in R.ROW_CASES} == {1, 5, 1100}
     assert all(c.spike and c.raw for c in R.SPIKE_CASES) and {c.D <= 64 for c in R.SPIKE_CASES} == {True, False}
     assert all(c.theta0 for c in R.THETA0_CASES) and not any(c.theta0 for c in R.WIDTH_CASES)
-    assert {c.B for c in R.THETA_CASES} == {5, 1100} and all(c.E == 1 for c in R.SINGLE_CASES)
+    assert {c.B for c in R.THETA_CASES} == {5, 116, 129, 1100} and all(c.E == 1 for c in R.SINGLE_CASES)
     # the launch geometry: one wave per row up to MAX_WAVES waves in workgroups of four, then rows wave, wave + MAX_WAVES, ...
     # -- 1100 rows give a wave its second and its third row; the workspace is one row per workgroup
     from multimodal_vae_comparison_amd import hipops
