@@ -444,6 +444,49 @@ int mmvae_mixprior_bwd(const mmvae_poe_bwd_args* a, const float* theta, const fl
                        mmvae_stream_t stream);
 size_t mmvae_mixprior_ws_floats(int B, int D);
 
+/* ------------------------------------------------------------------------------------------------
+ * MMVAE+ latent op, K = 1 (Palumbo, Daunhawer, Vogt, ICLR 2023): shared and private latents of E modalities in one launch
+ * each way (csrc/mmplus.hip).  Head e holds W = D + P columns per half: mu[e] / lv[e] point at (B, W) blocks whose rows are
+ * ld_in floats apart (packed heads [mu | lv]: ld_in = 2 W); columns [0, D) are the SHARED posterior q_e^u, [D, W) the
+ * PRIVATE one q_e^w, both N(mu, sigma = lv): the head is read as the SCALE.  raw_heads: lv = softmax(u, -1) + 1e-6 over
+ * all W columns, applied here both ways (dlv[e] receives d/du; the softmax couples shared and private columns).  Priors:
+ * p(u) = N(0, sp), sp = softmax(theta) D over the D shared columns; p(w) = N(0, 1).  eps_u (E,B,D), eps_w (E,B,P) and
+ * eps_a (E,E,B,P), indexed [decoder n][source m] (the diagonal is never read; E = 1: may be NULL), are standard-normal
+ * draws; aux_scale = s is the scale of the auxiliary cross prior r(w) = N(0, s^2): finite and > 0, or MMVAE_ERR_ARG.
+ * With u_m = mu_m^u + sigma_m^u eps_u[m], w_m = mu_m^w + sigma_m^w eps_w[m]:
+ *   z[n] (E B, W) : decoder n's whole input batch: row m B + b = [u_m[b] | w_m[b]] if n == m, else [u_m[b] | s eps_a[n][m][b]]
+ *   kl (3E,B)     : row m      : log q_m^u(u_m) - log (1/E) sum_j q_j^u(u_m), in mmvae_mixprior_fwd's difference arithmetic
+ *                   row E + m  : sum_d KL(q_m^u || N(0, sp))
+ *                   row 2E + m : sum_p KL(q_m^w || N(0, 1))
+ *   resp (E,E,B)  : resp[m][j] = the weight of q_j^u in the mixture density at u_m           (not differentiable)
+ * bwd: dz[n] (E B, W) each, dkl (3E,B), resp as the forward pass wrote it -> dmu[e], dlv[e] over all W columns, dtheta (D)
+ *   as mmvae_tc_fusion_bwd (ws: mmvae_mmplus_ws_floats(B, D, P) floats, accumulate, dtheta NULL).  The gradient of u_m is
+ *   the sum over n = 0 .. E-1 of columns [0, D) of row block m of dz[n]; that of w_m is columns [D, W) of row block m of
+ *   dz[m] alone.  dkl NULL and every dz[n] NULL on its own: an absent upstream gradient, taken as zeros.  Nothing is
+ *   detached.  Every sum in one fixed order, no atomics: bit-reproducible from run to run.
+ * 1 <= E <= MMVAE_MAX_EXPERTS, D >= 1, P >= 1 and D + P <= 256; anything else returns MMVAE_ERR_UNSUPPORTED and writes
+ * nothing (mmvae_mmplus_ws_floats: 0).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+  const float* mu[MMVAE_MAX_EXPERTS];
+  const float* lv[MMVAE_MAX_EXPERTS];
+  float* z[MMVAE_MAX_EXPERTS];
+} mmvae_mmplus_fwd_args;
+typedef struct {
+  const float* mu[MMVAE_MAX_EXPERTS];
+  const float* lv[MMVAE_MAX_EXPERTS];
+  const float* dz[MMVAE_MAX_EXPERTS];
+  float* dmu[MMVAE_MAX_EXPERTS];
+  float* dlv[MMVAE_MAX_EXPERTS];
+} mmvae_mmplus_bwd_args;
+int mmvae_mmplus_fwd(const mmvae_mmplus_fwd_args* a, const float* theta, const float* eps_u, const float* eps_w,
+                     const float* eps_a, float aux_scale, float* kl, float* resp, int E, int B, int D, int P, int ld_in,
+                     int raw_heads, mmvae_stream_t stream);
+int mmvae_mmplus_bwd(const mmvae_mmplus_bwd_args* a, const float* theta, const float* eps_u, const float* eps_w,
+                     const float* resp, const float* dkl, float* dtheta, float* ws, int E, int B, int D, int P, int ld_in,
+                     int raw_heads, int accumulate, mmvae_stream_t stream);
+size_t mmvae_mmplus_ws_floats(int B, int D, int P);
+
 /* Latent samples -> decoder inputs, and the transpose (round 6).  The reference decodes every subset's sample in a call of its
  * own (POE.objective, models/mmvae_models.py:159-187) and builds DMVAE's decoder inputs with torch.cat([z_shared, z_private], -1)
  * per pass (:494-502); here a decoder's passes are one batch, and the batches of ALL decoders are written by one launch:

@@ -1,6 +1,7 @@
 // The frame shared by the fused latent ops (latent.hip: product of experts; tcfusion.hip: total-correlation fusion;
-// jsfusion.hip: Jensen-Shannon fusion; mixprior.hip: mixture-of-experts prior): one wavefront per sample, lanes over the
-// latent dimension in POE_SLOTS column slots of 64.  Around each op's own arithmetic: the prior scale, the raw heads
+// jsfusion.hip: Jensen-Shannon fusion; mixprior.hip: mixture-of-experts prior; mmplus.hip: MMVAE+'s split latents): one
+// wavefront per sample, lanes over the latent dimension in POE_SLOTS column slots of 64.  Around each op's own arithmetic:
+// the prior scale, the raw heads
 // (lv = softmax(u) + 1e-6 applied by the kernels, both ways), the workgroup's partial prior-gradient row, the fold of these
 // rows into dtheta, and the host side's support rule, workspace size and fold launch.  The pointer tables come in as
 // arrays of MMVAE_MAX_EXPERTS pointers: mmvae_tc_*_args and mmvae_poe_*_args both fit.

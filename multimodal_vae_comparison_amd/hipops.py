@@ -50,6 +50,15 @@ class TcBwdArgs(ctypes.Structure):
                 ("dlv", c_p * MAX_EXPERTS)]
 
 
+class MmPlusFwdArgs(ctypes.Structure):      # mmvae_mmplus_fwd_args
+    _fields_ = [("mu", c_p * MAX_EXPERTS), ("lv", c_p * MAX_EXPERTS), ("z", c_p * MAX_EXPERTS)]
+
+
+class MmPlusBwdArgs(ctypes.Structure):      # mmvae_mmplus_bwd_args
+    _fields_ = [("mu", c_p * MAX_EXPERTS), ("lv", c_p * MAX_EXPERTS), ("dz", c_p * MAX_EXPERTS),
+                ("dmu", c_p * MAX_EXPERTS), ("dlv", c_p * MAX_EXPERTS)]
+
+
 FAN_MAX_BLOCKS, FAN_MAX_SRC, FAN_MAX_USES = 16, 8, 4
 
 
@@ -209,6 +218,9 @@ SIGNATURES = {
     "mmvae_mixprior_fwd": (c_i, [ctypes.POINTER(PoeFwdArgs)] + [c_p] * 3 + [c_i] * 5 + [c_p]),
     "mmvae_mixprior_bwd": (c_i, [ctypes.POINTER(PoeBwdArgs)] + [c_p] * 5 + [c_i] * 6 + [c_p]),
     "mmvae_mixprior_ws_floats": (c_sz, [c_i, c_i]),
+    "mmvae_mmplus_fwd": (c_i, [ctypes.POINTER(MmPlusFwdArgs)] + [c_p] * 4 + [c_f] + [c_p] * 2 + [c_i] * 6 + [c_p]),
+    "mmvae_mmplus_bwd": (c_i, [ctypes.POINTER(MmPlusBwdArgs)] + [c_p] * 7 + [c_i] * 7 + [c_p]),
+    "mmvae_mmplus_ws_floats": (c_sz, [c_i, c_i, c_i]),
     "mmvae_bce_rowsum_fwd": (c_i, [c_p] * 3 + [c_i] * 3 + [c_p]),
     "mmvae_bce_sigmoid_clamp_bwd": (c_i, [c_p] * 4 + [c_i] * 3 + [c_p]),
     "mmvae_bce_rowsum_bwd": (c_i, [c_p] * 4 + [c_i] * 2 + [c_p]),

@@ -16,6 +16,7 @@ Conventions used by every layer op
 """
 import bisect
 import ctypes
+import math
 import os
 
 import torch
@@ -1428,9 +1429,10 @@ def _theta_grad_dest(theta, gtheta, wanted):
     return ret, 0, ret
 
 
-def _fusion_ws(ws_floats, B, D, dev):
-    """the backward kernel's partial prior-gradient rows; ws_floats: the name of the op's mmvae_*_ws_floats"""
-    return H.workspace(getattr(H.lib(), ws_floats)(B, D), dev)
+def _fusion_ws(ws_floats, B, D, dev, *more):
+    """the backward kernel's partial prior-gradient rows; ws_floats: the name of the op's mmvae_*_ws_floats (`more`: its
+    arguments behind B and D)"""
+    return H.workspace(getattr(H.lib(), ws_floats)(B, D, *more), dev)
 
 
 class TcFusion(Function):
@@ -1581,6 +1583,80 @@ def mixprior_fusion(theta, packed, eps, gtheta=None, raw=False):
         raise ValueError(f"mixprior_fusion: eps is {tuple(eps.shape)}; {E} experts of shape {tuple(packed[0].shape)} want "
                          f"({E}, {packed[0].shape[0]}, {packed[0].shape[1] // 2})")
     kl, resp, *zs = MixPriorFusion.apply(theta, gtheta, raw, eps, *packed)
+    return tuple(zs), kl, resp
+
+
+class MmPlusFusion(Function):
+    """MMVAE+'s latent op, K = 1 (csrc/mmplus.hip).  packed[e]: (B, 2 W) = [mu_e | lv_e] head outputs of W = D + P columns
+    per half, [0, D) the shared posterior, [D, W) the private one; eps_u (E,B,D), eps_w (E,B,P), eps_a (E,E,B,P) indexed
+    [decoder][source].  Returns kl (3E,B) -- rows m: the one-sample KL of the shared posterior to the mixture of all E, rows
+    E + m: its closed-form KL to the prior, rows 2E + m: the private posterior's to N(0, 1) --, resp (E,E,B) [not
+    differentiable], and z_0 .. z_{E-1} (E B, W) each: decoder n's whole input batch, row block m = [u_m | w_m] if n == m,
+    else [u_m | aux_scale eps_a[n][m]].  E outputs, so that every decoder's gradient arrives on its own (or as None)."""
+
+    @staticmethod
+    def forward(ctx, theta, gtheta, raw, D, aux_scale, eps_u, eps_w, eps_a, *packed):
+        packed = [H.f32c(t) for t in packed]
+        theta, eps_u, eps_w, eps_a = H.f32c(theta), H.f32c(eps_u), H.f32c(eps_w), H.f32c(eps_a)
+        E, (B, W2), dev = len(packed), packed[0].shape, packed[0].device
+        W = W2 // 2
+        P = W - D
+        assert all(p.shape == (B, W2) for p in packed) and theta.numel() == D
+        assert eps_u.shape == (E, B, D) and eps_w.shape == (E, B, P) and eps_a.shape == (E, E, B, P)
+        kl = torch.empty(3 * E, B, device=dev)
+        resp = torch.empty(E, E, B, device=dev)
+        zs = [torch.empty(E * B, W, device=dev) for _ in range(E)]
+        a = _head_tables(H.MmPlusFwdArgs(), packed, W)
+        for e in range(min(E, H.MAX_EXPERTS)):
+            a.z[e] = zs[e].data_ptr()
+        H.call("mmvae_mmplus_fwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps_u), H.ptr(eps_w), H.ptr(eps_a), float(aux_scale),
+               H.ptr(kl), H.ptr(resp), E, B, D, P, 2 * W, int(bool(raw)), H.stream())
+        ctx.save_for_backward(theta, eps_u, eps_w, resp, *packed)
+        ctx.cfg = (gtheta, E, B, D, P, int(bool(raw)))
+        ctx.mark_non_differentiable(resp)
+        ctx.set_materialize_grads(False)
+        return (kl, resp, *zs)
+
+    @staticmethod
+    def backward(ctx, dkl, _dresp, *dzs):
+        gtheta, E, B, D, P, raw = ctx.cfg
+        theta, eps_u, eps_w, resp, *packed = ctx.saved_tensors
+        dpacked = [torch.empty_like(p) for p in packed]
+        a = _head_tables(H.MmPlusBwdArgs(), packed, D + P, dpacked)
+        dkl, dzs = _upstream(dkl), [_upstream(g) for g in dzs]
+        for e in range(E):
+            a.dz[e] = H.ptr(dzs[e])
+        dth, acc, ret = _theta_grad_dest(theta, gtheta, ctx.needs_input_grad[0])
+        ws = _fusion_ws("mmvae_mmplus_ws_floats", B, D, theta.device, P)
+        H.call("mmvae_mmplus_bwd", ctypes.byref(a), H.ptr(theta), H.ptr(eps_u), H.ptr(eps_w), H.ptr(resp), H.ptr(dkl),
+               H.ptr(dth), H.ptr(ws), E, B, D, P, 2 * (D + P), raw, acc, H.stream())
+        return (ret, None, None, None, None, None, None, None, *dpacked)
+
+
+def mmplus_fusion(theta, packed, eps_u, eps_w, eps_a, D, aux_scale, gtheta=None, raw=False):
+    """-> z (a tuple of E tensors (E B, W): every decoder's input batch), kl (3E,B), resp (E,E,B) of MMVAE+'s latent op
+    (MmPlusFusion).  D: the number of shared columns of the W = packed[e].shape[1] / 2 (the rest are private); eps_u
+    (E,B,D), eps_w (E,B,W-D), eps_a (E,E,B,W-D) standard-normal draws; aux_scale: the scale of the auxiliary cross prior;
+    gtheta, raw: as tc_fusion"""
+    E = len(packed)
+    if E < 1:
+        raise ValueError("mmplus_fusion: no heads")
+    B, W2 = packed[0].shape
+    D, aux_scale = int(D), float(aux_scale)
+    P = W2 // 2 - D
+    if W2 % 2 or any(tuple(p.shape) != (B, W2) for p in packed):
+        raise ValueError(f"mmplus_fusion: heads of shapes {[tuple(p.shape) for p in packed]}: every head is (B, 2 W) = "
+                         f"[mu | lv] with the same B and W")
+    if D < 1 or P < 1:
+        raise ValueError(f"mmplus_fusion: D = {D} shared of W = {W2 // 2} columns leaves P = {P} private: both must be >= 1")
+    if theta.numel() != D:
+        raise ValueError(f"mmplus_fusion: theta has {theta.numel()} elements; the D = {D} shared columns want {D}")
+    for name, t, want in (("eps_u", eps_u, (E, B, D)), ("eps_w", eps_w, (E, B, P)), ("eps_a", eps_a, (E, E, B, P))):
+        if tuple(t.shape) != want:
+            raise ValueError(f"mmplus_fusion: {name} is {tuple(t.shape)}; {E} heads of shape {(B, W2)} with D = {D} want {want}")
+    if not (math.isfinite(aux_scale) and aux_scale > 0):
+        raise ValueError(f"mmplus_fusion: aux_scale = {aux_scale} must be finite and > 0")
+    kl, resp, *zs = MmPlusFusion.apply(theta, gtheta, raw, D, aux_scale, eps_u, eps_w, eps_a, *packed)
     return tuple(zs), kl, resp
 
 

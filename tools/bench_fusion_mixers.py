@@ -1,11 +1,13 @@
-"""Timing of the MVTCAE, mmJSD and MMVM paths on the GPU box (no fallback: needs the MI355X).  Per mixer (--mixer, default:
-all three, one after the other) it writes profiles/<mixer>_timing.txt (--out-dir) and prints one JSON line.
+"""Timing of the MVTCAE, mmJSD and MMVM paths and of the MMVAE+ latent op on the GPU box (no fallback: needs the MI355X).  Per mixer (--mixer,
+default: the first three, one after the other) it writes profiles/<mixer>_timing.txt (--out-dir) and prints one JSON line.
 
-(a) the mixer's fusion op forward + backward (csrc/tcfusion.hip, jsfusion.hip, mixprior.hip: one launch each way + the fold
-    of the prior gradient) against the same function composed from torch-ROCm float32 ops with autograd (the mixer's
-    tests/*_reference.py on the device, in its cheaper form where it has two), raw heads off, at B = 128, D = 32,
-    E in {2, 3, 5} and B = 1000, D = 64, E = 2.  mmJSD: uniform weights, rows in balanced chunks.  Both sides eager, issued
-    from Python.
+(a) the mixer's fusion op forward + backward (csrc/tcfusion.hip, jsfusion.hip, mixprior.hip, mmplus.hip: one launch each way
+    + the fold of the prior gradient) against the same function composed from torch-ROCm float32 ops with autograd (the
+    mixer's tests/*_reference.py on the device, in its cheaper form where it has two), raw heads off, at B = 128, D = 32,
+    E in {2, 3, 5} and B = 1000, D = 64, E = 2.  mmJSD: uniform weights, rows in balanced chunks.  MMVAE+: P = D private
+    columns, and a third side, the same outputs composed from the library's EXISTING ops (mixprior_fusion on a copy of the
+    shared columns, one poe_reparam_kl per private code, the scaled auxiliary draws, rows_fan or torch.cat for the decoder
+    batches).  All sides eager, issued from Python.
 (b) ms/step of the captured step (trainer.capture / fused_step) of the mixer and of the mixers it is compared with (MIXERS)
     on the CdSprites+ towers at B = 128 (the cfg2 shapes: D = 32, T = 32) and on the image + text + action towers (the cfg5
     shapes: Ta = 100), one after the other in this process.
@@ -64,6 +66,44 @@ def _mm_composed(R, t):
     return [kl, z], [t["gkl"], t["gz"]]
 
 
+def _plus_hip(R, t):
+    z, kl, _ = ops.mmplus_fusion(t["theta"], t["heads"], t["eps_u"], t["eps_w"], t["eps_a"], t["D"], 1.5)
+    return [kl, *z], [t["gkl"], *t["gz"].unbind(0)]
+
+
+def _plus_composed(R, t):
+    z, kl, _ = R.mmplus_reference(t["theta"], t["heads"], t["eps_u"], t["eps_w"], t["eps_a"], t["D"], 1.5, form="plain")
+    return [kl, *z], [t["gkl"], *t["gz"].unbind(0)]
+
+
+def _plus_existing(R, t):
+    """the latent side of an MMVAE+ step from the ops the library had before mmplus_fusion (heads that are not raw: in a
+    step the towers' softmax launches, one per tower and direction, come on top)"""
+    heads, D = t["heads"], t["D"]
+    E, W = len(heads), heads[0].shape[1] // 2
+    P = W - D
+    if "theta0" not in t:
+        t["theta0"] = torch.zeros(1, P, device=DEV)
+        t["gklp"] = [torch.stack([torch.zeros_like(t["gkl"][0]), t["gkl"][2 * E + m]]) for m in range(E)]
+    shared = [torch.cat([h[:, :D], h[:, W:W + D]], -1) for h in heads]
+    u, kl, _ = ops.mixprior_fusion(t["theta"], shared, t["eps_u"])
+    w, klp = [], []
+    for m in range(E):
+        _, k, z = ops.poe_reparam_kl(t["theta0"], [heads[m]], [t["eps_w"][m]], 2, 0b10, cols=(D, P))
+        w.append(z[0])
+        klp.append(k)
+    aux = 1.5 * t["eps_a"]
+    zs = []
+    for n in range(E):
+        srcs = list(u) + [w[m] if m == n else aux[n, m] for m in range(E)]
+        plan = [(E, W, [(m, m, 0) for m in range(E)] + [(E + m, m, D) for m in range(E)])]
+        if ops.RowsFan.supported(plan, srcs):
+            zs.append(ops.rows_fan(plan, srcs)[0])
+        else:
+            zs.append(torch.cat([torch.cat(list(u), 0), torch.cat(srcs[E:], 0)], -1))
+    return [kl, *klp, *zs], [t["gkl"][:2 * E], *t["gklp"], *t["gz"].unbind(0)]
+
+
 # mixer -> title, reference module, op, the two sides of (a), what the composed side is, the mixers of (b) (the first: itself)
 MIXERS = {
     "mvtcae": dict(title="MVTCAE", ref="tc_reference", op="tc_fusion", hip=_tc_hip, composed=_tc_composed,
@@ -80,6 +120,14 @@ MIXERS = {
                     "    torch-ROCm float32 ops with autograd (absolute log-densities and their logsumexp: the cheaper form), both eager,",
                     "    ms per call (windows alternate composed, HIP):"],
                  steps=("mmvm", "moe", "mmjsd", "mopoe")),
+    "mmvaeplus": dict(title="MMVAE+", ref="mmplus_reference", op="mmplus_fusion", hip=_plus_hip, composed=_plus_composed,
+                      existing=_plus_existing, case=lambda R, E, D, B: R.Case(E, D, D, B),
+                      a=["(a) ops.mmplus_fusion forward + backward (2 launches + the prior-gradient fold), P = D private columns, vs the",
+                         "    same outputs composed from torch-ROCm float32 ops with autograd (absolute log-densities: the cheaper form) and",
+                         "    vs their composition from the library's existing ops (mixprior_fusion on a copy of the shared columns, E",
+                         "    poe_reparam_kl calls, the scaled auxiliary draws, rows_fan / cat per decoder; heads not raw: the 2 E softmax",
+                         "    launches of a step are not in it), all eager, ms per call (windows alternate composed, existing, HIP):"],
+                      steps=()),      # (the latent op alone: no mixer is built on it yet)
 }
 
 
@@ -97,7 +145,9 @@ def window(fn, calls):
 
 def bench_fusion(spec, B, D, E, windows, calls):
     R = importlib.import_module(spec["ref"])
-    t = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in R.make_inputs(R.Case(E, D, B)).items()}
+    case = spec["case"](R, E, D, B) if "case" in spec else R.Case(E, D, B)
+    t = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in R.make_inputs(case).items()}
+    t["D"] = D
     t["heads"] = [h.to(DEV).requires_grad_(True) for h in t["heads"]]
     t["theta"].requires_grad_(True)
     leaves = [t["theta"]] + t["heads"]
@@ -108,14 +158,22 @@ def bench_fusion(spec, B, D, E, windows, calls):
             return torch.autograd.grad(outs, leaves, gouts)
         return run
     hip, composed = side(spec["hip"]), side(spec["composed"])
+    existing = side(spec["existing"]) if "existing" in spec else None
     for _ in range(20):
         a, b = hip(), composed()
+        c = existing() if existing else None
     dev = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(a, b))
-    ms = {"hip": [], "torch": []}
+    ms = {"hip": [], "torch": [], "existing": []}
     for _ in range(windows):
         ms["torch"].append(window(composed, calls))
+        if existing:
+            ms["existing"].append(window(existing, calls))
         ms["hip"].append(window(hip, calls))
-    return {"B": B, "D": D, "E": E, "hip_ms": ms["hip"], "torch_ms": ms["torch"], "grad_dev": dev}
+    out = {"B": B, "D": D, "E": E, "hip_ms": ms["hip"], "torch_ms": ms["torch"], "grad_dev": dev}
+    if existing:
+        out["existing_ms"] = ms["existing"]
+        out["existing_grad_dev"] = max(float((x - y).abs().max() / y.abs().max()) for x, y in zip(c, b))
+    return out
 
 
 def bench_step(mixing, towers, windows, calls):
@@ -159,8 +217,12 @@ def bench_mixer(name, args):
         lines.append(f"    B {B:4d} D {D:2d} E {E}: HIP {h:.4f}  composed {t:.4f}  HIP/composed {h / t:.3f}  (HIP min-max "
                      f"{min(r['hip_ms']):.4f}-{max(r['hip_ms']):.4f}, composed {min(r['torch_ms']):.4f}-{max(r['torch_ms']):.4f}; "
                      f"gradients deviate {r['grad_dev']:.1e} relative)")
+        if "existing_ms" in r:
+            x = med(r["existing_ms"])
+            lines.append(f"                     existing ops {x:.4f}  HIP/existing {h / x:.3f}  (min-max {min(r['existing_ms']):.4f}-"
+                         f"{max(r['existing_ms']):.4f}; gradients deviate {r['existing_grad_dev']:.1e} relative)")
         flush()
-    if not args.skip_steps:
+    if not args.skip_steps and spec["steps"]:
         n = max(args.calls // 2, 1)
         lines += ["", f"(b) captured training step (objective + backward + Adam in one hipGraph), ms/step, B = 128, D = 32, T = 32, "
                       f"windows of {n} steps, the {2 * len(spec['steps'])} models one after the other:"]
@@ -180,7 +242,7 @@ def bench_mixer(name, args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mixer", choices=sorted(MIXERS), action="append", help="default: all three")
+    ap.add_argument("--mixer", choices=sorted(MIXERS), action="append", help="default: mvtcae, mmjsd and mmvm")
     ap.add_argument("--out-dir", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--calls", type=int, default=100)
