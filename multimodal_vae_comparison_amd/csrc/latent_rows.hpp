@@ -1,10 +1,10 @@
 // The frame shared by the fused latent ops (latent.hip: product of experts; tcfusion.hip: total-correlation fusion;
 // jsfusion.hip: Jensen-Shannon fusion; mixprior.hip: mixture-of-experts prior; mmplus.hip: MMVAE+'s split latents): one
 // wavefront per sample, lanes over the latent dimension in POE_SLOTS column slots of 64.  Around each op's own arithmetic:
-// the prior scale, the raw heads
-// (lv = softmax(u) + 1e-6 applied by the kernels, both ways), the workgroup's partial prior-gradient row, the fold of these
-// rows into dtheta, and the host side's support rule, workspace size and fold launch.  The pointer tables come in as
-// arrays of MMVAE_MAX_EXPERTS pointers: mmvae_tc_*_args and mmvae_poe_*_args both fit.
+// the prior scale, the raw heads (lv = softmax(u) + 1e-6 applied by the kernels, both ways), the workgroup's partial
+// prior-gradient row, the fold of these rows into dtheta, and the host side's support rule, workspace size and fold launch.
+// The pointer tables come in as arrays of MMVAE_MAX_EXPERTS pointers: mmvae_tc_*_args, mmvae_poe_*_args and
+// mmvae_mmplus_*_args all fit.  The arithmetic mixprior.hip and mmplus.hip share stands on this frame in mixture_rows.hpp.
 #pragma once
 #include "common.hpp"
 
@@ -169,8 +169,8 @@ __device__ __forceinline__ void poe_theta_body(const float* __restrict__ theta, 
   }
 }
 
-// the fold as a launch of its own behind tcfusion.hip's, jsfusion.hip's and mixprior.hip's backward kernels, whose
-// workgroups each leave one partial row in ws
+// the fold as a launch of its own behind tcfusion.hip's, jsfusion.hip's, mixprior.hip's and mmplus.hip's backward kernels,
+// whose workgroups each leave one partial row in ws
 static __global__ __launch_bounds__(256) void theta_fold_kernel(const float* __restrict__ theta, const float* __restrict__ ws,
                                                                 float* __restrict__ dtheta, int nrows, int D,
                                                                 int accumulate) {
@@ -178,7 +178,7 @@ static __global__ __launch_bounds__(256) void theta_fold_kernel(const float* __r
   poe_theta_body<false>(theta, ws, dtheta, nrows, D, accumulate, part);
 }
 
-// ---- host side of the three ops with one partial row per workgroup --------------------------------------------------
+// ---- host side of the four ops with one partial row per workgroup ---------------------------------------------------
 static inline bool fusion_supported(int E, int D) { return E <= MMVAE_MAX_EXPERTS && D <= 64 * POE_SLOTS; }
 
 static inline size_t fusion_ws_floats(int B, int D) {

@@ -7,24 +7,13 @@
 //
 // Expert j is q_j = N(mu_j, sigma_j = lv_j) (the head read as the SCALE, as MOE samples from it), the fixed prior is
 // N(0, sp), sp = softmax(theta) D.  Per row, with z_m = mu_m + sigma_m eps_m and h = (1/E) sum_j q_j:
-//   delta_mj = (mu_m - mu_j) + sigma_m eps_m                                    z_m - mu_j, formed from the difference
-//   u_mj     = delta_mj / sigma_j,   u_mm = eps_m
-//   D_mj     = sum_d [ -1/2 (u_mj - eps_m)(u_mj + eps_m) - log(sigma_j / sigma_m) ]   = log q_j(z_m) - log q_m(z_m), D_mm = 0
-//   kl_mix[m] = log q_m(z_m) - log h(z_m) = log E - log sum_j exp(D_mj)          (shifted by max_j D_mj >= 0)
-//   resp[m][j] = softmax_j D_mj
-//   kl_std[m] = sum_d KL(N(mu_m, sigma_m) || N(0, sp))
-// The absolute log-densities are never formed: at D = 256 they reach the hundreds and their difference keeps their
-// rounding, at scales of 1e-5 log sigma does (float32 on the host against float64: 4.8e-5 and 6.8e-5 of a KL entry against
-// 2.7e-6 and 7.4e-7 in this form).
-// Backward, with g_m = dkl[m], g'_m = dkl[E + m], gz_m = dz[m], c_mj = -g_m resp[m][j] (the responsibilities are read
-// back, the row sums are not taken again), r = 1 / sp^2, per element and for every ordered pair m != j:
-//   dmu_m  += -c_mj u_mj / sigma_j                      dmu_j  += c_mj u_mj / sigma_j
-//   dsg_m  +=  c_mj (1 / sigma_m - u_mj eps_m / sigma_j)  dsg_j  += c_mj (u_mj^2 - 1) / sigma_j
-// on top of dmu_m = gz_m + g'_m mu_m r, dsg_m = gz_m eps_m + g'_m (sigma_m r - 1 / sigma_m);
+//   kl_mix[m] = log q_m(z_m) - log h(z_m),   resp[m][j] = q_j(z_m) / sum_k q_k(z_m)      (mixture_rows.hpp: the arithmetic,
+//   kl_std[m] = sum_d KL(N(mu_m, sigma_m) || N(0, sp))                                     forward and backward)
+// Backward, with g'_m = dkl[E + m], gz_m = dz[m], r = 1 / sp^2, the mixture's pair terms come on top of
+//   dmu_m = gz_m + g'_m mu_m r,   dsg_m = gz_m eps_m + g'_m (sigma_m r - 1 / sigma_m);
 //   dsp = sum_m g'_m (1 - (sigma_m^2 + mu_m^2) r) / sp.
-// The pairs are walked sample by sample (m outermost), so every gradient element is a sum over the E samples in order.
 #include "common.hpp"
-#include "latent_rows.hpp"
+#include "mixture_rows.hpp"
 
 __global__ __launch_bounds__(256) void mixprior_fwd_kernel(mmvae_poe_fwd_args a, const float* __restrict__ theta,
                                                            float* __restrict__ kl, float* __restrict__ resp, int E, int B,
@@ -57,7 +46,7 @@ __global__ __launch_bounds__(256) void mixprior_fwd_kernel(mmvae_poe_fwd_args a,
           if (e >= E) continue;
           mu[e] = a.mu[e][oi];
           sg[e] = a.lv[e][oi];
-          if (raw) sg[e] = expf(sg[e] - umx[e]) * uinv[e] + 1e-6f;
+          if (raw) sg[e] = raw_head_scale(sg[e], umx[e], uinv[e]);
           ep[e] = a.eps[e][o];
           a.z[e][o] = mu[e] + sg[e] * ep[e];
           ks[e] += kl_elem(mu[e], sg[e], sp[s]);
@@ -68,8 +57,7 @@ __global__ __launch_bounds__(256) void mixprior_fwd_kernel(mmvae_poe_fwd_args a,
 #pragma unroll
           for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
             if (j >= E || j == m) continue;
-            const float u = ((mu[m] - mu[j]) + sg[m] * ep[m]) / sg[j];
-            dl[m][j] += -0.5f * (u - ep[m]) * (u + ep[m]) - logf(sg[j] / sg[m]);
+            dl[m][j] += mix_dl(mu[m], sg[m], ep[m], mu[j], sg[j]);
           }
         }
       }
@@ -78,28 +66,8 @@ __global__ __launch_bounds__(256) void mixprior_fwd_kernel(mmvae_poe_fwd_args a,
     for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {
       if (m >= E) continue;
       const float kstd = wave_sum(ks[m]);
-      float mx = 0.f;      // D_mm = 0 is one of the E
-#pragma unroll
-      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
-        if (j >= E || j == m) continue;
-        dl[m][j] = wave_sum(dl[m][j]);
-        mx = fmaxf(mx, dl[m][j]);
-      }
-      float ex[MMVAE_MAX_EXPERTS], S = 0.f;
-#pragma unroll
-      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
-        if (j >= E) continue;
-        ex[j] = expf(dl[m][j] - mx);      // (dl[m][m] is the 0 it was set to)
-        S += ex[j];
-      }
-      if (lane == 0) {
-        kl[(size_t)m * B + b] = logE - (mx + logf(S));
-        kl[(size_t)(E + m) * B + b] = kstd;
-        const float invS = 1.0f / S;
-#pragma unroll
-        for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j)
-          if (j < E) resp[((size_t)m * E + j) * B + b] = ex[j] * invS;
-      }
+      mix_row_finish(dl, m, E, B, b, lane, logE, kl, resp);
+      if (lane == 0) kl[(size_t)(E + m) * B + b] = kstd;
     }
   }
 }
@@ -118,15 +86,7 @@ __global__ __launch_bounds__(256) void mixprior_bwd_kernel(mmvae_poe_bwd_args a,
   for (int s = 0; s < POE_SLOTS; ++s) dsp[s] = 0.f;
   for (int b = wave; b < B; b += nwaves) {
     float c[MMVAE_MAX_EXPERTS][MMVAE_MAX_EXPERTS], gs[MMVAE_MAX_EXPERTS];
-#pragma unroll
-    for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {
-      if (m >= E) continue;
-      const float g = dkl ? dkl[(size_t)m * B + b] : 0.f;
-      gs[m] = dkl ? dkl[(size_t)(E + m) * B + b] : 0.f;
-#pragma unroll
-      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j)
-        if (j < E && j != m) c[m][j] = -g * resp[((size_t)m * E + j) * B + b];
-    }
+    mix_upstream(dkl, resp, E, B, b, c, gs);
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS], udot[MMVAE_MAX_EXPERTS];
 #pragma unroll
     for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) udot[e] = 0.f;
@@ -146,7 +106,7 @@ __global__ __launch_bounds__(256) void mixprior_bwd_kernel(mmvae_poe_bwd_args a,
           if (e >= E) continue;
           mu[e] = a.mu[e][oi];
           sg[e] = a.lv[e][oi];
-          if (raw) sg[e] = expf(sg[e] - umx[e]) * uinv[e] + 1e-6f;
+          if (raw) sg[e] = raw_head_scale(sg[e], umx[e], uinv[e]);
           ep[e] = a.eps[e][o];
           inv[e] = 1.0f / sg[e];
           const float gz = a.dz[e] ? a.dz[e][o] : 0.f;
@@ -161,12 +121,7 @@ __global__ __launch_bounds__(256) void mixprior_bwd_kernel(mmvae_poe_bwd_args a,
 #pragma unroll
           for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
             if (j >= E || j == m) continue;
-            const float u = ((mu[m] - mu[j]) + sg[m] * ep[m]) / sg[j];
-            const float t = c[m][j] * (u * inv[j]);
-            dmu[m] -= t;
-            dmu[j] += t;
-            dsg[m] += c[m][j] * (inv[m] - u * ep[m] * inv[j]);
-            dsg[j] += c[m][j] * ((u * u - 1.0f) * inv[j]);
+            mix_pair_bwd(mu[m], sg[m], ep[m], inv[m], mu[j], sg[j], inv[j], c[m][j], dmu[m], dsg[m], dmu[j], dsg[j]);
           }
         }
 #pragma unroll
@@ -178,23 +133,7 @@ __global__ __launch_bounds__(256) void mixprior_bwd_kernel(mmvae_poe_bwd_args a,
         }
       }
     }
-    // latent_rows.hpp's raw_head_bwd, kept as text: as a call this kernel, and only this one, came out at 260 VGPRs for 254
-    if (raw) {
-#pragma unroll
-      for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) {
-        if (e >= E) continue;
-        const float dot = wave_sum(udot[e]);
-#pragma unroll
-        for (int s = 0; s < POE_SLOTS; ++s) {
-          const int d = lane + 64 * s;
-          if (d < D) {
-            const size_t oi = (size_t)b * ld + d;
-            const float sv = expf(a.lv[e][oi] - umx[e]) * uinv[e];
-            a.dlv[e][oi] = D == 1 ? 0.f : sv * (a.dlv[e][oi] - dot);
-          }
-        }
-      }
-    }
+    if (raw) raw_head_bwd(a.lv, a.dlv, E, (size_t)b * ld, D, lane, umx, uinv, udot);
   }
   prior_grad_row(dsp, part, ws, D, lane);
 }

@@ -2,7 +2,7 @@
 // [0, D) its SHARED posterior q_m^u, [D, W) its PRIVATE posterior q_m^w --, and one launch each way does the whole latent
 // side of a step: one reparameterised sample (u_m, w_m) per modality, the auxiliary private draws s eps_a[n][m] every OTHER
 // decoder n gets in place of w_m, every decoder's whole input batch z[n] (E B, W), the one-sample estimate of the shared
-// posterior's KL to the uniform mixture of all E (mixprior.hip's arithmetic, column for column), the closed-form KLs of
+// posterior's KL to the uniform mixture of all E (mixture_rows.hpp, shared with mixprior.hip), the closed-form KLs of
 // the shared posterior to N(0, sp) and of the private one to N(0, 1), and the responsibilities.  The frame is
 // latent_rows.hpp's: one wavefront per sample, lanes over the columns in POE_SLOTS slots of 64 -- the shared columns in
 // one sweep, the private ones in a second --, wave-shuffle row sums; no atomics and no in-launch election: every sum is
@@ -12,18 +12,18 @@
 // columns, so the shared and the private columns share one normaliser and, backward, one dot product.  With sigma = lv,
 // sp = softmax(theta) D, u_m = mu_m^u + sigma_m^u eps_u[m], w_m = mu_m^w + sigma_m^w eps_w[m]:
 //   z[n] row m B + b = [u_m | w_m]  (n == m)     [u_m | s eps_a[n][m]]  (n != m)
-//   kl row m       = log q_m^u(u_m) - log (1/E) sum_j q_j^u(u_m)        (mixprior.hip: D_mj, formed from differences)
+//   kl row m       = log q_m^u(u_m) - log (1/E) sum_j q_j^u(u_m)        (mixture_rows.hpp: D_mj, formed from differences)
 //   kl row E + m   = sum_d KL(q_m^u || N(0, sp))
 //   kl row 2E + m  = sum_p KL(q_m^w || N(0, 1))
 //   resp[m][j]     = softmax_j D_mj
 // Backward: the gradient of u_m is the sum over n = 0 .. E-1, in that order, of columns [0, D) of row block m of dz[n];
 // the gradient of w_m is columns [D, W) of row block m of dz[m] alone (the auxiliary draws are noise).  The pair terms are
-// mixprior.hip's; the private columns add  dmu = gw + g'' mu,  dsg = gw eps_w + g'' (sigma - 1 / sigma),  g'' = dkl[2E + m].
+// mixture_rows.hpp's; the private columns add  dmu = gw + g'' mu,  dsg = gw eps_w + g'' (sigma - 1 / sigma),  g'' = dkl[2E + m].
 // The prior gradient is split at its cancellation (the end of mmplus_bwd_kernel).
 #include <cmath>
 
 #include "common.hpp"
-#include "latent_rows.hpp"
+#include "mixture_rows.hpp"
 
 __global__ __launch_bounds__(256) void mmplus_fwd_kernel(mmvae_mmplus_fwd_args a, const float* __restrict__ theta,
                                                          const float* __restrict__ eps_u, const float* __restrict__ eps_w,
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(256) void mmplus_fwd_kernel(mmvae_mmplus_fwd_args a
     }
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS];
     if (raw) raw_head_stats(a.lv, E, (size_t)b * ld, W, lane, umx, uinv);
-    // ---- the shared columns: mixprior.hip's sweep; u_m goes to row block m of EVERY decoder's batch
+    // ---- the shared columns: mixprior.hip's sweep around mixture_rows.hpp; u_m goes to row block m of EVERY decoder's batch
 #pragma unroll
     for (int s = 0; s < POE_SLOTS; ++s) {
       const int d = lane + 64 * s;
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void mmplus_fwd_kernel(mmvae_mmplus_fwd_args a
           if (e >= E) continue;
           mu[e] = a.mu[e][oi];
           sg[e] = a.lv[e][oi];
-          if (raw) sg[e] = expf(sg[e] - umx[e]) * uinv[e] + 1e-6f;
+          if (raw) sg[e] = raw_head_scale(sg[e], umx[e], uinv[e]);
           ep[e] = eps_u[((size_t)e * B + b) * D + d];
           const float zu = mu[e] + sg[e] * ep[e];
           const size_t oz = ((size_t)e * B + b) * W + d;
@@ -73,8 +73,7 @@ __global__ __launch_bounds__(256) void mmplus_fwd_kernel(mmvae_mmplus_fwd_args a
 #pragma unroll
           for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
             if (j >= E || j == m) continue;
-            const float u = ((mu[m] - mu[j]) + sg[m] * ep[m]) / sg[j];
-            dl[m][j] += -0.5f * (u - ep[m]) * (u + ep[m]) - logf(sg[j] / sg[m]);
+            dl[m][j] += mix_dl(mu[m], sg[m], ep[m], mu[j], sg[j]);
           }
         }
       }
@@ -90,7 +89,7 @@ __global__ __launch_bounds__(256) void mmplus_fwd_kernel(mmvae_mmplus_fwd_args a
           if (m >= E) continue;
           const float mu = a.mu[m][oi];
           float sg = a.lv[m][oi];
-          if (raw) sg = expf(sg - umx[m]) * uinv[m] + 1e-6f;
+          if (raw) sg = raw_head_scale(sg, umx[m], uinv[m]);
           const size_t oz = ((size_t)m * B + b) * W + D + p;
 #pragma unroll
           for (int n = 0; n < MMVAE_MAX_EXPERTS; ++n) {
@@ -107,28 +106,10 @@ __global__ __launch_bounds__(256) void mmplus_fwd_kernel(mmvae_mmplus_fwd_args a
       if (m >= E) continue;
       const float kstd = wave_sum(ks[m]);
       const float kprv = wave_sum(kw[m]);
-      float mx = 0.f;      // D_mm = 0 is one of the E
-#pragma unroll
-      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
-        if (j >= E || j == m) continue;
-        dl[m][j] = wave_sum(dl[m][j]);
-        mx = fmaxf(mx, dl[m][j]);
-      }
-      float ex[MMVAE_MAX_EXPERTS], S = 0.f;
-#pragma unroll
-      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
-        if (j >= E) continue;
-        ex[j] = expf(dl[m][j] - mx);      // (dl[m][m] is the 0 it was set to)
-        S += ex[j];
-      }
+      mix_row_finish(dl, m, E, B, b, lane, logE, kl, resp);
       if (lane == 0) {
-        kl[(size_t)m * B + b] = logE - (mx + logf(S));
         kl[(size_t)(E + m) * B + b] = kstd;
         kl[(size_t)(2 * E + m) * B + b] = kprv;
-        const float invS = 1.0f / S;
-#pragma unroll
-        for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j)
-          if (j < E) resp[((size_t)m * E + j) * B + b] = ex[j] * invS;
       }
     }
   }
@@ -152,16 +133,10 @@ __global__ __launch_bounds__(256) void mmplus_bwd_kernel(mmvae_mmplus_bwd_args a
   for (int s = 0; s < POE_SLOTS; ++s) dsp[s] = 0.f;
   for (int b = wave; b < B; b += nwaves) {
     float c[MMVAE_MAX_EXPERTS][MMVAE_MAX_EXPERTS], gs[MMVAE_MAX_EXPERTS], gp[MMVAE_MAX_EXPERTS];
+    mix_upstream(dkl, resp, E, B, b, c, gs);
 #pragma unroll
-    for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m) {
-      if (m >= E) continue;
-      const float g = dkl ? dkl[(size_t)m * B + b] : 0.f;
-      gs[m] = dkl ? dkl[(size_t)(E + m) * B + b] : 0.f;
-      gp[m] = dkl ? dkl[(size_t)(2 * E + m) * B + b] : 0.f;
-#pragma unroll
-      for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j)
-        if (j < E && j != m) c[m][j] = -g * resp[((size_t)m * E + j) * B + b];
-    }
+    for (int m = 0; m < MMVAE_MAX_EXPERTS; ++m)
+      if (m < E) gp[m] = dkl ? dkl[(size_t)(2 * E + m) * B + b] : 0.f;
     float umx[MMVAE_MAX_EXPERTS], uinv[MMVAE_MAX_EXPERTS], udot[MMVAE_MAX_EXPERTS];
 #pragma unroll
     for (int e = 0; e < MMVAE_MAX_EXPERTS; ++e) udot[e] = 0.f;
@@ -181,7 +156,7 @@ __global__ __launch_bounds__(256) void mmplus_bwd_kernel(mmvae_mmplus_bwd_args a
           if (e >= E) continue;
           mu[e] = a.mu[e][oi];
           sg[e] = a.lv[e][oi];
-          if (raw) sg[e] = expf(sg[e] - umx[e]) * uinv[e] + 1e-6f;
+          if (raw) sg[e] = raw_head_scale(sg[e], umx[e], uinv[e]);
           ep[e] = eps_u[((size_t)e * B + b) * D + d];
           inv[e] = 1.0f / sg[e];
           // u_e is read by every decoder: its gradient is their sum, decoder 0 first
@@ -201,12 +176,7 @@ __global__ __launch_bounds__(256) void mmplus_bwd_kernel(mmvae_mmplus_bwd_args a
 #pragma unroll
           for (int j = 0; j < MMVAE_MAX_EXPERTS; ++j) {
             if (j >= E || j == m) continue;
-            const float u = ((mu[m] - mu[j]) + sg[m] * ep[m]) / sg[j];
-            const float t = c[m][j] * (u * inv[j]);
-            dmu[m] -= t;
-            dmu[j] += t;
-            dsg[m] += c[m][j] * (inv[m] - u * ep[m] * inv[j]);
-            dsg[j] += c[m][j] * ((u * u - 1.0f) * inv[j]);
+            mix_pair_bwd(mu[m], sg[m], ep[m], inv[m], mu[j], sg[j], inv[j], c[m][j], dmu[m], dsg[m], dmu[j], dsg[j]);
           }
         }
 #pragma unroll
@@ -229,7 +199,7 @@ __global__ __launch_bounds__(256) void mmplus_bwd_kernel(mmvae_mmplus_bwd_args a
           if (m >= E) continue;
           const float mu = a.mu[m][oi];
           float sg = a.lv[m][oi];
-          if (raw) sg = expf(sg - umx[m]) * uinv[m] + 1e-6f;
+          if (raw) sg = raw_head_scale(sg, umx[m], uinv[m]);
           const float gz = a.dz[m] ? a.dz[m][((size_t)m * B + b) * W + D + p] : 0.f;
           const float dsg = gz * eps_w[((size_t)m * B + b) * P + p] + gp[m] * (sg - 1.0f / sg);
           a.dmu[m][oi] = gz + gp[m] * mu;

@@ -1385,7 +1385,7 @@ class PoeReparamKL(Function):
                 *([None] * ctx.n_eps_in))
 
 
-# ---- plumbing under the three single-pass fusions (TcFusion, JsFusion, MixPriorFusion) --------------------------------
+# ---- plumbing under the four single-pass fusions (TcFusion, JsFusion, MixPriorFusion, MmPlusFusion) -------------------
 def _fusion_inputs(theta, eps, packed, eps_per_expert=False):
     """float32 contiguous inputs and their shared shape checks: E heads (B, 2 D) = [mu_e | lv_e], theta of D numbers, eps
     (B,D) or, `eps_per_expert`, (E,B,D) -> (packed, theta, eps, E, B, D, device)"""
