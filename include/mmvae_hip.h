@@ -217,7 +217,8 @@ int mmvae_conv_plan(int split_bf16);
  *   A(m,k) at A[m*sam + k*sak],  B(k,n) at Bm[k*sbk + n*sbn],  C row-major with leading dim ldc.
  *   bias: per column n, or NULL.  a_rowsum (optional, length M): (+)= sum_k act(A)(m,k)
  *   (the bias gradient when A = dy^T).  splitk > 1 needs ws of mmvae_gemm_ws_floats() floats and
- *   allows neither bias nor epilogue (partials are summed by mmvae_reduce_rows).
+ *   allows neither bias nor epilogue (partials are summed by mmvae_reduce_rows: unless deferred, ldc must be N then,
+ *   or MMVAE_ERR_UNSUPPORTED).
  * ---------------------------------------------------------------------------------------------- */
 int mmvae_gemm_f32(const float* A, const float* Bm, const float* bias, const float* aux, float* C,
                    float* a_rowsum, float* ws, int M, int N, int K, long sam, long sak, long sbk, long sbn,
@@ -283,6 +284,100 @@ int mmvae_linear_bwd(const float* dy, const float* x, const float* w, const floa
                      float* db, float* ws, int M, int N, int K, long ldx, int x_act, int ep_mode, int accumulate,
                      mmvae_stream_t stream);
 size_t mmvae_linear_bwd_ws_floats(int M, int N, int K);
+
+/* Which kernel instantiation of csrc/gemm.hip serves a call: one value per instantiation, returned by the three queries
+ * below and switched on by mmvae_gemm_f32 / mmvae_linear_fwd / mmvae_linear_bwd themselves (the query IS the dispatch).
+ * Operand orientation suffix: A then B, K = reduction index contiguous in memory, M / N = row / column index contiguous.
+ * Load suffix of the register-operand kernels: A then B, V = float4 along k, S = strided dwords.
+ *   B16_<o>_<g>       gemm_b16_kernel (split-bf16 LDS tiles), g k-groups per tile
+ *   BIG<bn>_<o>       gemm_big_kernel, 128 x bn tiles
+ *   RSPLIT_<d>        rgemm_kernel<d, false, false> with gridDim.z = nz > 1 (weight gradients with few tiles)
+ *   R16_<d>_<l>       rgemm16_kernel (16 x 16 tiles), reduction slices d deep
+ *   R32_<d>_<l>       rgemm_kernel (32 x 32 tiles), one split
+ *   STAGED<v>_<o>     gemm_kernel<v, ..> (LDS staged; v = 1: 128 x 32 tiles, 4 / 8: 32 x 32 tiles over 4 / 8 waves)
+ *   PROJ32            the 32-wide projection of csrc/ffn.hip (mmvae_linear_fwd only)
+ *   LINBWD_B16_<g>    gemm_b16_linear_bwd_kernel<g>
+ *   LINBWD_R_<d>_T<t> rgemm_grouped_kernel<d, 16, t == 16>: data gradient d deep on t x t tiles
+ *   LINBWD_STAGED     gemm_grouped_kernel
+ *   LINBWD_TWO        mmvae_linear_bwd_weight, then mmvae_linear_bwd_data (each with its own path) */
+enum {
+  MMVAE_GEMM_B16_KK_1 = 16,
+  MMVAE_GEMM_B16_KN_1,
+  MMVAE_GEMM_B16_MK_1,
+  MMVAE_GEMM_B16_MN_1,
+  MMVAE_GEMM_B16_KK_2,
+  MMVAE_GEMM_B16_KN_2,
+  MMVAE_GEMM_B16_MK_2,
+  MMVAE_GEMM_B16_MN_2,
+  MMVAE_GEMM_BIG128_KK,
+  MMVAE_GEMM_BIG128_KN,
+  MMVAE_GEMM_BIG128_MK,
+  MMVAE_GEMM_BIG128_MN,
+  MMVAE_GEMM_BIG64_KK,
+  MMVAE_GEMM_BIG64_KN,
+  MMVAE_GEMM_BIG64_MK,
+  MMVAE_GEMM_BIG64_MN,
+  MMVAE_GEMM_RSPLIT_16,
+  MMVAE_GEMM_RSPLIT_64,
+  MMVAE_GEMM_R16_16_VV,
+  MMVAE_GEMM_R16_16_VS,
+  MMVAE_GEMM_R16_16_SV,
+  MMVAE_GEMM_R16_16_SS,
+  MMVAE_GEMM_R16_64_VV,
+  MMVAE_GEMM_R16_64_VS,
+  MMVAE_GEMM_R16_64_SV,
+  MMVAE_GEMM_R16_64_SS,
+  MMVAE_GEMM_R32_16_VV,
+  MMVAE_GEMM_R32_16_VS,
+  MMVAE_GEMM_R32_16_SV,
+  MMVAE_GEMM_R32_16_SS,
+  MMVAE_GEMM_R32_64_VV,
+  MMVAE_GEMM_R32_64_VS,
+  MMVAE_GEMM_R32_64_SV,
+  MMVAE_GEMM_R32_64_SS,
+  MMVAE_GEMM_STAGED1_KK,
+  MMVAE_GEMM_STAGED1_KN,
+  MMVAE_GEMM_STAGED1_MK,
+  MMVAE_GEMM_STAGED1_MN,
+  MMVAE_GEMM_STAGED4_KK,
+  MMVAE_GEMM_STAGED4_KN,
+  MMVAE_GEMM_STAGED4_MK,
+  MMVAE_GEMM_STAGED4_MN,
+  MMVAE_GEMM_STAGED8_KK,
+  MMVAE_GEMM_STAGED8_KN,
+  MMVAE_GEMM_STAGED8_MK,
+  MMVAE_GEMM_STAGED8_MN,
+  MMVAE_GEMM_PROJ32,
+  MMVAE_GEMM_LINBWD_B16_1,
+  MMVAE_GEMM_LINBWD_B16_2,
+  MMVAE_GEMM_LINBWD_R_16_T32,
+  MMVAE_GEMM_LINBWD_R_16_T16,
+  MMVAE_GEMM_LINBWD_R_64_T32,
+  MMVAE_GEMM_LINBWD_R_64_T16,
+  MMVAE_GEMM_LINBWD_STAGED,
+  MMVAE_GEMM_LINBWD_TWO
+};
+/* THE dispatch rule of mmvae_gemm_f32, as a pure host query (no launch, no GPU needed): one of the values above, or a
+ * NEGATED error: -MMVAE_ERR_ARG for a non-positive size, -MMVAE_ERR_UNSUPPORTED for strides no kernel takes (neither sak
+ * nor sam is 1, or B is neither k-major nor sbn == 1).  has_rowsum: a_rowsum != NULL; a_al16 / b_al16: the operand pointer
+ * is 16-byte aligned.  ldc and accumulate decide one thing: splits that the call sums itself (nz > 1, accumulate !=
+ * MMVAE_ACC_DEFER) are written by mmvae_reduce_rows as M * N contiguous floats, so they need ldc == N, else
+ * -MMVAE_ERR_UNSUPPORTED (deferred partials never touch C: any ldc).  nz_out / kper_out (may be NULL):
+ * the number of reduction splits that write partials (1: straight to C) and the reduction length of one split. */
+int mmvae_gemm_path(int M, int N, int K, long sam, long sak, long sbk, long sbn, long ldc, int a_act, int b_act,
+                    int ep_mode, int accumulate, int splitk, int has_rowsum, int a_al16, int b_al16, int* nz_out,
+                    int* kper_out);
+/* ... of mmvae_linear_fwd: MMVAE_GEMM_PROJ32 or the mmvae_gemm_f32 path of (x, W).  out_al16: y and b 16-byte aligned */
+int mmvae_linear_fwd_path(int M, int N, int K, long ldx, int x_act, int ep_mode, int x_al16, int w_al16, int out_al16);
+/* ... of mmvae_linear_bwd_weight: the mmvae_gemm_f32 path of the (N x K) = dy^T act(x) problem with reduction length M and
+ * the split request the wrapper makes.  has_db: db != NULL (the row sums of dy^T) */
+int mmvae_linear_bwd_weight_path(int M, int N, int K, long ldx, int x_act, int accumulate, int has_db, int dy_al16,
+                                 int x_al16, int* nz_out, int* kper_out);
+/* ... of mmvae_linear_bwd: a MMVAE_GEMM_LINBWD_* value, or -MMVAE_ERR_ARG where the chosen grouped kernel needs an
+ * alignment the call lacks (split-bf16: dy, x, W 16-byte aligned and ldx % 4 == 0; register-operand: dy).  nz_out: the
+ * number of weight-gradient partials (= mmvae_linear_bwd_splits); kper_out: rows of the reduction per partial. */
+int mmvae_linear_bwd_path(int M, int N, int K, long ldx, int x_act, int ep_mode, int accumulate, int has_db, int dy_al16,
+                          int x_al16, int w_al16, int* nz_out, int* kper_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Encoder heads: VaeComponent.process_output, models/encoders.py:49-54

@@ -471,8 +471,8 @@ __global__ __launch_bounds__(512) void rgemm_grouped_kernel(GemmGroup grp) {
   }
 }
 
-static inline bool rgemm_aligned(const float* p, long row_stride, int K) {
-  return ((uintptr_t)p & 15) == 0 && (row_stride & 3) == 0 && (K & 3) == 0 && K >= 4;
+static inline bool rgemm_aligned(bool al16, long row_stride, int K) {
+  return al16 && (row_stride & 3) == 0 && (K & 3) == 0 && K >= 4;
 }
 static inline int rgemm_depth(int K) { return K >= 384 ? 64 : 16; }
 static bool rgemm_enabled() { return true; }
@@ -684,35 +684,25 @@ __global__ __launch_bounds__(256) void gemm_big_kernel(GemmArgs g) {
 }
 
 // shapes the large-tile kernel takes: enough 128-row tiles to put >= 2 workgroups on every CU, float4-loadable
-// operands.  Returns the N tile (128 | 64) or 0.
-static inline int gemm_big_bn(const GemmArgs& g, int nz, bool ak, bool bk_major) {
-  if (g.K < 16 || g.N < 32 || g.M < 128) return 0;
-  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  if (!al16(g.A) || !al16(g.B)) return 0;
-  if (ak) { if ((g.sam & 3) || (g.K & 3) || (g.kper & 3)) return 0; }
-  else { if ((g.sak & 3) || (g.M & 3)) return 0; }
-  if (bk_major) { if ((g.sbn & 3) || (g.K & 3) || (g.kper & 3)) return 0; }
-  else { if ((g.sbk & 3) || (g.N & 3)) return 0; }
-  const long rows = (g.M + 127) / 128;
-  if (rows * ((g.N + 127) / 128) * nz >= 512 && g.N > 64) return 128;
-  if (rows * ((g.N + 63) / 64) * nz >= 384) return 64;
+// operands (a16 / b16: the operand pointer is 16-byte aligned).  Returns the N tile (128 | 64) or 0.
+static inline int gemm_big_bn_shape(int M, int N, int K, long sam, long sak, long sbk, long sbn, int kper, int nz, bool ak,
+                                    bool bk_major, bool a16, bool b16) {
+  if (K < 16 || N < 32 || M < 128) return 0;
+  if (!a16 || !b16) return 0;
+  if (ak) { if ((sam & 3) || (K & 3) || (kper & 3)) return 0; }
+  else { if ((sak & 3) || (M & 3)) return 0; }
+  if (bk_major) { if ((sbn & 3) || (K & 3) || (kper & 3)) return 0; }
+  else { if ((sbk & 3) || (N & 3)) return 0; }
+  const long rows = (M + 127) / 128;
+  if (rows * ((N + 127) / 128) * nz >= 512 && N > 64) return 128;
+  if (rows * ((N + 63) / 64) * nz >= 384) return 64;
   // (A 64 x 64-tile variant for mid-size problems past the register-operand regime was measured in round 3 and removed in
   // round 4: 1000 x 512 x 512 took 34 us on it against 17.7 us on the register-operand kernel.)
   return 0;
 }
-static void gemm_big_launch(const GemmArgs& g, int bn, int nz, bool ak, bool bk_major, hipStream_t st) {
-  constexpr int bm = 128;
-  const dim3 grid((g.N + bn - 1) / bn, (g.M + bm - 1) / bm, nz);
-#define GB_LAUNCH(BM, BN)                                                                                   \
-  do {                                                                                                      \
-    if (ak && bk_major) hipLaunchKernelGGL((gemm_big_kernel<BM, BN, true, true>), grid, dim3(256), 0, st, g);   \
-    else if (ak) hipLaunchKernelGGL((gemm_big_kernel<BM, BN, true, false>), grid, dim3(256), 0, st, g);         \
-    else if (!bk_major) hipLaunchKernelGGL((gemm_big_kernel<BM, BN, false, false>), grid, dim3(256), 0, st, g); \
-    else hipLaunchKernelGGL((gemm_big_kernel<BM, BN, false, true>), grid, dim3(256), 0, st, g);                 \
-  } while (0)
-  if (bn == 128) GB_LAUNCH(128, 128);
-  else GB_LAUNCH(128, 64);
-#undef GB_LAUNCH
+static inline bool gemm_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline int gemm_big_bn(const GemmArgs& g, int nz, bool ak, bool bk_major) {
+  return gemm_big_bn_shape(g.M, g.N, g.K, g.sam, g.sak, g.sbk, g.sbn, g.kper, nz, ak, bk_major, gemm_al16(g.A), gemm_al16(g.B));
 }
 
 // tiling variant, reduction length per split and number of splits actually used for (M, N, K, requested splitk)
@@ -736,6 +726,79 @@ extern "C" size_t mmvae_gemm_ws_floats(int M, int N, int splitk) {
   return splitk > 1 ? (size_t)splitk * ((size_t)M * N + M) : 0;
 }
 
+// ---- THE dispatch rule ----------------------------------------------------------------------------------------------
+// mmvae_gemm_f32, mmvae_linear_fwd and mmvae_linear_bwd switch on the code these functions return and on nothing else, so
+// the exported queries (mmvae_gemm_path, mmvae_linear_fwd_path, mmvae_linear_bwd_path) cannot drift from what runs.  The
+// codes of a family are consecutive in include/mmvae_hip.h; inside a family the operand forms are ordered (A, B) =
+// (true, true), (true, false), (false, true), (false, false): orientation KK, KN, MK, MN or loads VV, VS, SV, SS.
+static inline int gemm_form(bool a, bool b) { return (a ? 0 : 2) + (b ? 0 : 1); }
+#define GEMM_FORM_CASES(BASE, L)          \
+  case (BASE) + 0: L(true, true); break;  \
+  case (BASE) + 1: L(true, false); break; \
+  case (BASE) + 2: L(false, true); break; \
+  case (BASE) + 3: L(false, false); break
+
+static int gemm_path_plan(int M, int N, int K, long sam, long sak, long sbk, long sbn, long ldc, int a_act, int b_act,
+                          int ep_mode, int accumulate, int splitk, bool has_rs, bool a16, bool b16, int* nz_out, int* kper_out) {
+  if (M <= 0 || N <= 0 || K <= 0) return -MMVAE_ERR_ARG;
+  if (splitk < 1) splitk = 1;
+  int nz = 1, kper = K;
+  auto done = [&](int path) {
+    if (nz_out) *nz_out = nz;
+    if (kper_out) *kper_out = kper;
+    return path;
+  };
+  // wide layers at large row counts: the LDS-tiled split-bf16 kernel (gemm_b16.inc); forward and data gradient
+  if (splitk == 1 && !has_rs && ep_mode != MMVAE_EP_GELU && gb_act_ok(a_act) && gb_act_ok(b_act) && gb_shape_ok(M, N, K) &&
+      M <= G16_MAX_ROWS) {
+    const bool akc = sak == 1, bkc = (sbk == 1 && sbn != 1);
+    const long lda = akc ? sam : sak, ldb = bkc ? sbn : sbk;
+    const bool a_ok = (akc || sam == 1) && a16 && (lda & 3) == 0 && (akc || (M & 3) == 0);
+    const bool b_ok = (bkc || sbn == 1) && b16 && (ldb & 3) == 0;
+    if (a_ok && b_ok) {
+      // fewer tiles than CUs: two k-groups per tile (twice the waves, half the chain)
+      const long tiles = (long)((N + G16_TM - 1) / G16_TM) * ((M + G16_TM - 1) / G16_TM);
+      const bool ks2 = tiles < 256 && K >= 4 * G16_BK;
+      return done(MMVAE_GEMM_B16_KK_1 + (ks2 ? 4 : 0) + gemm_form(akc, bkc));
+    }
+  }
+  // Tiling choice (all that matters at batch 128 is the length of the serial load -> MFMA chain per workgroup):
+  //   K <= 128 and many rows : 128x32 tiles, one stage, no cross-wave reduction            (KSPLIT 1)
+  //   K >= 384, few tiles    : 32x32 tile, 8 waves x 256-deep stages (half the serial stages)  (KSPLIT 8)
+  //   otherwise              : 32x32 tile, 4 waves x 128-deep stages                       (KSPLIT 4)
+  int variant;
+  nz = gemm_split_plan(M, N, K, splitk, &variant, &kper);
+  // operand orientation is a template argument (per-slot address stride folds to a constant): the three forms a
+  // Linear layer needs are  fwd: A k-major, B k-major;  dgrad: A k-major, B n-major;  wgrad: A m-major, B n-major
+  const bool ak = sak == 1, bk_major = (sbk == 1 && sbn != 1);
+  if ((!ak && sam != 1) || (!bk_major && sbn != 1)) return done(-MMVAE_ERR_UNSUPPORTED);
+  // partials that the call sums itself go through mmvae_reduce_rows, which writes C as M * N contiguous floats
+  if (nz > 1 && accumulate != MMVAE_ACC_DEFER && ldc != N) return done(-MMVAE_ERR_UNSUPPORTED);
+  const long tiles32 = (long)((M + 31) / 32) * ((N + 31) / 32);
+  // large problems: 128 x 128 | 64 tiles, float4 staging (same kper / partial layout)
+  if (const int bn = gemm_big_bn_shape(M, N, K, sam, sak, sbk, sbn, kper, nz, ak, bk_major, a16, b16))
+    return done((bn == 128 ? MMVAE_GEMM_BIG128_KK : MMVAE_GEMM_BIG64_KK) + gemm_form(ak, bk_major));
+  // split reduction over workgroups with few output tiles (the text towers' (L*N)-row weight gradients: 162 x 54
+  // outputs, 4096 rows): same kper / partial layout as the staged kernel, register-operand body
+  if (nz > 1 && tiles32 <= 64 && kper <= 1024 && !ak && !bk_major)
+    return done(rgemm_depth(kper) == 64 ? MMVAE_GEMM_RSPLIT_64 : MMVAE_GEMM_RSPLIT_16);
+  // few tiles, short reduction: register-operand kernel (no LDS staging)
+  if (splitk == 1 && tiles32 <= 1024 && K <= 1024) {
+    // k-contiguous operands that are not float4-aligned take the strided (dword) loads with a k stride of 1
+    const bool ak4 = ak && rgemm_aligned(a16, sam, K), bk4 = bk_major && rgemm_aligned(b16, sbn, K);
+    kper = K;   // (one split: nz == 1)
+    const int base = (tiles32 <= 128 && !has_rs) ? MMVAE_GEMM_R16_16_VV : MMVAE_GEMM_R32_16_VV;   // 16 x 16 tiles
+    return done(base + (rgemm_depth(K) == 64 ? 4 : 0) + gemm_form(ak4, bk4));
+  }
+  return done(MMVAE_GEMM_STAGED1_KK + 4 * (variant == 1 ? 0 : variant == 4 ? 1 : 2) + gemm_form(ak, bk_major));
+}
+extern "C" int mmvae_gemm_path(int M, int N, int K, long sam, long sak, long sbk, long sbn, long ldc, int a_act, int b_act,
+                               int ep_mode, int accumulate, int splitk, int has_rowsum, int a_al16, int b_al16, int* nz_out,
+                               int* kper_out) {
+  return gemm_path_plan(M, N, K, sam, sak, sbk, sbn, ldc, a_act, b_act, ep_mode, accumulate, splitk, has_rowsum != 0, a_al16 != 0, b_al16 != 0,
+                        nz_out, kper_out);
+}
+
 extern "C" int mmvae_gemm_f32(const float* A, const float* Bm, const float* bias, const float* aux, float* C,
                               float* a_rowsum, float* ws, int M, int N, int K, long sam, long sak, long sbk, long sbn,
                               long ldc, int a_act, int b_act, int ep_mode, int accumulate, int splitk,
@@ -744,127 +807,66 @@ extern "C" int mmvae_gemm_f32(const float* A, const float* Bm, const float* bias
   if (splitk < 1) splitk = 1;
   if (splitk > 1 && (!ws || bias || ep_mode != MMVAE_EP_NONE)) return MMVAE_ERR_ARG;
   if (ep_reads_aux(ep_mode) && !aux) return MMVAE_ERR_ARG;
+  int nz = 1, kper = K;
+  const int path = gemm_path_plan(M, N, K, sam, sak, sbk, sbn, ldc, a_act, b_act, ep_mode, accumulate, splitk, a_rowsum != nullptr,
+                                  gemm_al16(A), gemm_al16(Bm), &nz, &kper);
+  if (nz > 1 && !ws) return MMVAE_ERR_ARG;
+  if (path < 0) return -path;
   GemmArgs g;
   g.A = A; g.B = Bm; g.bias = bias; g.aux = const_cast<float*>(aux); g.C = C; g.a_rowsum = a_rowsum; g.ws = ws;
   g.M = M; g.N = N; g.K = K; g.sam = sam; g.sak = sak; g.sbk = sbk; g.sbn = sbn; g.ldc = ldc;
   g.a_act = a_act; g.b_act = b_act; g.ep = ep_mode;
   g.accumulate = accumulate ? 1 : 0;   // DEFER without a split == plain accumulation
-  // wide layers at large row counts: the LDS-tiled split-bf16 kernel (gemm_b16.inc); forward and data gradient
-  if (splitk == 1 && !a_rowsum && ep_mode != MMVAE_EP_GELU && gb_act_ok(a_act) && gb_act_ok(b_act) && gb_shape_ok(M, N, K) &&
-      M <= G16_MAX_ROWS) {
-    const bool akc = sak == 1, bkc = (sbk == 1 && sbn != 1);
-    const long lda = akc ? sam : sak, ldb = bkc ? sbn : sbk;
-    const bool a_ok = (akc || sam == 1) && gb_al16(A) && (lda & 3) == 0 && (akc || (M & 3) == 0);
-    const bool b_ok = (bkc || sbn == 1) && gb_al16(Bm) && (ldb & 3) == 0;
-    if (a_ok && b_ok && (!akc || !bkc || true)) {
-      GbArgs b{A, Bm, bias, aux, C, nullptr, nullptr, M, N, K, lda, ldb, ldc, a_act, b_act, ep_mode, g.accumulate, K};
-      const dim3 grid((N + G16_TM - 1) / G16_TM, (M + G16_TM - 1) / G16_TM, 1);
-      hipStream_t st = (hipStream_t)stream;
-      // fewer tiles than CUs: two k-groups per tile (twice the waves, half the chain)
-      const bool ks2 = (long)grid.x * grid.y < 256 && K >= 4 * G16_BK;
-#define G16_LAUNCH(AK_, BK_)                                                                                   \
-  do {                                                                                                         \
-    if (ks2) hipLaunchKernelGGL((gemm_b16_kernel<AK_, BK_, 2>), grid, dim3(512), 0, st, b);                     \
-    else hipLaunchKernelGGL((gemm_b16_kernel<AK_, BK_, 1>), grid, dim3(256), 0, st, b);                         \
-  } while (0)
-      if (akc && bkc) G16_LAUNCH(true, true);
-      else if (akc) G16_LAUNCH(true, false);
-      else if (bkc) G16_LAUNCH(false, true);
-      else G16_LAUNCH(false, false);
-#undef G16_LAUNCH
-      return mmvae_launch_status();
-    }
-  }
-  const int ntn = (N + 31) / 32;
-  // Tiling choice (all that matters at batch 128 is the length of the serial load -> MFMA chain per workgroup):
-  //   K <= 128 and many rows : 128x32 tiles, one stage, no cross-wave reduction            (KSPLIT 1)
-  //   K >= 384, few tiles    : 32x32 tile, 8 waves x 256-deep stages (half the serial stages)  (KSPLIT 8)
-  //   otherwise              : 32x32 tile, 4 waves x 128-deep stages                       (KSPLIT 4)
-  const long tiles128 = (long)((M + 127) / 128) * ntn, tiles32 = (long)((M + 31) / 32) * ntn;
-  int variant, kper;
-  const int nz = gemm_split_plan(M, N, K, splitk, &variant, &kper);
   g.kper = kper;
-  if (nz > 1 && !ws) return MMVAE_ERR_ARG;
+  // the split-bf16 kernel's view of the same call: leading dimension of each operand along its non-contiguous axis
+  const GbArgs b{A, Bm, bias, aux, C, nullptr, nullptr, M, N, K, sak == 1 ? sam : sak, (sbk == 1 && sbn != 1) ? sbn : sbk, ldc,
+                 a_act, b_act, ep_mode, g.accumulate, K};
   hipStream_t st = (hipStream_t)stream;
-  // operand orientation is a template argument (per-slot address stride folds to a constant): the three forms a
-  // Linear layer needs are  fwd: A k-major, B k-major;  dgrad: A k-major, B n-major;  wgrad: A m-major, B n-major
-  const bool ak = sak == 1, bk_major = (sbk == 1 && sbn != 1);
-  if (!ak && sam != 1) return MMVAE_ERR_UNSUPPORTED;
-  if (!bk_major && sbn != 1) return MMVAE_ERR_UNSUPPORTED;
-  // large problems: 128 x 128 | 64 tiles, float4 staging (same kper / partial layout)
-  if (const int big_bn = gemm_big_bn(g, nz, ak, bk_major)) {
-    gemm_big_launch(g, big_bn, nz, ak, bk_major, st);
-    int rc = mmvae_launch_status();
-    if (rc) return rc;
-    if (nz > 1 && accumulate != MMVAE_ACC_DEFER) {
-      rc = mmvae_reduce_rows(ws, C, nz, (long)M * N, (long)M * N, accumulate, stream);
-      if (rc) return rc;
-      if (a_rowsum) rc = mmvae_reduce_rows(ws + (size_t)nz * M * N, a_rowsum, nz, M, M, accumulate, stream);
-    }
-    return rc;
+  const int ntn = (N + 31) / 32, ntm = (M + 31) / 32;
+  const dim3 grid_b16((N + G16_TM - 1) / G16_TM, (M + G16_TM - 1) / G16_TM, 1);
+  const dim3 grid_big128((N + 127) / 128, (M + 127) / 128, nz), grid_big64((N + 63) / 64, (M + 127) / 128, nz);
+  const dim3 grid16((N + 15) / 16, (M + 15) / 16, 1), grid32(ntn, ntm, nz), grid128(ntn, (M + 127) / 128, nz);
+#define L_B16_1(AK_, BK_) hipLaunchKernelGGL((gemm_b16_kernel<AK_, BK_, 1>), grid_b16, dim3(256), 0, st, b)
+#define L_B16_2(AK_, BK_) hipLaunchKernelGGL((gemm_b16_kernel<AK_, BK_, 2>), grid_b16, dim3(512), 0, st, b)
+#define L_BIG128(AK_, BK_) hipLaunchKernelGGL((gemm_big_kernel<128, 128, AK_, BK_>), grid_big128, dim3(256), 0, st, g)
+#define L_BIG64(AK_, BK_) hipLaunchKernelGGL((gemm_big_kernel<128, 64, AK_, BK_>), grid_big64, dim3(256), 0, st, g)
+#define L_R16_16(AK_, BK_) hipLaunchKernelGGL((rgemm16_kernel<16, AK_, BK_>), grid16, dim3(512), 0, st, g)
+#define L_R16_64(AK_, BK_) hipLaunchKernelGGL((rgemm16_kernel<64, AK_, BK_>), grid16, dim3(512), 0, st, g)
+#define L_R32_16(AK_, BK_) hipLaunchKernelGGL((rgemm_kernel<16, AK_, BK_>), grid32, dim3(512), 0, st, g)
+#define L_R32_64(AK_, BK_) hipLaunchKernelGGL((rgemm_kernel<64, AK_, BK_>), grid32, dim3(512), 0, st, g)
+#define L_STAGED1(AK_, BK_) hipLaunchKernelGGL((gemm_kernel<1, AK_, BK_>), grid128, dim3(256), 0, st, g)
+#define L_STAGED4(AK_, BK_) hipLaunchKernelGGL((gemm_kernel<4, AK_, BK_>), grid32, dim3(256), 0, st, g)
+#define L_STAGED8(AK_, BK_) hipLaunchKernelGGL((gemm_kernel<8, AK_, BK_>), grid32, dim3(512), 0, st, g)
+  switch (path) {
+    GEMM_FORM_CASES(MMVAE_GEMM_B16_KK_1, L_B16_1);
+    GEMM_FORM_CASES(MMVAE_GEMM_B16_KK_2, L_B16_2);
+    GEMM_FORM_CASES(MMVAE_GEMM_BIG128_KK, L_BIG128);
+    GEMM_FORM_CASES(MMVAE_GEMM_BIG64_KK, L_BIG64);
+    case MMVAE_GEMM_RSPLIT_16: L_R32_16(false, false); break;
+    case MMVAE_GEMM_RSPLIT_64: L_R32_64(false, false); break;
+    GEMM_FORM_CASES(MMVAE_GEMM_R16_16_VV, L_R16_16);
+    GEMM_FORM_CASES(MMVAE_GEMM_R16_64_VV, L_R16_64);
+    GEMM_FORM_CASES(MMVAE_GEMM_R32_16_VV, L_R32_16);
+    GEMM_FORM_CASES(MMVAE_GEMM_R32_64_VV, L_R32_64);
+    GEMM_FORM_CASES(MMVAE_GEMM_STAGED1_KK, L_STAGED1);
+    GEMM_FORM_CASES(MMVAE_GEMM_STAGED4_KK, L_STAGED4);
+    GEMM_FORM_CASES(MMVAE_GEMM_STAGED8_KK, L_STAGED8);
+    default: return MMVAE_ERR_UNSUPPORTED;
   }
-  // split reduction over workgroups with few output tiles (the text towers' (L*N)-row weight gradients: 162 x 54
-  // outputs, 4096 rows): same kper / partial layout as the staged kernel, register-operand body
-  const bool rsplit = true;
-  if (rgemm_enabled() && rsplit && nz > 1 && tiles32 <= 64 && kper <= 1024 && !ak && !bk_major) {
-    const dim3 rgrid(ntn, (M + 31) / 32, nz);
-    if (rgemm_depth(kper) == 64) hipLaunchKernelGGL((rgemm_kernel<64, false, false>), rgrid, dim3(512), 0, st, g);
-    else hipLaunchKernelGGL((rgemm_kernel<16, false, false>), rgrid, dim3(512), 0, st, g);
-    int rc = mmvae_launch_status();
-    if (rc) return rc;
-    if (accumulate != MMVAE_ACC_DEFER) {
-      rc = mmvae_reduce_rows(ws, C, nz, (long)M * N, (long)M * N, accumulate, stream);
-      if (rc) return rc;
-      if (a_rowsum) rc = mmvae_reduce_rows(ws + (size_t)nz * M * N, a_rowsum, nz, M, M, accumulate, stream);
-    }
-    return rc;
-  }
-  // few tiles, short reduction: register-operand kernel (no LDS staging)
-  if (rgemm_enabled() && splitk == 1 && tiles32 <= 1024 && K <= 1024) {
-    // k-contiguous operands that are not float4-aligned take the strided (dword) loads with a k stride of 1
-    const bool ak4 = ak && rgemm_aligned(A, sam, K), bk4 = bk_major && rgemm_aligned(Bm, sbn, K);
-    g.kper = K;
-    const dim3 rgrid(ntn, (M + 31) / 32, 1);
-#define RGEMM_LAUNCH(D)                                                                                  \
-  do {                                                                                                   \
-    if (ak4 && bk4) hipLaunchKernelGGL((rgemm_kernel<D, true, true>), rgrid, dim3(512), 0, st, g);        \
-    else if (ak4) hipLaunchKernelGGL((rgemm_kernel<D, true, false>), rgrid, dim3(512), 0, st, g);         \
-    else if (!bk4) hipLaunchKernelGGL((rgemm_kernel<D, false, false>), rgrid, dim3(512), 0, st, g);       \
-    else hipLaunchKernelGGL((rgemm_kernel<D, false, true>), rgrid, dim3(512), 0, st, g);                  \
-  } while (0)
-    if (tiles32 <= 128 && !a_rowsum) {   // 16 x 16 tiles
-      const dim3 grid16((N + 15) / 16, (M + 15) / 16, 1);
-#define RGEMM16_LAUNCH(D)                                                                                   \
-  do {                                                                                                      \
-    if (ak4 && bk4) hipLaunchKernelGGL((rgemm16_kernel<D, true, true>), grid16, dim3(512), 0, st, g);        \
-    else if (ak4) hipLaunchKernelGGL((rgemm16_kernel<D, true, false>), grid16, dim3(512), 0, st, g);         \
-    else if (!bk4) hipLaunchKernelGGL((rgemm16_kernel<D, false, false>), grid16, dim3(512), 0, st, g);       \
-    else hipLaunchKernelGGL((rgemm16_kernel<D, false, true>), grid16, dim3(512), 0, st, g);                  \
-  } while (0)
-      if (rgemm_depth(K) == 64) RGEMM16_LAUNCH(64);
-      else RGEMM16_LAUNCH(16);
-#undef RGEMM16_LAUNCH
-      return mmvae_launch_status();
-    }
-    if (rgemm_depth(K) == 64) RGEMM_LAUNCH(64);
-    else RGEMM_LAUNCH(16);
-#undef RGEMM_LAUNCH
-    return mmvae_launch_status();
-  }
-  const dim3 grid(ntn, variant == 1 ? (M + 127) / 128 : (M + 31) / 32, nz), block(variant == 8 ? 512 : 256);
-#define GEMM_LAUNCH(V)                                                                            \
-  do {                                                                                            \
-    if (ak && bk_major) hipLaunchKernelGGL((gemm_kernel<V, true, true>), grid, block, 0, st, g);   \
-    else if (ak) hipLaunchKernelGGL((gemm_kernel<V, true, false>), grid, block, 0, st, g);         \
-    else if (!bk_major) hipLaunchKernelGGL((gemm_kernel<V, false, false>), grid, block, 0, st, g); \
-    else hipLaunchKernelGGL((gemm_kernel<V, false, true>), grid, block, 0, st, g);                 \
-  } while (0)
-  if (variant == 1) GEMM_LAUNCH(1);
-  else if (variant == 8) GEMM_LAUNCH(8);
-  else GEMM_LAUNCH(4);
-#undef GEMM_LAUNCH
+#undef L_B16_1
+#undef L_B16_2
+#undef L_BIG128
+#undef L_BIG64
+#undef L_R16_16
+#undef L_R16_64
+#undef L_R32_16
+#undef L_R32_64
+#undef L_STAGED1
+#undef L_STAGED4
+#undef L_STAGED8
   int rc = mmvae_launch_status();
   if (rc) return rc;
+  // split reduction: the partials in ws ([z][M][N], then [z][M] row sums) are summed here unless the caller defers it
   if (nz > 1 && accumulate != MMVAE_ACC_DEFER) {
     rc = mmvae_reduce_rows(ws, C, nz, (long)M * N, (long)M * N, accumulate, stream);
     if (rc) return rc;
@@ -875,13 +877,22 @@ extern "C" int mmvae_gemm_f32(const float* A, const float* Bm, const float* bias
 
 // ---- nn.Linear wrappers ---------------------------------------------------------------------------
 int mmvae_proj32_fwd_launch(const float* x, const float* w, const float* b, float* y, int M, int N, mmvae_stream_t stream);   // ffn.hip
-extern "C" int mmvae_linear_fwd(const float* x, const float* w, const float* b, float* aux, float* y, int M, int N,
-                                int K, long ldx, int x_act, int ep_mode, mmvae_stream_t stream) {
+extern "C" int mmvae_linear_fwd_path(int M, int N, int K, long ldx, int x_act, int ep_mode, int x_al16, int w_al16,
+                                     int out_al16) {
   // many rows of a 32-wide input into 32 .. 128 outputs (the action towers' QKV projection): one wave per 32 rows
   if (K == 32 && ldx == 32 && M >= 1024 && N >= 32 && N <= 128 && (N & 31) == 0 && x_act == MMVAE_ACT_NONE &&
-      ep_mode == MMVAE_EP_NONE && x && w && y && ((((uintptr_t)x | (uintptr_t)w | (uintptr_t)y | (uintptr_t)b) & 15) == 0))
-    return mmvae_proj32_fwd_launch(x, w, b, y, M, N, stream);
+      ep_mode == MMVAE_EP_NONE && x_al16 && w_al16 && out_al16)
+    return MMVAE_GEMM_PROJ32;
   // y[m,n] = sum_k x[m,k] w[n,k]: A = x (sam = ldx, sak = 1), B(k,n) = w[n*K + k]
+  return gemm_path_plan(M, N, K, ldx, 1, 1, K, N, x_act, MMVAE_ACT_NONE, ep_mode, 0, 1, false, x_al16 != 0, w_al16 != 0, nullptr,
+                        nullptr);
+}
+extern "C" int mmvae_linear_fwd(const float* x, const float* w, const float* b, float* aux, float* y, int M, int N,
+                                int K, long ldx, int x_act, int ep_mode, mmvae_stream_t stream) {
+  MMVAE_CHECK_ARG(x && w && y && M > 0 && N > 0 && K > 0);
+  if (mmvae_linear_fwd_path(M, N, K, ldx, x_act, ep_mode, gemm_al16(x), gemm_al16(w), gemm_al16(y) && gemm_al16(b)) ==
+      MMVAE_GEMM_PROJ32)
+    return mmvae_proj32_fwd_launch(x, w, b, y, M, N, stream);
   return mmvae_gemm_f32(x, w, b, aux, y, nullptr, nullptr, M, N, K, ldx, 1, 1, K, N, x_act, MMVAE_ACT_NONE, ep_mode, 0,
                         1, stream);
 }
@@ -911,17 +922,19 @@ static int wgrad_splitk(int M, int N, int K) {
   return s;
 }
 extern "C" int mmvae_linear_bwd_weight_splits(int M, int N, int K) {
-  // mirrors the kper rounding of mmvae_gemm_f32 for the (N x K) = dy^T x problem with reduction length M
-  int sk = wgrad_splitk(M, N, K);
-  // gemm problem: rows N, cols K, reduction M
-  const long tiles128 = (long)((N + 127) / 128) * ((K + 31) / 32), tiles32 = (long)((N + 31) / 32) * ((K + 31) / 32);
-  int variant = 4;
-  if (tiles128 >= 256) variant = 1;
-  else if (M >= 384 && tiles32 <= 512 && sk == 1) variant = 8;
-  const int bk = variant == 1 ? GEMM_BK1 : 32 * variant;
-  int kper = (M + sk - 1) / sk;
-  kper = (kper + bk - 1) / bk * bk;
-  return (M + kper - 1) / kper;
+  // the split plan of mmvae_gemm_f32 itself for the (N x K) = dy^T x problem with reduction length M
+  return gemm_split_plan(N, K, M, wgrad_splitk(M, N, K), nullptr, nullptr);
+}
+// dw[n,k] = sum_m dy[m,n] act(x[m,k]): "A"(n,m) = dy[m*N + n] (sam = 1, sak = N), "B"(m,k) = x[m*ldx + k];
+// db[n] = row sum of "A".  The one place that states the weight gradient as a mmvae_gemm_f32 problem.
+static int wgrad_path_plan(int M, int N, int K, long ldx, int x_act, bool has_db, bool dy16, bool x16, int* nz_out, int* kper_out) {
+  return gemm_path_plan(N, K, M, 1, N, ldx, 1, K, MMVAE_ACT_NONE, x_act, MMVAE_EP_NONE, 0, wgrad_splitk(M, N, K), has_db, dy16, x16,
+                        nz_out, kper_out);
+}
+extern "C" int mmvae_linear_bwd_weight_path(int M, int N, int K, long ldx, int x_act, int accumulate, int has_db, int dy_al16,
+                                            int x_al16, int* nz_out, int* kper_out) {
+  (void)accumulate;   // part of the call, decides nothing
+  return wgrad_path_plan(M, N, K, ldx, x_act, has_db != 0, dy_al16 != 0, x_al16 != 0, nz_out, kper_out);
 }
 extern "C" size_t mmvae_linear_bwd_weight_ws_floats(int M, int N, int K) {
   return mmvae_gemm_ws_floats(N, K, wgrad_splitk(M, N, K));
@@ -1027,112 +1040,126 @@ constexpr int RGEMM_BWD_MAX_M = 1024;
 static inline bool linear_bwd_rgemm(int M, int N) { return rgemm_enabled() && M <= RGEMM_BWD_MAX_M && (N & 3) == 0 && N >= 4; }
 // the tiled split-bf16 grouped launch (gemm_b16.inc): data gradient (M x K, reduction N) + weight gradient (N x K, reduction M)
 static inline bool linear_bwd_b16(int M, int N, int K) { return gb_shape_ok(M, K, N) && M <= G16_MAX_ROWS; }
+// THE dispatch rule of mmvae_linear_bwd (see gemm_path_plan).  nz / kper: splits of the weight gradient's reduction over M
+//   problem 0 (data):   C[M,K] = dy[M,N] W[N,K]            reduction N
+//   problem 1 (weight): C[N,K] = dy^T[N,M] act(x)[M,K]     reduction M, split over workgroups
+static int linear_bwd_plan(int M, int N, int K, long ldx, int x_act, bool has_db, bool dy16, bool x16, bool w16, int* nz_out,
+                           int* kper_out) {
+  if (M <= 0 || N <= 0 || K <= 0) return -MMVAE_ERR_ARG;
+  int nz = 1, kper = M;
+  auto done = [&](int path) {
+    if (nz_out) *nz_out = nz;
+    if (kper_out) *kper_out = kper;
+    return path;
+  };
+  if (linear_bwd_b16(M, N, K)) {
+    if (!dy16 || !x16 || !w16 || (ldx & 3) != 0) return -MMVAE_ERR_ARG;   // float4 staging
+    kper = gb_wgrad_kper(M, gb_wgrad_splits(M, N, K));
+    nz = (M + kper - 1) / kper;
+    const long tk = (K + G16_TM - 1) / G16_TM, tm = (M + G16_TM - 1) / G16_TM, tn = (N + G16_TM - 1) / G16_TM;
+    const bool ks2 = tk * tm + tk * tn * nz < 256 && M >= 4 * G16_BK && N >= 4 * G16_BK;
+    return done(ks2 ? MMVAE_GEMM_LINBWD_B16_2 : MMVAE_GEMM_LINBWD_B16_1);
+  }
+  if (linear_bwd_rgemm(M, N)) {
+    if (!rgemm_aligned(dy16, N, N)) return -MMVAE_ERR_ARG;   // this regime needs a 16-byte aligned dy
+    const bool t16 = (long)((M + 31) / 32) * ((K + 31) / 32) <= 128;   // data gradient on 16 x 16 tiles
+    return done(MMVAE_GEMM_LINBWD_R_16_T32 + (rgemm_depth(N) == 64 ? 2 : 0) + (t16 ? 1 : 0));
+  }
+  // the staged grouped kernel is the 4-wave 32 x 32 tiling: both problems must want it
+  // (a 512-deep data gradient alone prefers the 8-wave tiling, but one grouped launch beats two: +4 % on the step)
+  const bool d_ok = (long)((M + 127) / 128) * ((K + 31) / 32) < 256;
+  const int sk = wgrad_splitk(M, N, K);
+  int variant;
+  nz = gemm_split_plan(N, K, M, sk, &variant, &kper);
+  if (d_ok && variant == 4) return done(MMVAE_GEMM_LINBWD_STAGED);
+  // two launches: the weight gradient's splits are whatever mmvae_gemm_f32 gives that problem
+  wgrad_path_plan(M, N, K, ldx, x_act, has_db, dy16, x16, &nz, &kper);
+  return done(MMVAE_GEMM_LINBWD_TWO);
+}
+extern "C" int mmvae_linear_bwd_path(int M, int N, int K, long ldx, int x_act, int ep_mode, int accumulate, int has_db,
+                                     int dy_al16, int x_al16, int w_al16, int* nz_out, int* kper_out) {
+  (void)ep_mode; (void)accumulate;   // part of the call, decide nothing
+  return linear_bwd_plan(M, N, K, ldx, x_act, has_db != 0, dy_al16 != 0, x_al16 != 0, w_al16 != 0, nz_out, kper_out);
+}
+extern "C" int mmvae_linear_bwd_splits(int M, int N, int K) {
+  int nz = 1;   // (no pointer, no ldx: the plan of aligned operands with ldx = K; the split count depends on neither)
+  const int path = linear_bwd_plan(M, N, K, (long)K, MMVAE_ACT_NONE, true, true, true, true, &nz, nullptr);
+  return path < 0 ? 1 : nz;
+}
 extern "C" size_t mmvae_linear_bwd_ws_floats(int M, int N, int K) {
   if (linear_bwd_b16(M, N, K)) {
-    const int nz = gb_wgrad_nz(M, N, K);
+    const int nz = mmvae_linear_bwd_splits(M, N, K);
     return nz > 1 ? (size_t)nz * ((size_t)N * K + N) : 0;
   }
   return linear_bwd_rgemm(M, N) ? 0 : mmvae_linear_bwd_weight_ws_floats(M, N, K);
-}
-extern "C" int mmvae_linear_bwd_splits(int M, int N, int K) {
-  if (linear_bwd_b16(M, N, K)) return gb_wgrad_nz(M, N, K);
-  return linear_bwd_rgemm(M, N) ? 1 : mmvae_linear_bwd_weight_splits(M, N, K);
 }
 extern "C" int mmvae_linear_bwd(const float* dy, const float* x, const float* w, const float* aux, float* dx,
                                 float* dw, float* db, float* ws, int M, int N, int K, long ldx, int x_act, int ep_mode,
                                 int accumulate, mmvae_stream_t stream) {
   MMVAE_CHECK_ARG(dy && x && w && dx && dw && M > 0 && N > 0 && K > 0);
   if (ep_reads_aux(ep_mode) && !aux) return MMVAE_ERR_ARG;
-  // problem 0 (data):   C[M,K] = dy[M,N] W[N,K]            reduction N
-  // problem 1 (weight): C[N,K] = dy^T[N,M] act(x)[M,K]     reduction M, split over workgroups
-  if (linear_bwd_b16(M, N, K)) {
-    if (!gb_al16(dy) || !gb_al16(x) || !gb_al16(w) || (ldx & 3) != 0) return MMVAE_ERR_ARG;   // float4 staging
-    const int nz = gb_wgrad_nz(M, N, K);
-    if (nz > 1 && !ws) return MMVAE_ERR_ARG;
-    GbGroup grp;
-    grp.g[0] = GbArgs{dy, w, nullptr, aux, dx, nullptr, nullptr, M, K, N, (long)N, (long)K, (long)K, MMVAE_ACT_NONE,
-                      MMVAE_ACT_NONE, ep_mode, 0, N};
-    grp.g[1] = GbArgs{dy, x, nullptr, nullptr, dw, db, ws, N, K, M, (long)N, ldx, (long)K, MMVAE_ACT_NONE, x_act,
-                      MMVAE_EP_NONE, accumulate ? 1 : 0, gb_wgrad_kper(M, gb_wgrad_splits(M, N, K))};
-    grp.nx[0] = (K + G16_TM - 1) / G16_TM; grp.ny[0] = (M + G16_TM - 1) / G16_TM; grp.nz[0] = 1;
-    grp.nx[1] = (K + G16_TM - 1) / G16_TM; grp.ny[1] = (N + G16_TM - 1) / G16_TM; grp.nz[1] = nz;
-    grp.blk0[0] = 0;
-    grp.blk0[1] = grp.nx[0] * grp.ny[0];
-    grp.blk0[2] = grp.blk0[1] + grp.nx[1] * grp.ny[1] * nz;
-    if (grp.blk0[2] < 256 && M >= 4 * G16_BK && N >= 4 * G16_BK)
-      hipLaunchKernelGGL(gemm_b16_linear_bwd_kernel<2>, dim3(grp.blk0[2]), dim3(512), 0, (hipStream_t)stream, grp);
-    else
-      hipLaunchKernelGGL(gemm_b16_linear_bwd_kernel<1>, dim3(grp.blk0[2]), dim3(256), 0, (hipStream_t)stream, grp);
-    int rc = mmvae_launch_status();
-    if (rc) return rc;
-    if (nz > 1 && accumulate != MMVAE_ACC_DEFER) {
-      rc = mmvae_reduce_rows(ws, dw, nz, (long)N * K, (long)N * K, accumulate, stream);
+  int nz = 1, kper = M;
+  const int path = linear_bwd_plan(M, N, K, ldx, x_act, db != nullptr, gemm_al16(dy), gemm_al16(x), gemm_al16(w), &nz, &kper);
+  if (path < 0) return -path;
+  hipStream_t st = (hipStream_t)stream;
+  switch (path) {
+    case MMVAE_GEMM_LINBWD_TWO: {
+      const int rc = mmvae_linear_bwd_weight(dy, x, dw, db, ws, M, N, K, ldx, x_act, accumulate, stream);
       if (rc) return rc;
-      if (db) rc = mmvae_reduce_rows(ws + (size_t)nz * N * K, db, nz, N, N, accumulate, stream);
+      return mmvae_linear_bwd_data(dy, w, aux, dx, M, N, K, ep_mode, 0, stream);
     }
-    return rc;
+    case MMVAE_GEMM_LINBWD_B16_1:
+    case MMVAE_GEMM_LINBWD_B16_2: {
+      if (nz > 1 && !ws) return MMVAE_ERR_ARG;
+      GbGroup grp;
+      grp.g[0] = GbArgs{dy, w, nullptr, aux, dx, nullptr, nullptr, M, K, N, (long)N, (long)K, (long)K, MMVAE_ACT_NONE,
+                        MMVAE_ACT_NONE, ep_mode, 0, N};
+      grp.g[1] = GbArgs{dy, x, nullptr, nullptr, dw, db, ws, N, K, M, (long)N, ldx, (long)K, MMVAE_ACT_NONE, x_act,
+                        MMVAE_EP_NONE, accumulate ? 1 : 0, kper};
+      grp.nx[0] = (K + G16_TM - 1) / G16_TM; grp.ny[0] = (M + G16_TM - 1) / G16_TM; grp.nz[0] = 1;
+      grp.nx[1] = (K + G16_TM - 1) / G16_TM; grp.ny[1] = (N + G16_TM - 1) / G16_TM; grp.nz[1] = nz;
+      grp.blk0[0] = 0;
+      grp.blk0[1] = grp.nx[0] * grp.ny[0];
+      grp.blk0[2] = grp.blk0[1] + grp.nx[1] * grp.ny[1] * nz;
+      if (path == MMVAE_GEMM_LINBWD_B16_2)
+        hipLaunchKernelGGL(gemm_b16_linear_bwd_kernel<2>, dim3(grp.blk0[2]), dim3(512), 0, st, grp);
+      else
+        hipLaunchKernelGGL(gemm_b16_linear_bwd_kernel<1>, dim3(grp.blk0[2]), dim3(256), 0, st, grp);
+      break;
+    }
+    default: {   // the grouped fp32-MFMA kernels: register-operand bodies or the staged body
+      if (nz > 1 && !ws) return MMVAE_ERR_ARG;
+      const bool staged = path == MMVAE_GEMM_LINBWD_STAGED;
+      const bool t16 = path == MMVAE_GEMM_LINBWD_R_16_T16 || path == MMVAE_GEMM_LINBWD_R_64_T16;
+      GemmGroup grp;
+      GemmArgs& gd = grp.g[0];
+      gd.A = dy; gd.B = w; gd.bias = nullptr; gd.aux = const_cast<float*>(aux); gd.C = dx; gd.a_rowsum = nullptr; gd.ws = nullptr;
+      gd.M = M; gd.N = K; gd.K = N; gd.sam = N; gd.sak = 1; gd.sbk = K; gd.sbn = 1; gd.ldc = K;
+      gd.a_act = MMVAE_ACT_NONE; gd.b_act = MMVAE_ACT_NONE; gd.ep = ep_mode; gd.accumulate = 0;
+      gd.kper = staged ? (N + 127) / 128 * 128 : N;
+      GemmArgs& gw = grp.g[1];
+      gw.A = dy; gw.B = x; gw.bias = nullptr; gw.aux = nullptr; gw.C = dw; gw.a_rowsum = db; gw.ws = staged ? ws : nullptr;
+      gw.M = N; gw.N = K; gw.K = M; gw.sam = 1; gw.sak = N; gw.sbk = ldx; gw.sbn = 1; gw.ldc = K;
+      gw.a_act = MMVAE_ACT_NONE; gw.b_act = x_act; gw.ep = MMVAE_EP_NONE; gw.accumulate = accumulate ? 1 : 0;
+      gw.kper = kper;
+      grp.n = 2;
+      const int td = t16 ? 16 : 32;
+      grp.nx[0] = (K + td - 1) / td; grp.ny[0] = (M + td - 1) / td; grp.nz[0] = 1;
+      grp.nx[1] = (K + 31) / 32; grp.ny[1] = (N + 31) / 32; grp.nz[1] = nz;
+      grp.blk0[0] = 0;
+      grp.blk0[1] = grp.nx[0] * grp.ny[0];
+      grp.blk0[2] = grp.blk0[1] + grp.nx[1] * grp.ny[1] * nz;
+      const dim3 grid(grp.blk0[2]);
+      switch (path) {
+        case MMVAE_GEMM_LINBWD_R_64_T16: hipLaunchKernelGGL((rgemm_grouped_kernel<64, 16, true>), grid, dim3(512), 0, st, grp); break;
+        case MMVAE_GEMM_LINBWD_R_64_T32: hipLaunchKernelGGL((rgemm_grouped_kernel<64, 16, false>), grid, dim3(512), 0, st, grp); break;
+        case MMVAE_GEMM_LINBWD_R_16_T16: hipLaunchKernelGGL((rgemm_grouped_kernel<16, 16, true>), grid, dim3(512), 0, st, grp); break;
+        case MMVAE_GEMM_LINBWD_R_16_T32: hipLaunchKernelGGL((rgemm_grouped_kernel<16, 16, false>), grid, dim3(512), 0, st, grp); break;
+        case MMVAE_GEMM_LINBWD_STAGED: hipLaunchKernelGGL(gemm_grouped_kernel, grid, dim3(256), 0, st, grp); break;
+        default: return MMVAE_ERR_UNSUPPORTED;
+      }
+    }
   }
-  if (linear_bwd_rgemm(M, N)) {
-    if (!rgemm_aligned(dy, N, N)) return MMVAE_ERR_ARG;   // this regime needs a 16-byte aligned dy
-    GemmGroup grp;
-    GemmArgs& gd = grp.g[0];
-    gd.A = dy; gd.B = w; gd.bias = nullptr; gd.aux = const_cast<float*>(aux); gd.C = dx; gd.a_rowsum = nullptr; gd.ws = nullptr;
-    gd.M = M; gd.N = K; gd.K = N; gd.sam = N; gd.sak = 1; gd.sbk = K; gd.sbn = 1; gd.ldc = K;
-    gd.a_act = MMVAE_ACT_NONE; gd.b_act = MMVAE_ACT_NONE; gd.ep = ep_mode; gd.accumulate = 0; gd.kper = N;
-    GemmArgs& gw = grp.g[1];
-    gw.A = dy; gw.B = x; gw.bias = nullptr; gw.aux = nullptr; gw.C = dw; gw.a_rowsum = db; gw.ws = nullptr;
-    gw.M = N; gw.N = K; gw.K = M; gw.sam = 1; gw.sak = N; gw.sbk = ldx; gw.sbn = 1; gw.ldc = K;
-    gw.a_act = MMVAE_ACT_NONE; gw.b_act = x_act; gw.ep = MMVAE_EP_NONE; gw.accumulate = accumulate ? 1 : 0; gw.kper = M;
-    grp.n = 2;
-    const bool t16 = (long)((M + 31) / 32) * ((K + 31) / 32) <= 128;   // data gradient on 16 x 16 tiles
-    const int td = t16 ? 16 : 32;
-    grp.nx[0] = (K + td - 1) / td; grp.ny[0] = (M + td - 1) / td; grp.nz[0] = 1;
-    grp.nx[1] = (K + 31) / 32; grp.ny[1] = (N + 31) / 32; grp.nz[1] = 1;
-    grp.blk0[0] = 0;
-    grp.blk0[1] = grp.nx[0] * grp.ny[0];
-    grp.blk0[2] = grp.blk0[1] + grp.nx[1] * grp.ny[1];
-    const dim3 rgrid(grp.blk0[2]);
-    hipStream_t st = (hipStream_t)stream;
-    const bool deep = rgemm_depth(N) == 64;
-    if (deep && t16) hipLaunchKernelGGL((rgemm_grouped_kernel<64, 16, true>), rgrid, dim3(512), 0, st, grp);
-    else if (deep) hipLaunchKernelGGL((rgemm_grouped_kernel<64, 16, false>), rgrid, dim3(512), 0, st, grp);
-    else if (t16) hipLaunchKernelGGL((rgemm_grouped_kernel<16, 16, true>), rgrid, dim3(512), 0, st, grp);
-    else hipLaunchKernelGGL((rgemm_grouped_kernel<16, 16, false>), rgrid, dim3(512), 0, st, grp);
-    return mmvae_launch_status();
-  }
-  const long t128_d = (long)((M + 127) / 128) * ((K + 31) / 32), t32_d = (long)((M + 31) / 32) * ((K + 31) / 32);
-  // (a 512-deep data gradient alone prefers the 8-wave tiling, but one grouped launch beats two: +4 % on the step)
-  const bool d_ok = t128_d < 256;
-  const int nz = mmvae_linear_bwd_weight_splits(M, N, K);
-  const long t128_w = (long)((N + 127) / 128) * ((K + 31) / 32), t32_w = (long)((N + 31) / 32) * ((K + 31) / 32);
-  const int sk = wgrad_splitk(M, N, K);
-  const bool w_ok = t128_w < 256 && !(M >= 384 && t32_w <= 512 && sk == 1);
-  if (!d_ok || !w_ok) {
-    int rc = mmvae_linear_bwd_weight(dy, x, dw, db, ws, M, N, K, ldx, x_act, accumulate, stream);
-    if (rc) return rc;
-    return mmvae_linear_bwd_data(dy, w, aux, dx, M, N, K, ep_mode, 0, stream);
-  }
-  if (nz > 1 && !ws) return MMVAE_ERR_ARG;
-  GemmGroup grp;
-  GemmArgs& gd = grp.g[0];
-  gd.A = dy; gd.B = w; gd.bias = nullptr; gd.aux = const_cast<float*>(aux); gd.C = dx; gd.a_rowsum = nullptr; gd.ws = nullptr;
-  gd.M = M; gd.N = K; gd.K = N; gd.sam = N; gd.sak = 1; gd.sbk = K; gd.sbn = 1; gd.ldc = K;
-  gd.a_act = MMVAE_ACT_NONE; gd.b_act = MMVAE_ACT_NONE; gd.ep = ep_mode; gd.accumulate = 0;
-  gd.kper = (N + 127) / 128 * 128;
-  GemmArgs& gw = grp.g[1];
-  gw.A = dy; gw.B = x; gw.bias = nullptr; gw.aux = nullptr; gw.C = dw; gw.a_rowsum = db; gw.ws = ws;
-  gw.M = N; gw.N = K; gw.K = M; gw.sam = 1; gw.sak = N; gw.sbk = ldx; gw.sbn = 1; gw.ldc = K;
-  gw.a_act = MMVAE_ACT_NONE; gw.b_act = x_act; gw.ep = MMVAE_EP_NONE; gw.accumulate = accumulate ? 1 : 0;
-  int kper = (M + sk - 1) / sk;
-  kper = (kper + 127) / 128 * 128;
-  gw.kper = kper;
-  grp.n = 2;
-  grp.nx[0] = (K + 31) / 32; grp.ny[0] = (M + 31) / 32; grp.nz[0] = 1;
-  grp.nx[1] = (K + 31) / 32; grp.ny[1] = (N + 31) / 32; grp.nz[1] = nz;
-  grp.blk0[0] = 0;
-  grp.blk0[1] = grp.nx[0] * grp.ny[0];
-  grp.blk0[2] = grp.blk0[1] + grp.nx[1] * grp.ny[1] * nz;
-  hipLaunchKernelGGL(gemm_grouped_kernel, dim3(grp.blk0[2]), dim3(256), 0, (hipStream_t)stream, grp);
   int rc = mmvae_launch_status();
   if (rc) return rc;
   if (nz > 1 && accumulate != MMVAE_ACC_DEFER) {

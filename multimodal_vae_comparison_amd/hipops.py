@@ -174,6 +174,10 @@ SIGNATURES = {
     "mmvae_gemm_f32": (c_i, [c_p] * 7 + [c_i] * 3 + [c_l] * 5 + [c_i] * 5 + [c_p]),
     "mmvae_gemm_ws_floats": (c_sz, [c_i] * 3),
     "mmvae_gemm_splits": (c_i, [c_i] * 4),
+    "mmvae_gemm_path": (c_i, [c_i] * 3 + [c_l] * 5 + [c_i] * 8 + [ctypes.POINTER(c_i)] * 2),
+    "mmvae_linear_fwd_path": (c_i, [c_i] * 3 + [c_l] + [c_i] * 5),
+    "mmvae_linear_bwd_weight_path": (c_i, [c_i] * 3 + [c_l] + [c_i] * 5 + [ctypes.POINTER(c_i)] * 2),
+    "mmvae_linear_bwd_path": (c_i, [c_i] * 3 + [c_l] + [c_i] * 7 + [ctypes.POINTER(c_i)] * 2),
     "mmvae_bias_group_add": (c_i, [c_p, c_p, c_i, c_i, c_i, c_p]),
     "mmvae_bias_group_grad": (c_i, [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p]),
     "mmvae_bias_group_ws_floats": (c_sz, [c_i, c_i]),

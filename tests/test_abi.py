@@ -64,6 +64,17 @@ def test_pure_queries_run_without_gpu():
     assert L.mmvae_gemm_ws_floats(64, 64, 4) == 4 * (64 * 64 + 64)
     assert L.mmvae_conv_wgrad_ws_floats(128, 32, 32, 16) > 0
     assert L.mmvae_poe_ws_floats(128, 32) >= 32
+    # the GEMM dispatch rule as a query: a code of the header's enum (>= 16), the split plan, negated errors
+    nz, kper = ctypes.c_int(0), ctypes.c_int(0)
+    assert L.mmvae_gemm_path(128, 512, 512, 512, 1, 1, 512, 512, 1, 0, 0, 0, 1, 0, 1, 1, ctypes.byref(nz), ctypes.byref(kper)) >= 16
+    assert (nz.value, kper.value) == (1, 512)
+    assert L.mmvae_gemm_path(0, 512, 512, 512, 1, 1, 512, 512, 1, 0, 0, 0, 1, 0, 1, 1, None, None) == -hipops.ERR_ARG
+    assert L.mmvae_gemm_path(8, 8, 8, 16, 2, 1, 8, 8, 0, 0, 0, 0, 1, 0, 1, 1, None, None) == -hipops.ERR_UNSUPPORTED
+    assert L.mmvae_linear_fwd_path(128, 512, 512, 512, 1, 0, 1, 1, 1) >= 16
+    assert L.mmvae_linear_bwd_weight_path(4096, 162, 54, 54, 0, 0, 1, 1, 1, ctypes.byref(nz), ctypes.byref(kper)) >= 16
+    assert nz.value == L.mmvae_linear_bwd_weight_splits(4096, 162, 54) > 1
+    assert L.mmvae_linear_bwd_path(128, 512, 512, 512, 1, 3, 0, 1, 1, 1, 1, ctypes.byref(nz), ctypes.byref(kper)) >= 16
+    assert nz.value == L.mmvae_linear_bwd_splits(128, 512, 512) == 1
 
 
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):

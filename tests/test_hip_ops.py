@@ -231,17 +231,73 @@ def test_split_bf16_non_finite_inputs(ops, hip_lib, kind, B, C, Hin):
         assert e <= 2e-6, (name, e)
 
 
+_DACT_EP = {0: 0, 1: 3, 2: 2, 3: 5}      # the data gradient's epilogue behind an input activation (MMVAE_EP_MUL_*_GRAD)
+
+
+def _linear_kernels(M, K, N, act):
+    """the kernels ops.linear's calls land on, as the library's own dispatch queries name them (tests/gemm_reference.py
+    PATHS): (forward, grouped backward), and behind LINBWD_TWO the weight and data gradient launches"""
+    import gemm_reference as GR
+    from multimodal_vae_comparison_amd import hipops
+    lib = hipops.lib()
+    out = [GR.PATH_NAME[lib.mmvae_linear_fwd_path(M, N, K, K, act, 0, 1, 1, 1)],
+           GR.PATH_NAME[lib.mmvae_linear_bwd_path(M, N, K, K, act, _DACT_EP[act], 0, 1, 1, 1, 1, None, None)]]
+    if out[1] == "LINBWD_TWO":
+        out.append(GR.PATH_NAME[lib.mmvae_linear_bwd_weight_path(M, N, K, K, act, 0, 1, 1, 1, None, None)])
+        out.append(GR.PATH_NAME[lib.mmvae_gemm_path(M, K, N, N, 1, K, 1, K, 0, 0, _DACT_EP[act], 0, 1, 0, 1, 1, None, None)])
+    return tuple(out)
+
+
+# what the comments beside the shapes below claim, as a check (the split-bf16 core never takes these: fewer than 2048 rows,
+# more than 4096, or a dimension below 128)
+_LINEAR_KERNELS = {
+    (7680, 400, 400, 2): ("BIG64_KK", "LINBWD_TWO", "BIG64_MN", "BIG64_KN"),
+    (7680, 400, 784, 2): ("BIG64_KK", "LINBWD_TWO", "BIG64_MN", "BIG64_KN"),
+    (7680, 20, 400, 0): ("BIG64_KK", "LINBWD_STAGED"),
+    (6144, 576, 64, 2): ("R32_64_VV", "LINBWD_TWO", "RSPLIT_64", "BIG64_KN"),
+    (32000, 56, 160, 0): ("BIG64_KK", "LINBWD_TWO", "RSPLIT_64", "STAGED1_KN"),
+    (1000, 2048, 512, 2): ("STAGED8_KK", "LINBWD_R_64_T32"),
+    (520, 1024, 256, 3): ("R32_64_VV", "LINBWD_R_16_T32"),
+    (3844, 36, 132, 1): ("R32_16_VV", "LINBWD_STAGED"),
+    (1000, 512, 512, 2): ("R32_64_VV", "LINBWD_R_64_T32"),
+    (512, 512, 512, 0): ("R32_64_VV", "LINBWD_R_64_T32"),
+    (1000, 32, 512, 0): ("R32_16_VV", "LINBWD_R_64_T16"),
+    (996, 512, 64, 1): ("R16_64_VV", "LINBWD_R_16_T32"),
+    (300, 516, 100, 1): ("R16_64_VV", "LINBWD_R_16_T32"),
+    (12800, 32, 96, 0): ("PROJ32", "LINBWD_STAGED"),
+    (1030, 32, 32, 0): ("PROJ32", "LINBWD_STAGED"),
+    (3200, 32, 128, 0): ("PROJ32", "LINBWD_STAGED"),
+    (2049, 32, 64, 0): ("PROJ32", "LINBWD_STAGED"),
+    # test_linear_small_batch_paths
+    (1, 4, 1, 0): ("R16_16_VV", "LINBWD_STAGED"),
+    (17, 20, 33, 1): ("R16_16_VV", "LINBWD_STAGED"),
+    (128, 1024, 64, 0): ("R16_64_VV", "LINBWD_R_16_T16"),
+    (256, 36, 512, 2): ("R16_16_VV", "LINBWD_R_64_T16"),
+    (130, 516, 100, 1): ("R16_64_VV", "LINBWD_R_16_T16"),
+    (64, 54, 54, 0): ("R16_16_SS", "LINBWD_STAGED"),
+    (3, 1028, 5, 0): ("STAGED8_KK", "LINBWD_STAGED"),
+    (200, 8, 8, 3): ("R16_16_VV", "LINBWD_R_16_T16"),
+    (16, 512, 2048, 1): ("R16_64_VV", "LINBWD_R_64_T16"),
+}
+
+
 @pytest.mark.parametrize("M,K,N,act", [(128, 512, 512, 1), (6, 8, 512, 0), (7, 512, 64, 2), (4096, 54, 162, 0),
                                        (160, 128, 54, 3), (33000, 54, 128, 0), (5, 54, 16, 0), (300, 32, 27, 0),
-                                       # the large-tile kernel (gemm_big_kernel): MNIST towers at K*B rows, ResNet shapes,
-                                       # ragged edges in M / N / K, every orientation through fwd / dgrad / wgrad
+                                       # the large-tile kernel (gemm_big_kernel, 128 x 64 tiles): MNIST towers at K*B rows,
+                                       # ResNet shapes, ragged edges in M / N / K; of the four below the first, second,
+                                       # fourth and sixth reach it (forward, data or weight gradient), the others the staged
+                                       # and register-operand kernels (_LINEAR_KERNELS; the 128 x 128 tiles and the
+                                       # m-major / k-major orientation are tests/test_gemm_gpu.py's)
                                        (7680, 400, 400, 2), (7680, 400, 784, 2), (7680, 20, 400, 0), (6144, 576, 64, 2),
                                        (1000, 2048, 512, 2), (32000, 56, 160, 0), (520, 1024, 256, 3), (3844, 36, 132, 1),
-                                       # 64 x 64 tiles (round 3): the 512-wide image-tower linears at batch 512 .. 1000
+                                       # the 512-wide image-tower linears at batch 512 .. 1000: the register-operand kernels
+                                       # (the 64 x 64 tiles of round 3 were removed in round 4)
                                        (1000, 512, 512, 2), (512, 512, 512, 0), (1000, 32, 512, 0), (996, 512, 64, 1), (300, 516, 100, 1),
                                        # one wave per 32 rows (round 6): the action towers' 32 -> 96 / 32 projections at 12 800 rows
                                        (12800, 32, 96, 0), (1030, 32, 32, 0), (3200, 32, 128, 0), (2049, 32, 64, 0)])
 def test_linear_fwd_bwd(ops, M, K, N, act):
+    if (M, K, N, act) in _LINEAR_KERNELS:
+        assert _linear_kernels(M, K, N, act) == _LINEAR_KERNELS[(M, K, N, act)]
     g = torch.Generator().manual_seed(M + K + N)
     x = torch.randn(M, K, generator=g)
     w = torch.randn(N, K, generator=g) / math.sqrt(K)
@@ -264,6 +320,7 @@ def test_linear_fwd_bwd(ops, M, K, N, act):
 def test_linear_small_batch_paths(ops, M, K, N, act):
     """shapes around the dispatch boundaries of the register-operand GEMMs (16x16 / 32x32 tiles, float4 vs strided
     operand loads for K % 4 != 0, reductions longer than 1024 back on the staged kernel) and the fused backward"""
+    assert _linear_kernels(M, K, N, act) == _LINEAR_KERNELS[(M, K, N, act)]
     g = torch.Generator().manual_seed(M * 7 + K * 3 + N)
     x = torch.randn(M, K, generator=g)
     w = torch.randn(N, K, generator=g) / math.sqrt(K)
@@ -304,6 +361,8 @@ def test_linear_tiled_split_bf16_is_fp32_equivalent(ops, hip_lib, M, K, N, act):
         for core in (1, 0):
             hip_lib.mmvae_gemm_b16_set(core)
             assert hip_lib.mmvae_linear_bwd_splits(M, N, K) >= 1
+            # the switch decides the core: split-bf16 forward and grouped backward with it on, none of either with it off
+            assert [p.startswith(("B16_", "LINBWD_B16_")) for p in _linear_kernels(M, K, N, act)[:2]] == [bool(core)] * 2
             for preset in (False, True):
                 xg, wg, bg = (t.to(DEV).requires_grad_(True) for t in (x, w, b))
                 gw = torch.ones(N, K, device=DEV) if preset else None
