@@ -1359,6 +1359,50 @@ int mmvae_kid_sums(const float* X, const float* Y, const int* idx_x, const int* 
                    mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Kernel two-sample test of latents (TorchMMVAE.latent_two_sample; csrc/mmd.hip): the sums behind the unbiased MMD^2
+ * (Gretton et al. 2012) of X (n_x, D) against Y (n_y, D), fp32 rows, for the observed split and for P relabellings of the
+ * pooled sample (X's rows, then Y's; n = n_x + n_y).  member (P, n) bytes: row p marks with 1 the pooled rows that count as
+ * "X" under relabelling p (n_x ones per row: the caller checks; NULL with P = 0).  With d^2 = |x - y|^2:
+ *   MMVAE_MMD_RBF     k = (1 / S) sum_s exp(-params[s] d^2)             (params: the S rates gamma_s)
+ *   MMVAE_MMD_IMQ     k = (1 / S) sum_s params[s] / (params[s] + d^2)   (params: the S constants c_s)
+ *   MMVAE_MMD_ENERGY  k = -d                                            (params and S are not read)
+ * params is a HOST array of S finite positive doubles (anything else: MMVAE_ERR_ARG).
+ *   sums (1 + P, 3) doubles: row 0 the observed split, row 1 + p relabelling p, each
+ *     [sum_{i != j, both X} k_ij, sum_{i != j, both Y} k_ij, sum_{i in X, j in Y} k_ij]   (the layout of mmvae_kid_sums)
+ *   row_sums (n) doubles: r_i = sum_{j != i} k_ij.  The diagonal is left out by POSITION.
+ *   Arithmetic: rows centred by the pooled mean in double (the families are translation invariant), d^2 = max(0, (|z_i|^2
+ *   + |z_j|^2) - 2 z_i . z_j) with the Gram tiles of csrc/pair_tile.hpp on v_mfma_f64_16x16x4_f64 and |z_i|^2 taken from
+ *   the diagonal of the same tiles; a pair whose d^2 comes out below a quarter of |z_i|^2 + |z_j|^2 (the Gram form has
+ *   cancelled: close rows of a wide sample) is computed again by differences, so rows with equal bits give d = 0 exactly
+ *   and clusters far apart cost no accuracy.  Per split with indicator a: r = K 1,
+ *   T = 1' r, sxx = a' K a, sxy = (1 - a)' K a, each a sum of its own terms, syy = (T - sxx) - 2 sxy.  K a: every 64 x 64
+ *   tile of K, in LDS, times
+ *   the 64 x MMVAE_MMD_PBLOCK block of indicator columns (column 0 the observed split, 1 + p relabelling p) on the same
+ *   MFMA, dotted with the row tile's indicators (and their complement) and summed over a chunk of column tiles; blocks of columns are on the grid
+ *   and the first of them also adds the rows of every tile (r).  The n x n matrix is never written.  Three small launches merge the partials in a fixed order.  No atomics: two runs with one plan give the
+ *   same bits, a split's row does not depend on its position in `member` or on P; two chunk plans agree to rounding only.
+ *   chunks: 0 = the default plan, mmvae_mmd_chunks(n) = min(ceil(512 / tiles), ceil(tiles / 4)), tiles = ceil(n / 64) (a
+ *     function of n alone); a positive value asks for that many (at most one per column tile).
+ *   ws: mmvae_mmd_ws_doubles(n, D, P, chunks) doubles (centred rows, norms, partials, packed indicators).
+ *   2 <= n_x, n_y, n <= MMVAE_MMD_MAX_ROWS, 1 <= D <= MMVAE_MMD_MAX_D, 0 <= P <= MMVAE_MMD_MAX_PERMUTATIONS, 1 <= S <=
+ *   MMVAE_MMD_MAX_SCALES, chunks >= 0; anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.  The two helpers
+ *   are host functions (0 outside the limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_MMD_MAX_ROWS 16384
+#define MMVAE_MMD_MAX_D 256
+#define MMVAE_MMD_MAX_PERMUTATIONS 2048
+#define MMVAE_MMD_MAX_SCALES 8
+#define MMVAE_MMD_PBLOCK 128
+#define MMVAE_MMD_RBF 0
+#define MMVAE_MMD_IMQ 1
+#define MMVAE_MMD_ENERGY 2
+int mmvae_mmd_chunks(long n);
+size_t mmvae_mmd_ws_doubles(long n, int D, int P, int chunks);
+int mmvae_mmd_sums(const float* X, const float* Y, const unsigned char* member, double* ws, double* sums, double* row_sums,
+                   long n_x, long n_y, int D, int P, int family, const double* params, int S, int chunks,
+                   mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Cross-modal correlation of generations (TorchMMVAE.cross_modal_correlation; csrc/cca.hip): the canonical-correlation
  * score of image-caption models (Shi et al. 2019), the arithmetic of the reference's cca / apply_weights / apply_pc
  * (eval/mnistsvhn_helper.py:26-78, 149-177), in double, no atomics, every sum in a fixed order: two runs give the same bits.

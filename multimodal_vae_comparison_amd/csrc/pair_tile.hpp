@@ -1,7 +1,8 @@
-// The fp64 pair-tile walker shared by manifold.hip (squared distances) and kid.hip (polynomial kernel values): a workgroup of
-// 256 threads owns 64 row positions and walks a range of 64-wide column tiles of a matrix of dot products g_ij = b_i . a_j of
-// fp32 rows, converted to double on load; every finished tile goes through LDS to the caller's epilogue and the matrix is
-// never written to memory.  g_ij has one summation order: features in order, no split over F.
+// The fp64 pair-tile walker shared by manifold.hip (squared distances), kid.hip (polynomial kernel values) and mmd.hip
+// (kernel values of centred rows, times blocks of indicators): a workgroup of 256 threads owns 64 row positions and walks a
+// range of 64-wide column tiles of a matrix of dot products g_ij = b_i . a_j of rows (fp32, or double where a caller keeps
+// them so: the type that Rows::b returns), converted to double on load; every finished tile goes through LDS to the caller's
+// epilogue and the matrix is never written to memory.  g_ij has one summation order: features in order, no split over F.
 //   v_mfma_f64_16x16x4_f64 (f64_tile.hpp: f64_mfma_slab; lane layout there), 64 x 64 tile per workgroup, 32 x 32 per wave,
 //   32 features per staged step.
 //   Staging: a thread holds the features k0 + tid % 32 of the rows tid / 32 + 8 e, e < 8, of each operand.  The fp32 elements
@@ -13,11 +14,11 @@
 //   the four quarters of a row are four neighbouring lanes.
 // The callers differ in two policies, every member __forceinline__ (Rows is taken by value: the walker owns its copy):
 //   Rows      columns(j0)                 before the first fetch of the column tile at j0
-//             b(e, k0), a(e, j0, k0)      the thread's fp32 element e of the step at feature k0: feature k0 + tid % 32 of row
+//             b(e, k0), a(e, j0, k0)      the thread's element e (fp32 or double) of the step at feature k0: feature k0 + tid % 32 of row
 //                                         tid / 32 + 8 e of the row tile / of the column tile at j0; 0 outside the operand
 //                                         (e is a constant after unrolling)
 //   Epilogue  stage(t)                    before the values of column tile t are written (what its readers need beside it)
-//             column(t, cj)               what the values of column cj of the tile share (read once per column)
+//             column(t, cj)               what the values of column cj of the tile share (read once per column; any type)
 //             element(col, ci, g)         the value of the tile at row ci of that column from its dot product g
 //             tile(lds, t)                after the barrier behind the writes: the thread takes its quarter of its row
 #pragma once
@@ -58,7 +59,8 @@ __device__ __forceinline__ void pair_tile_walk(Rows rows, Epilogue& epi, int F, 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = (wave >> 1) * 32, wn = (wave & 1) * 32, lr = lane & 15, lk = lane >> 4;
   const int frow = tid / PT_KT, fk = tid % PT_KT;
-  float pb[PT_LOADS], pa[PT_LOADS];
+  using elem_t = decltype(rows.b(0, 0));      // fp32 (manifold, kid) or double (mmd: rows centred in double)
+  elem_t pb[PT_LOADS], pa[PT_LOADS];
   auto fetch = [&](long j0, int k0) {
 #pragma unroll
     for (int e = 0; e < PT_LOADS; ++e) {
@@ -95,7 +97,7 @@ __device__ __forceinline__ void pair_tile_walk(Rows rows, Epilogue& epi, int F, 
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
       const int cj = wn + 16 * ni + lr;
-      const double col = epi.column(t, cj);
+      const auto col = epi.column(t, cj);
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll

@@ -107,6 +107,9 @@ IQ_MIN_WIN, IQ_MAX_WIN, IQ_MAX_SIDE, IQ_MAX_CHANNELS, IQ_MAX_SCALES, IQ_MAX_ROWS
 TQ_MAX_STEPS, TQ_MAX_VOCAB, TQ_MAX_ORDER, TQ_MAX_ROWS = 256, 256, 4, 2 ** 26 - 1    # csrc/text_quality.hip
 RETRIEVAL_MAX_ROWS, RETRIEVAL_MAX_DIM, RETRIEVAL_MAX_SETS, RETRIEVAL_MAX_PAIRS, RETRIEVAL_MAX_KEEP = 16384, 256, 16, 240, 16      # csrc/retrieval.hip
 RETRIEVAL_METRICS = {"l2": 0, "cosine": 1, "w2": 2, "skl": 3}      # MMVAE_RETRIEVAL_*; w2 and skl need the scales
+MMD_MAX_ROWS, MMD_MAX_D, MMD_MAX_PERMUTATIONS, MMD_MAX_SCALES = 16384, 256, 2048, 8      # csrc/mmd.hip
+MMD_PBLOCK, MMD_EXTRA_COLUMNS = 128, 1      # indicator columns per workgroup; the observed split is column 0 of the first
+MMD_KERNELS = {"rbf": 0, "imq": 1, "energy": 2}      # MMVAE_MMD_*
 
 
 class LmeRows(ctypes.Structure):
@@ -398,6 +401,9 @@ SIGNATURES = {
     "mmvae_retrieval_chunks": (c_i, [c_l, c_i]),
     "mmvae_retrieval_ws_bytes": (c_sz, [c_l, c_i, c_i, c_i]),
     "mmvae_retrieval_ranks": (c_i, [c_p] * 10 + [c_l] + [c_i] * 6 + [c_p]),
+    "mmvae_mmd_chunks": (c_i, [c_l]),
+    "mmvae_mmd_ws_doubles": (c_sz, [c_l, c_i, c_i, c_i]),
+    "mmvae_mmd_sums": (c_i, [c_p] * 6 + [c_l, c_l, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

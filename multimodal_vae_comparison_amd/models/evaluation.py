@@ -5,7 +5,8 @@ cross-modal (canonical) correlation of generations, the cluster analysis of the 
 generated images against the images they were generated for (PSNR, SSIM, MS-SSIM) and of generated text against the captions
 it was generated for (error rates, BLEU, ROUGE-L, perplexity), the cross-modal retrieval of latents (recall@k, median
 rank, MRR), and the ex-post density estimation of the latents (a Gaussian mixture per conditioning subset, and draws from it
-for the joint metrics).  What they share is here once: the
+for the joint metrics), and the kernel two-sample tests of the latents against the prior, each other and a fitted density
+(MMD^2 with a permutation null).  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -542,6 +543,85 @@ class EvaluationMixin:
             loc, scale = self.pz_params
             joint_eps = ((z.double() - loc.double()) / scale.double()).float()      # (one rounding)
         return {"latents": z, "components": comp, "joint_eps": joint_eps}
+
+    # ---- kernel two-sample tests of the latents ---------------------------------------------------
+    def latent_two_sample(self, batches, given=None, kernel="rbf", scales=ops.MMD_SCALES, permutations=1000, seed=0,
+                          eps=None, density=None):
+        """How far apart are sets of latents, as distributions?  Kernel two-sample tests (Gretton et al. 2012;
+        ops.mmd_two_sample, csrc/mmd.hip: unbiased MMD^2 in float64, a permutation null of `permutations` relabellings
+        drawn by ops.mmd_draw(n_x, n_y, permutations, seed)).  `kernel`: "rbf" (InfoVAE's Gaussian family), "imq" (the
+        WAE's inverse multiquadratics), both with the widths `scales` x the mean squared distance of the pooled sample, or
+        "energy" (k = -d, the energy distance).  `batches`: an iterable of batch dicts; `given`: modality-name lists
+        (default_given()), keys "+".join(names).  With Z_s the N rows latents_for gives for subset s over the batches
+        (all subsets first, in the order of `given`; DMVAE: its shared code):
+          "prior"[key]        Z_s against N draws of the prior p(z) = Normal(*pz_params), made after the latents, per subset
+                              in order, as joint_coherence makes its latents (`eps` (N, D): those draws, for every subset)
+                              -- the prior hole: which models need fit_latent_density before joint generation
+          "pairs"[ka|kb]      for every unordered pair of subsets, Z_a's EVEN rows against Z_b's ODD rows -- the modality
+                              gap.  The split is the point: a permutation test assumes two independent samples, and the two
+                              posteriors of ONE input are not independent; the halves never share an input.
+          "density"[key]      with `density` = a result of fit_latent_density: Z_s of these (held-out) batches against N
+                              draws sample_latent_density(density[key], N, seed) -- did the fitted density close the gap?
+                              (made after the prior draws, per subset in order; subsets the fit does not hold are left out)
+        -> {"prior": {...}, "pairs": {...}, "density": {...} | None, "n": N}; every entry {"mmd2" (unbiased, may be
+            negative), "p_value" = (1 + #{null >= mmd2}) / (1 + P), "null_mean", "null_std", "z", "params", "n_x", "n_y"}.
+        Needs eval mode, 4 <= N <= 8192 rows, D <= 256.  Runs without gradients; the draws come from the evaluation generator
+        or `eps_override`: the training noise state, the dropout counters, gradients and the optimiser stay as they are."""
+        who = "latent_two_sample"
+        self._need_eval(who, _LATENTS)
+        names, batches, H = list(self.vaes.keys()), list(batches), ops.H
+        if not batches:
+            raise ValueError(f"{who}: `batches` is empty")
+        if kernel not in H.MMD_KERNELS:
+            raise ValueError(f"{who}: kernel = {kernel!r} (one of {', '.join(H.MMD_KERNELS)})")
+        permutations = int(permutations)
+        if not 0 <= permutations <= H.MMD_MAX_PERMUTATIONS:
+            raise ValueError(f"{who}: permutations = {permutations} (0 .. {H.MMD_MAX_PERMUTATIONS} are on the MI355X path)")
+        given = self.default_given() if given is None else [list(g) for g in given]
+        for g in given:
+            if not g or any(m not in names for m in g):
+                raise ValueError(f"{who}: `given` entry {g} must name modalities of this model ({names})")
+        given = [[m for m in names if m in g] for g in given]
+        keys = ["+".join(g) for g in given]
+        if not given or len(set(keys)) != len(keys):
+            raise ValueError(f"{who}: the subsets {keys} (different conditioning subsets)")
+        for batch in batches:
+            for g in given:
+                if any(m not in batch or batch[m]["data"] is None for m in g):
+                    raise ValueError(f"{who}: `given` entry {g} names a modality without data")
+        N, D = sum(len(b[given[0][0]]["data"]) for b in batches), self.n_latents
+        if not 4 <= N <= H.MMD_MAX_ROWS // 2 or not 1 <= D <= H.MMD_MAX_D:
+            raise ValueError(f"{who}: {N} rows of {D} latent dimensions (4 .. {H.MMD_MAX_ROWS // 2} rows -- a pair keeps half "
+                             f"of each set, a prior comparison pools twice as many -- of 1 .. {H.MMD_MAX_D} dimensions are on "
+                             f"the MI355X path)")
+        if density is not None and (not isinstance(density, dict) or not any(k in density for k in keys)):
+            raise ValueError(f"{who}: density is a result of fit_latent_density with an entry for one of {keys}")
+        if eps is not None and (not torch.is_tensor(eps) or eps.numel() != N * D):
+            raise ValueError(f"{who}: eps is {tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}; the (N, D) = "
+                             f"({N}, {D}) prior draws")
+        Z = [torch.cat([self.latents_for(b, g) for b in batches]).float().contiguous() for g in given]
+        with self._eval_noise():
+            priors = [self._prior_sample(N, eps, who)[0] for _ in given]
+        drawn = None if density is None else {k: self.sample_latent_density(density[k], N, seed=seed)["latents"]
+                                              for k in keys if k in density}
+        members = {}
+
+        def test(X, Y):
+            size = (X.shape[0], Y.shape[0])
+            if size not in members:
+                members[size] = torch.from_numpy(ops.mmd_draw(*size, permutations, seed)).to(X.device)
+            with torch.no_grad():
+                r = ops.mmd_two_sample(X, Y, member=members[size], kernel=kernel, scales=scales)
+            out = {k: float(r[k]) for k in ("mmd2", "p_value", "null_mean", "null_std", "z")}
+            out.update(params=r["params"], n_x=size[0], n_y=size[1])
+            return out
+
+        res = {"prior": {k: test(z, p) for k, z, p in zip(keys, Z, priors)}, "pairs": {}, "density": None, "n": N}
+        for a, b in itertools.combinations(range(len(keys)), 2):
+            res["pairs"][f"{keys[a]}|{keys[b]}"] = test(Z[a][0::2].contiguous(), Z[b][1::2].contiguous())
+        if drawn is not None:
+            res["density"] = {k: test(z, drawn[k]) for k, z in zip(keys, Z) if k in drawn}
+        return res
 
     # ---- generation coherence (DESIGN.md section 7c) ------------------------------------------------------------------
     def _image_text(self, image, text):

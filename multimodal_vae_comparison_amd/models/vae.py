@@ -36,7 +36,8 @@ MIXER_METRICS = dict.fromkeys(("latents_for", "classify_latents", "cross_coheren
                                "digit_cross_coherence", "digit_joint_coherence", "analyse_latents",
                                "frechet_distances", "manifold_metrics", "kernel_distances", "disentanglement",
                                "cross_modal_correlation", "cluster_latents", "reconstruction_quality", "text_quality",
-                               "cross_modal_retrieval", "fit_latent_density", "sample_latent_density"),
+                               "cross_modal_retrieval", "fit_latent_density", "sample_latent_density",
+                               "latent_two_sample"),
                               "the multimodal mixers")
 MIXER_METRICS["estimate_log_likelihood"] = "the multimodal mixers poe, moe and mopoe"
 

@@ -3422,3 +3422,4 @@ from .metrics.image_quality import *       # noqa: E402,F401,F403
 from .metrics.text_quality import *        # noqa: E402,F401,F403
 from .metrics.aggpost import *             # noqa: E402,F401,F403
 from .metrics.retrieval import *           # noqa: E402,F401,F403
+from .metrics.mmd import *                 # noqa: E402,F401,F403
