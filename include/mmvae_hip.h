@@ -1403,6 +1403,40 @@ int mmvae_mmd_sums(const float* X, const float* Y, const unsigned char* member, 
                    mmvae_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Sliced Wasserstein distances and marginal Kolmogorov-Smirnov tests (ops.swd_slices, TorchMMVAE.latent_transport and
+ * sliced_distances; csrc/swd.hip): X (n_x, F) and Y (n_y, F) fp32 rows are projected on L directions, every projection is
+ * sorted, and the two sorted lists of a direction are compared.  dirs (L, F) doubles on the device; dirs NULL selects AXIS
+ * MODE: L must equal F (<= MMVAE_SWD_MAX_DIRECTIONS) and direction d is coordinate d -- the projection is the float
+ * converted to double, no multiplication, exact.  Per direction l, with x_(0) <= ... <= x_(n_x - 1), y_(0) <= ... <=
+ * y_(n_y - 1) the sorted projections and N = n_x n_y:
+ *   w (L, 2) doubles: w[l][0] = W_1, w[l][1] = W_2^2 of the two empirical measures, exact for unequal sizes: the quantile
+ *     functions are steps on a grid of 1 / N, x_(i) covers [i n_y, (i + 1) n_y), y_(j) covers [j n_x, (j + 1) n_x), and
+ *     W_p^p = (1 / N) sum over overlapping (i, j) of len_ij |x_(i) - y_(j)|^p, len_ij the integer overlap.  Order of the sum:
+ *     thread t of 1024 adds the terms of i = t, t + 1024, ... with i ascending and j ascending within i; the 1024 partials are
+ *     added by the tree p[t] += p[t + o] for o = 512, 256, ..., 1; one division by N.
+ *   ks (L) 64-bit integers: the numerator of the two-sample Kolmogorov-Smirnov statistic, max over the pooled values t of
+ *     |n_y #{x <= t} - n_x #{y <= t}| (D = ks / N), taken at the last element of every run of equal values: exact under ties.
+ *   Projections: the tile routine of mmvae_f64_gemm on v_mfma_f64_16x16x4_f64 (directions as doubles, rows converted on
+ *     load), k in steps of 4 in order, no K-split: the bits of a projection depend on its row and its direction only -- not on
+ *     L, on the direction's place among the directions, on n_x or n_y; rows with equal bits project to equal bits in
+ *     whichever set they sit.
+ *   Sort: one workgroup per (direction, set), a bitonic network over the next power of two >= max(n, 256) values (+inf past
+ *     n) held in registers, exchanged by lane shuffles and, between waves, through that many doubles of dynamic LDS (64 KiB
+ *     at n = 8192).  Equal values are never exchanged; -0.0 and +0.0 compare equal and no output depends on their order.
+ *   No atomics: two runs give the same bits, and a direction's w and ks do not depend on the other directions of the call.
+ *   ws: mmvae_swd_ws_doubles(n_x, n_y, F, L) = L (n_x + n_y) doubles (the projections, sorted in place; never returned).
+ *   1 <= n_x, n_y <= MMVAE_SWD_MAX_ROWS, 1 <= F <= MMVAE_SWD_MAX_F, 1 <= L <= MMVAE_SWD_MAX_DIRECTIONS (axis mode: L == F);
+ *   anything else returns MMVAE_ERR_UNSUPPORTED and writes nothing.  The rows must be finite (the caller checks).  The helper
+ *   is a host function (0 outside the limits).
+ * ---------------------------------------------------------------------------------------------- */
+#define MMVAE_SWD_MAX_ROWS 8192          /* per set */
+#define MMVAE_SWD_MAX_F 16384            /* 3 x 64 x 64 pixels = 12288 fit */
+#define MMVAE_SWD_MAX_DIRECTIONS 1024
+size_t mmvae_swd_ws_doubles(long n_x, long n_y, int F, int L);
+int mmvae_swd_slices(const float* X, const float* Y, const double* dirs, double* ws, double* w, long long* ks,
+                     long n_x, long n_y, int F, int L, mmvae_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Cross-modal correlation of generations (TorchMMVAE.cross_modal_correlation; csrc/cca.hip): the canonical-correlation
  * score of image-caption models (Shi et al. 2019), the arithmetic of the reference's cca / apply_weights / apply_pc
  * (eval/mnistsvhn_helper.py:26-78, 149-177), in double, no atomics, every sum in a fixed order: two runs give the same bits.

@@ -110,6 +110,7 @@ RETRIEVAL_METRICS = {"l2": 0, "cosine": 1, "w2": 2, "skl": 3}      # MMVAE_RETRI
 MMD_MAX_ROWS, MMD_MAX_D, MMD_MAX_PERMUTATIONS, MMD_MAX_SCALES = 16384, 256, 2048, 8      # csrc/mmd.hip
 MMD_PBLOCK, MMD_EXTRA_COLUMNS = 128, 1      # indicator columns per workgroup; the observed split is column 0 of the first
 MMD_KERNELS = {"rbf": 0, "imq": 1, "energy": 2}      # MMVAE_MMD_*
+SWD_MAX_ROWS, SWD_MAX_F, SWD_MAX_DIRECTIONS = 8192, 16384, 1024      # csrc/swd.hip (rows per set)
 
 
 class LmeRows(ctypes.Structure):
@@ -404,6 +405,8 @@ SIGNATURES = {
     "mmvae_mmd_chunks": (c_i, [c_l]),
     "mmvae_mmd_ws_doubles": (c_sz, [c_l, c_i, c_i, c_i]),
     "mmvae_mmd_sums": (c_i, [c_p] * 6 + [c_l, c_l, c_i, c_i, c_i, c_p, c_i, c_i, c_p]),
+    "mmvae_swd_ws_doubles": (c_sz, [c_l, c_l, c_i, c_i]),
+    "mmvae_swd_slices": (c_i, [c_p] * 6 + [c_l, c_l, c_i, c_i, c_p]),
     "mmvae_avgpool_fwd": (c_i, [c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_avgpool_bwd": (c_i, [c_p, c_p, c_p] + [c_i] * 4 + [c_p]),
     "mmvae_rc_tables": (c_i, [c_p, c_p] + [c_i] * 6 + [c_p]),

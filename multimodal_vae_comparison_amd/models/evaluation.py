@@ -6,7 +6,8 @@ generated images against the images they were generated for (PSNR, SSIM, MS-SSIM
 it was generated for (error rates, BLEU, ROUGE-L, perplexity), the cross-modal retrieval of latents (recall@k, median
 rank, MRR), and the ex-post density estimation of the latents (a Gaussian mixture per conditioning subset, and draws from it
 for the joint metrics), and the kernel two-sample tests of the latents against the prior, each other and a fitted density
-(MMD^2 with a permutation null).  What they share is here once: the
+(MMD^2 with a permutation null), and the sliced Wasserstein distances and per-dimension Kolmogorov-Smirnov tests of the
+same latent sets and of generated against real rows.  What they share is here once: the
 guard (`_need_eval`), the noise context (`_eval_noise`), the joint metrics' prior sample (`_prior_sample`), the modality
 lookup (`_find_modalities`), the walk over real and generated feature sets (`_walk_generations`).  The mixers override the
 hooks `_proposal_size`, `_proposal`, `_sample`, `_unimodal` and `_joint_posterior`."""
@@ -544,6 +545,47 @@ class EvaluationMixin:
             joint_eps = ((z.double() - loc.double()) / scale.double()).float()      # (one rounding)
         return {"latents": z, "components": comp, "joint_eps": joint_eps}
 
+    def _latent_sets(self, who, batches, given, eps, density, seed, own_checks, least, most, most_dims, why):
+        """What latent_two_sample and latent_transport compare: after the guard and every argument check (`own_checks()`
+        raises the metric's own refusals, after the one of empty `batches`; `least` .. `most` rows of at most `most_dims`
+        dimensions, `why`: the clause on the row limit; all of it before the first encoder call), the rows Z_s latents_for
+        gives for every subset over the batches (all subsets first, in the order of `given`), then N prior draws per subset
+        in order from the evaluation generator (`eps`: those draws, for every subset), then, with `density`, N draws
+        sample_latent_density(density[key], N, seed) per subset the fit holds.
+        -> (keys, [Z_s], [prior draws], {key: density draws} | None, N)"""
+        self._need_eval(who, _LATENTS)
+        names, batches = list(self.vaes.keys()), list(batches)
+        if not batches:
+            raise ValueError(f"{who}: `batches` is empty")
+        own_checks()
+        given = self.default_given() if given is None else [list(g) for g in given]
+        for g in given:
+            if not g or any(m not in names for m in g):
+                raise ValueError(f"{who}: `given` entry {g} must name modalities of this model ({names})")
+        given = [[m for m in names if m in g] for g in given]
+        keys = ["+".join(g) for g in given]
+        if not given or len(set(keys)) != len(keys):
+            raise ValueError(f"{who}: the subsets {keys} (different conditioning subsets)")
+        for batch in batches:
+            for g in given:
+                if any(m not in batch or batch[m]["data"] is None for m in g):
+                    raise ValueError(f"{who}: `given` entry {g} names a modality without data")
+        N, D = sum(len(b[given[0][0]]["data"]) for b in batches), self.n_latents
+        if not least <= N <= most or not 1 <= D <= most_dims:
+            raise ValueError(f"{who}: {N} rows of {D} latent dimensions ({least} .. {most} rows -- {why} -- of 1 .. {most_dims} "
+                             f"dimensions are on the MI355X path)")
+        if density is not None and (not isinstance(density, dict) or not any(k in density for k in keys)):
+            raise ValueError(f"{who}: density is a result of fit_latent_density with an entry for one of {keys}")
+        if eps is not None and (not torch.is_tensor(eps) or eps.numel() != N * D):
+            raise ValueError(f"{who}: eps is {tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}; the (N, D) = "
+                             f"({N}, {D}) prior draws")
+        Z = [torch.cat([self.latents_for(b, g) for b in batches]).float().contiguous() for g in given]
+        with self._eval_noise():
+            priors = [self._prior_sample(N, eps, who)[0] for _ in given]
+        drawn = None if density is None else {k: self.sample_latent_density(density[k], N, seed=seed)["latents"]
+                                              for k in keys if k in density}
+        return keys, Z, priors, drawn, N
+
     # ---- kernel two-sample tests of the latents (DESIGN.md section 7t) ---------------------------------------------------
     def latent_two_sample(self, batches, given=None, kernel="rbf", scales=ops.MMD_SCALES, permutations=1000, seed=0,
                           eps=None, density=None):
@@ -567,43 +609,19 @@ class EvaluationMixin:
             negative), "p_value" = (1 + #{null >= mmd2}) / (1 + P), "null_mean", "null_std", "z", "params", "n_x", "n_y"}.
         Needs eval mode, 4 <= N <= 8192 rows, D <= 256.  Runs without gradients; the draws come from the evaluation generator
         or `eps_override`: the training noise state, the dropout counters, gradients and the optimiser stay as they are."""
-        who = "latent_two_sample"
-        self._need_eval(who, _LATENTS)
-        names, batches, H = list(self.vaes.keys()), list(batches), ops.H
-        if not batches:
-            raise ValueError(f"{who}: `batches` is empty")
-        if kernel not in H.MMD_KERNELS:
-            raise ValueError(f"{who}: kernel = {kernel!r} (one of {', '.join(H.MMD_KERNELS)})")
+        who, H = "latent_two_sample", ops.H
+
+        def own_checks():
+            if kernel not in H.MMD_KERNELS:
+                raise ValueError(f"{who}: kernel = {kernel!r} (one of {', '.join(H.MMD_KERNELS)})")
+            if not 0 <= int(permutations) <= H.MMD_MAX_PERMUTATIONS:
+                raise ValueError(f"{who}: permutations = {int(permutations)} (0 .. {H.MMD_MAX_PERMUTATIONS} are on the MI355X "
+                                 f"path)")
+
+        keys, Z, priors, drawn, N = self._latent_sets(
+            who, batches, given, eps, density, seed, own_checks, 4, H.MMD_MAX_ROWS // 2, H.MMD_MAX_D,
+            "a pair keeps half of each set, a prior comparison pools twice as many")
         permutations = int(permutations)
-        if not 0 <= permutations <= H.MMD_MAX_PERMUTATIONS:
-            raise ValueError(f"{who}: permutations = {permutations} (0 .. {H.MMD_MAX_PERMUTATIONS} are on the MI355X path)")
-        given = self.default_given() if given is None else [list(g) for g in given]
-        for g in given:
-            if not g or any(m not in names for m in g):
-                raise ValueError(f"{who}: `given` entry {g} must name modalities of this model ({names})")
-        given = [[m for m in names if m in g] for g in given]
-        keys = ["+".join(g) for g in given]
-        if not given or len(set(keys)) != len(keys):
-            raise ValueError(f"{who}: the subsets {keys} (different conditioning subsets)")
-        for batch in batches:
-            for g in given:
-                if any(m not in batch or batch[m]["data"] is None for m in g):
-                    raise ValueError(f"{who}: `given` entry {g} names a modality without data")
-        N, D = sum(len(b[given[0][0]]["data"]) for b in batches), self.n_latents
-        if not 4 <= N <= H.MMD_MAX_ROWS // 2 or not 1 <= D <= H.MMD_MAX_D:
-            raise ValueError(f"{who}: {N} rows of {D} latent dimensions (4 .. {H.MMD_MAX_ROWS // 2} rows -- a pair keeps half "
-                             f"of each set, a prior comparison pools twice as many -- of 1 .. {H.MMD_MAX_D} dimensions are on "
-                             f"the MI355X path)")
-        if density is not None and (not isinstance(density, dict) or not any(k in density for k in keys)):
-            raise ValueError(f"{who}: density is a result of fit_latent_density with an entry for one of {keys}")
-        if eps is not None and (not torch.is_tensor(eps) or eps.numel() != N * D):
-            raise ValueError(f"{who}: eps is {tuple(eps.shape) if torch.is_tensor(eps) else type(eps).__name__}; the (N, D) = "
-                             f"({N}, {D}) prior draws")
-        Z = [torch.cat([self.latents_for(b, g) for b in batches]).float().contiguous() for g in given]
-        with self._eval_noise():
-            priors = [self._prior_sample(N, eps, who)[0] for _ in given]
-        drawn = None if density is None else {k: self.sample_latent_density(density[k], N, seed=seed)["latents"]
-                                              for k in keys if k in density}
         members = {}
 
         def test(X, Y):
@@ -614,6 +632,47 @@ class EvaluationMixin:
                 r = ops.mmd_two_sample(X, Y, member=members[size], kernel=kernel, scales=scales)
             out = {k: float(r[k]) for k in ("mmd2", "p_value", "null_mean", "null_std", "z")}
             out.update(params=r["params"], n_x=size[0], n_y=size[1])
+            return out
+
+        res = {"prior": {k: test(z, p) for k, z, p in zip(keys, Z, priors)}, "pairs": {}, "density": None, "n": N}
+        for a, b in itertools.combinations(range(len(keys)), 2):
+            res["pairs"][f"{keys[a]}|{keys[b]}"] = test(Z[a][0::2].contiguous(), Z[b][1::2].contiguous())
+        if drawn is not None:
+            res["density"] = {k: test(z, drawn[k]) for k, z in zip(keys, Z) if k in drawn}
+        return res
+
+    # ---- sliced transport distances and marginal tests of the latents ------------------------------------
+    def latent_transport(self, batches, given=None, n_directions=128, seed=0, eps=None, density=None):
+        """Which latent dimensions are off, and by how much?  The sets, the walk, the guards, the draw order and the keys of
+        latent_two_sample; per comparison the sliced Wasserstein distances of the two sets of rows (ops.sliced_wasserstein over
+        the directions ops.swd_draw(D, n_directions, seed), one set for every comparison) and the per-dimension table of
+        ops.marginal_tests (csrc/swd.hip: projections on the fp64 MFMA, sorted on the device, exact for unequal sizes):
+          "prior"[key]        Z_s against N draws of the prior (`eps` (N, D): those draws, for every subset)
+          "pairs"[ka|kb]      Z_a's EVEN rows against Z_b's ODD rows: the Kolmogorov-Smirnov p-value assumes two independent
+                              samples, and the two posteriors of ONE input are not independent; the halves never share an input
+          "density"[key]      with `density` = a result of fit_latent_density: Z_s against N draws of the fitted density
+        -> {"prior": {...}, "pairs": {...}, "density": {...} | None, "n": N}; every entry {"swd1": mean_l W_1, "swd2":
+            sqrt(mean_l W_2^2), "max_sliced1", "max_sliced2": floats; "w1", "w2" (D,): W_1 and W_2 of every latent dimension,
+            "ks" (D,): its Kolmogorov-Smirnov statistic, "ks_p" (D,): the asymptotic p-value (per dimension, uncorrected),
+            float64 host tensors; "n_x", "n_y"}.
+        Needs eval mode, 2 <= N <= 8192 rows, D <= 256.  Runs without gradients; the draws come from the evaluation generator
+        or `eps_override`: the training noise state, the dropout counters, gradients and the optimiser stay as they are."""
+        who, H = "latent_transport", ops.H
+
+        def own_checks():
+            if not 1 <= int(n_directions) <= H.SWD_MAX_DIRECTIONS:
+                raise ValueError(f"{who}: n_directions = {int(n_directions)} (1 .. {H.SWD_MAX_DIRECTIONS} are on the MI355X path)")
+
+        keys, Z, priors, drawn, N = self._latent_sets(who, batches, given, eps, density, seed, own_checks, 2, H.SWD_MAX_ROWS,
+                                                      H.MMD_MAX_D, "a pair keeps half of each set")
+        directions = torch.from_numpy(ops.swd_draw(self.n_latents, int(n_directions), seed)).to(Z[0].device)
+
+        def test(X, Y):
+            with torch.no_grad():
+                s, t = ops.sliced_wasserstein(X, Y, directions=directions), ops.marginal_tests(X, Y)
+            out = {k: float(s[k]) for k in ("swd1", "swd2", "max_sliced1", "max_sliced2")}
+            out.update({k: t[k].cpu() for k in ("w1", "w2", "ks")})
+            out.update(ks_p=torch.from_numpy(np.atleast_1d(t["ks_p"])), n_x=X.shape[0], n_y=Y.shape[0])
             return out
 
         res = {"prior": {k: test(z, p) for k, z, p in zip(keys, Z, priors)}, "pairs": {}, "density": None, "n": N}
@@ -1015,6 +1074,60 @@ class EvaluationMixin:
                         r["cross"][key[1]], r["m"]["from_{}".format(key[1])] = pair, out["m"]
                     else:
                         r[key], r["m"][key] = pair, out["m"]
+                res[m] = r
+        return res
+
+    # ---- sliced Wasserstein distance of generated rows ----------------------------------------------------
+    def sliced_distances(self, batches, features, n_directions=128, seed=0, n_joint=0, eps=None, joint_eps=None):
+        """Sliced Wasserstein distances (Rabin et al. 2011; Bonneel et al. 2015; max-sliced: Deshpande et al. 2019) between
+        the features of real and of generated rows, in float64 on the device (ops.sliced_wasserstein; csrc/swd.hip): a
+        transport distance with no kernel width and no moment estimate, exact for sets of different sizes.
+        `batches`, `features`, `n_joint`, `eps`, `joint_eps`, the sets (real, recon, cross[g], joint) and the order of the
+        forward() calls are those of frechet_distances; the fp32 rows of every set are kept until the walk ends.
+        `features[m]` may be `lambda x: x.flatten(1)`: the distance is then taken on the raw pixels and needs no classifier, no
+        labels and no weights -- which is the point.  The directions are ops.swd_draw(F, n_directions, seed), one set for every
+        modality of one feature width.
+        -> {m: {"recon": {...}, "cross": {g: {...}}, "joint": {...} | None, "n": real rows, "F": F}}, every {...} = {"swd1":
+            mean_l W_1, "swd2": sqrt(mean_l W_2^2), "max_sliced1": max_l W_1, "max_sliced2": sqrt(max_l W_2^2), floats; "n":
+            the rows of the generated set}.
+        Needs eval mode, at most 8192 rows per set, F <= 16384, 1 <= n_directions <= 1024; runs without gradients; the training
+        noise state, the dropout counters, gradients and the optimiser stay as they are."""
+        who, H = "sliced_distances", ops.H
+        n_directions, sets, drawn = int(n_directions), {}, {}
+
+        def rows_ok(rows, n_joint):
+            if not 1 <= n_directions <= H.SWD_MAX_DIRECTIONS:
+                raise ValueError(f"{who}: n_directions = {n_directions} (1 .. {H.SWD_MAX_DIRECTIONS} are on the MI355X path)")
+            if not 1 <= rows <= H.SWD_MAX_ROWS or n_joint > H.SWD_MAX_ROWS:
+                raise ValueError(f"{who}: {rows} real rows, n_joint = {n_joint} (1 .. {H.SWD_MAX_ROWS} rows per set are on the "
+                                 f"MI355X path)")
+
+        def keep_rows(f):      # a copy: a kept view would hold the extractor's whole output (rows beyond B) until the end
+            return f.detach().to(torch.float32, copy=True)
+
+        mods, dims = self._walk_generations(who, batches, features, n_joint, eps, joint_eps, rows_ok,
+                                            lambda m, key, f: sets.setdefault((m, key), []).append(keep_rows(f)))
+        res = {}
+        with torch.no_grad():
+            for m in mods:
+                real, F = torch.cat(sets[(m, "real")]), dims[m]
+                if not 1 <= F <= H.SWD_MAX_F:
+                    raise ValueError(f"{who}: the extractor of {m!r} returned F = {F} features (1 .. {H.SWD_MAX_F} are on the "
+                                     f"MI355X path)")
+                if F not in drawn:
+                    drawn[F] = torch.from_numpy(ops.swd_draw(F, n_directions, seed)).to(real.device)
+                r = {"recon": None, "cross": {}, "joint": None, "n": real.shape[0], "F": F}
+                for (mm, key), rows in sets.items():
+                    if mm != m or key == "real":
+                        continue
+                    gen = torch.cat(rows)
+                    out = ops.sliced_wasserstein(real, gen, directions=drawn[F])
+                    entry = {k: float(out[k]) for k in ("swd1", "swd2", "max_sliced1", "max_sliced2")}
+                    entry["n"] = gen.shape[0]
+                    if isinstance(key, tuple):
+                        r["cross"][key[1]] = entry
+                    else:
+                        r[key] = entry
                 res[m] = r
         return res
 

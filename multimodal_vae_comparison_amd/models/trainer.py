@@ -222,6 +222,26 @@ class MultimodalVAE(nn.Module):
                               for name, key in (("kid", "kid"), ("kid_std", "std")))
         return out
 
+    def sliced_distances(self, batches, features, **kwargs):
+        """sliced Wasserstein distances of generated rows against real ones (TorchMMVAE.sliced_distances; the model must be in
+        eval mode), logged as test_swd2_<m>_recon, test_swd2_<m>_from_<g> and test_swd2_<m>_joint"""
+        out = self.model.sliced_distances(batches, features, **kwargs)
+        for m, r in out.items():
+            self._log_metrics([("test_swd2_{}_recon".format(m), r["recon"]["swd2"])] +
+                              [("test_swd2_{}_from_{}".format(m, g), d["swd2"]) for g, d in r["cross"].items()] +
+                              ([] if r["joint"] is None else [("test_swd2_{}_joint".format(m), r["joint"]["swd2"])]))
+        return out
+
+    def latent_transport(self, batches, **kwargs):
+        """sliced Wasserstein distances and per-dimension Kolmogorov-Smirnov tests of the latents (TorchMMVAE.latent_transport;
+        the model must be in eval mode), logged per conditioning subset as test_swd2_prior_<key> and test_ks_max_prior_<key>
+        (the largest statistic over the latent dimensions)"""
+        out = self.model.latent_transport(batches, **kwargs)
+        for key, r in out["prior"].items():
+            self._log_metrics([("test_swd2_prior_{}".format(key), r["swd2"]),
+                               ("test_ks_max_prior_{}".format(key), float(r["ks"].max()))])
+        return out
+
     def disentanglement(self, batches, **kwargs):
         """ELBO decomposition and mutual information gap of the latent code (TorchMMVAE.disentanglement; the model must be
         in eval mode), logged per posterior key as test_{mi,tc,dwkl,kl}_<key> and, where labels were given, test_mig_<key>"""

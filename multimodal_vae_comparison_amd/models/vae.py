@@ -37,7 +37,7 @@ MIXER_METRICS = dict.fromkeys(("latents_for", "classify_latents", "cross_coheren
                                "frechet_distances", "manifold_metrics", "kernel_distances", "disentanglement",
                                "cross_modal_correlation", "cluster_latents", "reconstruction_quality", "text_quality",
                                "cross_modal_retrieval", "fit_latent_density", "sample_latent_density",
-                               "latent_two_sample"),
+                               "latent_two_sample", "latent_transport", "sliced_distances"),
                               "the multimodal mixers")
 MIXER_METRICS["estimate_log_likelihood"] = "the multimodal mixers poe, moe and mopoe"
 

@@ -3422,4 +3422,5 @@ from .metrics.image_quality import *       # noqa: E402,F401,F403
 from .metrics.text_quality import *        # noqa: E402,F401,F403
 from .metrics.aggpost import *             # noqa: E402,F401,F403
 from .metrics.retrieval import *           # noqa: E402,F401,F403
+from .metrics.swd import *                 # noqa: E402,F401,F403
 from .metrics.mmd import *                 # noqa: E402,F401,F403
